@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the SpGEMM hot path (C = A^2, fp64, CSR) on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--dump-outputs DIR] [--full]
 
 A "step" is one bhsparse::spgemm() over the synthetic matrix, inputs already resident in HBM: for the stencil
 workloads here that is the row-class pipeline (classify the rows of B and A -> class patterns -> scan -> numeric,
@@ -14,9 +14,17 @@ Workloads (BASELINE.json `configs`; values = gallery.fill_values, seed 20140519)
   p27_weak (default) poisson27pt, 128^3 rows per GPU: 128^3 at N=1 (configs[2]),
                      128x128x256 at N=2, 128x256x256 at N=4, 256^3 at N=8 (configs[4])
   p27_128 / p27_160 / p27_256 / p5_1024   fixed-size variants (strong scaling at N > 1)
-Prints ONE JSON line on rank 0.  At N=1 its `cpu_baseline` object holds the CPU oracle's figure on a bounded sample
-(kind "port") and, when oracle/_ref was built, `reference_opencl_same_gpu`: the reference's own OpenCL implementation
-run once on the same GPU and matrix, as timed by its own spgemm() timer.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints the headline (`value`,
+`ms_per_step` = wall time of the K timed steps / K; the roofline of the dominant kernel comes from the events of those
+same steps).  Everything else is measured only with --full: the GPU's clocks (rocm-smi), the per-family kernel times
+of three untimed multiplies, the check of the assembled C at N > 1 (and under BENCH_FORCE_GATHER), and at N=1 the
+general pipeline, the set-up and fresh-handle figures, the other BASELINE configs (`additional_configs`) and the
+`cpu_baseline` object: the CPU oracle's figure on a bounded sample (kind "port") and, when oracle/_ref was built,
+`reference_opencl_same_gpu`: the reference's own OpenCL implementation run once on the same GPU and matrix, as timed
+by its own spgemm() timer.  (--no-cpu-baseline, --no-reference, --no-extra and --no-general trim a --full run.)
+
+--dump-outputs DIR: after the timed steps, rank 0 writes the C of the last timed step as float64 .npy files
+(OUTPUT_FILES below; a fixed, seeded sample where an array is larger than its cap, < 64 MB in all).
 """
 import argparse
 import json
@@ -108,6 +116,43 @@ def device_digest(bh, m, dev):
     return d
 
 
+# --dump-outputs: what a caller of the timed multiply receives -- rowPtrC, colIndC, valC and the two counts -- as float64
+# (exact for these integers).  rowPtrC whole up to DUMP_ROWPTR_CAP entries, colIndC / valC whole up to DUMP_ENTRY_CAP;
+# beyond that the same seeded sample of DUMP_SAMPLE positions (first and last always in it), saved beside as *_index.npy.
+# At most 6 x 2^20 (+ 4) float64 values: 48 MiB.
+DUMP_ROWPTR_CAP, DUMP_ENTRY_CAP, DUMP_SAMPLE, DUMP_SEED = 3 << 20, 1 << 20, 1 << 20, 20140519
+OUTPUT_FILES = "C_rowptr.npy [C_rowptr_index.npy] C_colind.npy C_val.npy [C_entry_index.npy] C_nnz.npy (nnzCt, nnzC)"
+
+
+def dump_outputs(out_dir, rp, cc, vv, nnzCt):
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+
+    def sample(n, cap, salt):
+        if n <= cap:
+            return None
+        draw = np.random.default_rng([DUMP_SEED, salt]).integers(0, n, DUMP_SAMPLE, dtype=np.int64)
+        return np.unique(np.concatenate([draw, [0, n - 1]]))
+
+    def save(name, t, idx):
+        if idx is not None:
+            t = t.index_select(0, torch.from_numpy(idx).to(t.device))
+        np.save(os.path.join(out_dir, name + ".npy"), t.double().cpu().numpy())
+
+    nnz = int(rp[-1].item())
+    cc, vv = cc[:nnz], vv[:nnz]
+    ir = sample(int(rp.numel()), DUMP_ROWPTR_CAP, 1)
+    ie = sample(nnz, DUMP_ENTRY_CAP, 2)
+    save("C_rowptr", rp, ir)
+    save("C_colind", cc, ie)
+    save("C_val", vv, ie)
+    for name, idx in (("C_rowptr_index", ir), ("C_entry_index", ie)):
+        if idx is not None:
+            np.save(os.path.join(out_dir, name + ".npy"), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, "C_nnz.npy"), np.array([nnzCt, nnz], np.float64))
+
+
 def reference_opencl_leg(m, rp, col, val, nnzCt, mine=None):
     """One C = A^2 of the same matrix through oracle/_ref/ref_opencl_spgemm (the reference's SpGEMM_opencl, unmodified);
     `mine`: digests of this library's C for the same input -- compared with the digests of the reference's C."""
@@ -161,7 +206,13 @@ def main():
     ap.add_argument("--no-gather", action="store_true", help="N>1: skip the all-gatherv (compute-only)")
     ap.add_argument("--no-extra", action="store_true", help="N=1: skip the short runs of the other BASELINE configs")
     ap.add_argument("--no-general", action="store_true", help="N=1: skip the second headline (general pipeline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the C of the last timed step to DIR/*.npy (float64; seeded sample of large arrays)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the figures and checks beside the headline (clocks, kernel families, baselines, other configs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     import numpy as np
     import torch
@@ -336,7 +387,7 @@ def main():
     for _ in range(args.warmup):
         step()
     barrier()
-    state_before = gpu_state() if rank == 0 else None
+    state_before = gpu_state() if rank == 0 and args.full else None
     kstats = {}
     stage = np.zeros(4)
     t_compute = 0.0
@@ -357,15 +408,41 @@ def main():
         tcomp_l[i_] = bh.time_ms
     barrier()
     elapsed = time.perf_counter() - t0
+    if world > 1:
+        tt = torch.tensor([elapsed], dtype=torch.float64, device=dev)
+        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+        elapsed = float(tt.item())
+        if native is not None:
+            nnzCt_total, nnzC_total = native_totals          # the library's size exchange already summed them
+        else:
+            cnt = torch.tensor([bh.nnzCt, bh.nnzC], dtype=torch.int64, device=dev)
+            dist.all_reduce(cnt, op=dist.ReduceOp.SUM)
+            nnzCt_total, nnzC_total = int(cnt[0].item()), int(cnt[1].item())
+    else:
+        nnzCt_total, nnzC_total = bh.nnzCt, bh.nnzC
+    ms_per_step = elapsed / args.steps * 1e3
+    gflops = 2.0 * nnzCt_total / (ms_per_step * 1e6)
+    # ---- the last timed step's C, before anything else multiplies (the assembled copy at N > 1 is overwritten in place)
+    if args.dump_outputs and rank == 0:
+        if full is not None:
+            out_rp, out_cc, out_vv = full
+        else:
+            pr, pc, pv = bh.get_C_device()
+            out_rp = bdist.device_view(pr, r1 - r0 + 1, torch.int32, dev)
+            out_cc = bdist.device_view(pc, bh.nnzC, torch.int32, dev)
+            out_vv = bdist.device_view(pv, bh.nnzC, torch.float64, dev)
+        dump_outputs(args.dump_outputs, out_rp, out_cc, out_vv, nnzCt_total)
+        del out_rp, out_cc, out_vv
     kfam = {}
-    assert bh.set_option("kernel_stats", 1) == 0
-    for _ in range(3):                                        # (every rank alike: the steps of an N > 1 job are collective)
-        step()
-        for s in bh.kernel_stats():
-            if s["launches"] > 0:
-                kfam[s["name"]] = kfam.get(s["name"], 0.0) + s["ms"] / 3
-    barrier()
-    assert bh.set_option("kernel_stats", 2) == 0
+    if args.full:
+        assert bh.set_option("kernel_stats", 1) == 0
+        for _ in range(3):                                    # (every rank alike: the steps of an N > 1 job are collective)
+            step()
+            for s in bh.kernel_stats():
+                if s["launches"] > 0:
+                    kfam[s["name"]] = kfam.get(s["name"], 0.0) + s["ms"] / 3
+        barrier()
+        assert bh.set_option("kernel_stats", 2) == 0
     for i_ in range(args.steps):
         for s in bh.decode_kernel_stats(raw_stats[i_], raw_n[i_]):
             d = kstats.setdefault(s["name"], {"ms": 0.0, "launches": 0, "rows": 0, "products": 0, "nnz_out": 0,
@@ -375,11 +452,11 @@ def main():
                 d[kk] = s[kk]
         stage += np.array(stage_l[i_])
         t_compute += tcomp_l[i_]
-    state_after = gpu_state() if rank == 0 else None
+    state_after = gpu_state() if rank == 0 and args.full else None
     # ... and once UNDER LOAD (outside the timed region): rocm-smi is asked while this rank keeps multiplying for about a
     # second -- boxes of the pool differ by up to 15 % on the same build, and the clocks an idle GPU reports say nothing
     state_load = None
-    if rank == 0 and world == 1 and not args.no_general:
+    if args.full and rank == 0 and world == 1 and not args.no_general:
         import threading
         box = {}
         th = threading.Thread(target=lambda: box.update(s=gpu_state()))
@@ -397,23 +474,9 @@ def main():
         if isinstance(state_load, dict):
             state_load["multiplies_meanwhile"] = n_l
             state_load["stream_copy_GBs"] = stream_copy_GBs(dev)
-    if world > 1:
-        tt = torch.tensor([elapsed], dtype=torch.float64, device=dev)
-        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-        elapsed = float(tt.item())
-        if native is not None:
-            nnzCt_total, nnzC_total = native_totals          # the library's size exchange already summed them
-        else:
-            cnt = torch.tensor([bh.nnzCt, bh.nnzC], dtype=torch.int64, device=dev)
-            dist.all_reduce(cnt, op=dist.ReduceOp.SUM)
-            nnzCt_total, nnzC_total = int(cnt[0].item()), int(cnt[1].item())
-    else:
-        nnzCt_total, nnzC_total = bh.nnzCt, bh.nnzC
-    ms_per_step = elapsed / args.steps * 1e3
-    gflops = 2.0 * nnzCt_total / (ms_per_step * 1e6)
 
     # ---- correctness of the assembled result at N > 1 (cheap digest check on rank 0)
-    if full is not None and rank == 0:
+    if args.full and full is not None and rank == 0:
         rp, cc, vv = full
         assert int(rp[-1].item()) == nnzC_total and int(rp[0].item()) == 0
         assert bool((rp[1:] >= rp[:-1]).all())
@@ -494,7 +557,7 @@ def main():
 
     # ---- CPU baseline: the oracle (kind "port") on a bounded row-block sample, all host cores
     cpu = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         from oracle import oracle
         hBp, hBj, hBx = Bp.cpu().numpy(), Bj.cpu().numpy(), Bx.cpu().numpy()
         cores = oracle.max_threads()
@@ -547,7 +610,7 @@ def main():
     # re-runs the general pipeline), but their choice comes from bhs_set_data's scans -- `setup_ms` -- so both
     # figures are printed.
     general = None
-    if world == 1 and not args.no_general:
+    if args.full and world == 1 and not args.no_general:
         headline_digest = device_digest(bh, m, dev)
         for key in ("class_path", "wave_first", "lane_first", "direct_bins"):
             assert bh.set_option(key, 0) == 0
@@ -571,7 +634,7 @@ def main():
     # sortedness of B: the choices of the direct launches and of the class path rest on them -- plus the multiply), and
     # the spread of the steady-state figure over fresh handles in this same process
     incl_setup, fresh = None, None
-    if world == 1 and not args.no_general:
+    if args.full and world == 1 and not args.no_general:
         ts = []
         for _ in range(5):
             torch.cuda.synchronize()
@@ -607,7 +670,7 @@ def main():
 
     # ---- the other single-GPU configurations of BASELINE.json, short runs, reported beside the headline
     extra = None
-    if world == 1 and not args.no_extra and args.workload == "p27_weak":
+    if args.full and world == 1 and not args.no_extra and args.workload == "p27_weak":
         extra = {}
         bh.free_mem()
         del Ap, Aj, Ax, Bp, Bj, Bx
@@ -743,7 +806,8 @@ def main():
         # (numeric kernels: the timed steps' own events; the other families: three multiplies in front of the timed region)
         "kernels_ms_per_step": dict({k2: round(v2, 4) for k2, v2 in sorted(kfam.items())},
                                     **{k2: round(v["ms"] / max(1, v["steps"]), 4) for k2, v in sorted(kstats.items()) if v["ms"] > 0}),
-        "kernel_events_in_timed_region": "numeric kernels only (kernel_stats = 2); every family over 3 untimed multiplies behind it",
+        "kernel_events_in_timed_region": "numeric kernels only (kernel_stats = 2)" +
+                                         ("; every family over 3 untimed multiplies behind it" if args.full else ""),
         "roofline": roof, "cpu_baseline": cpu, "additional_configs": extra,
     }
     print(json.dumps(out))

@@ -4,7 +4,7 @@ This module sorts first on purpose: the launcher below is started before anythin
 touched the GPU, as one fresh child process tree (`python -m torch.distributed.run`, one rank), backend "nccl"
 (== RCCL), world_size 1.  The rank runs bench.py with BENCH_FORCE_GATHER=1: every step is spgemm() followed by
 dist.allgatherv_csr() on the library's device buffers (size exchange with all_gather_into_tensor on RCCL, local
-block copied in place), and bench.py asserts that the gathered CSR equals the local result bit for bit.  A second
+block copied in place), and bench.py --full asserts that the gathered CSR equals the local result bit for bit.  A second
 run drives the C-ABI entry bhs_allgatherv_csr (ncclGroupStart / ncclSend / ncclRecv / ncclGroupEnd issued by the
 library on its own stream) through tests/driver/spgemm -gpus 1.
 """
@@ -35,7 +35,7 @@ def _bench_rank(workload, extra_env=None):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
            os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
-           "--workload", workload, "--no-cpu-baseline", "--no-extra"]
+           "--workload", workload, "--full", "--no-cpu-baseline", "--no-extra"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stdout[-4000:] + p.stderr[-4000:]
     line = [ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1]
