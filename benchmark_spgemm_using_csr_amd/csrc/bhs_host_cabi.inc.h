@@ -110,6 +110,10 @@ int bhs_destroy(bhs_handle* h)
     release(h->bWin); release(h->bWinTab); release(h->bWinSpill);
     release(h->hubBits); release(h->hubRank); release(h->hubItems); release(h->hubSeg); release(h->hubCtl);
     release(h->spaBits);
+    release(h->maskCtl); release(h->maskQueue);
+    for (int i = 0; i < 3; ++i) release(h->maskM[i]);
+    if (h->maskHost) (void)hipHostFree(h->maskHost);
+    for (int i = 0; i < 2; ++i) if (h->maskEv[i]) (void)hipEventDestroy(h->maskEv[i]);
     if (h->hostSmall) (void)hipHostFree(h->hostSmall);
     if (h->hostRowPtr) (void)hipHostFree(h->hostRowPtr);
     for (int i = 0; i < bhs_handle::kBinStreams; ++i) {
@@ -368,6 +372,13 @@ int bhs_set_option(bhs_handle* h, const char* key, int64_t value)
     // (2: event pairs around the numeric kernels only -- what a roofline of the dominant kernel needs, at a fifth of the events;
     // timers decide nothing: what the next multiply may assume of the last one stands)
     if (!strcmp(key, "kernel_stats")) { h->kernelStats = (int)std::max<int64_t>(0, std::min<int64_t>(value, 2)); return BHS_SUCCESS; }
+    // (the masked multiply's keys decide nothing the ordinary multiply does)
+    if (!strcmp(key, "masked_max_table_log2")) {
+        if (value < 4 || value > 11) return BHS_ERR_INVALID_ARG;
+        h->maskTableLog2 = (int)value;
+        return BHS_SUCCESS;
+    }
+    if (!strcmp(key, "masked_hub_min_products")) { h->maskHubMin = std::max<int64_t>(0, value); return BHS_SUCCESS; }
     h->classSpec.valid = false;                                     // (any other option may change what a multiply decides)
     h->laneSpec.valid = false;
     if (!strcmp(key, "spec_numeric")) { h->specNumeric = value ? 1 : 0; return BHS_SUCCESS; }

@@ -1,0 +1,186 @@
+// bhs_host_masked.inc.h -- the masked multiply (bhs_spgemm_masked[_device], kernels in bhs_masked.hip.h)
+// (A part of bhsparse_hip.hip's translation unit: included there after the C-ABI of the ordinary multiply.)
+//
+// The call works beside the ordinary multiply, never through it: its counters, queues, events and (host-array entry)
+// staging copies are buffers of its own, so C of the last bhs_spgemm, the pipeline state, the class path's state and the
+// speculative-launch figures stay as they were.  Only the kernel records are replaced: bhs_get_kernel_stats reports
+// the last call, whichever it was.
+
+namespace {
+
+constexpr int kMaskHubItem = 8192;       // products per part of a hub row (k_masked_hub)
+constexpr int kMaskHubMaxParts = 1024;
+
+int masked_run(bhs_handle* h, const int* dMp, const int* dMj, int nnzM, value_t* dValC, int64_t* nnzCt_out, double* ms_out)
+{
+    const int m = h->m;
+    h->ls = h->stream;
+    h->evUsed = 0;
+    for (auto& s : h->stats) { s.launches = 0; s.ms = 0; s.rows = s.products = s.nnz_out = s.nnzA_rows = 0; }
+    if (!h->maskEv[0]) {
+        BHS_HIP(hipEventCreate(&h->maskEv[0]));
+        BHS_HIP(hipEventCreate(&h->maskEv[1]));
+    }
+    if (!h->maskHost) BHS_HIP(hipHostMalloc((void**)&h->maskHost, sizeof(int) * MS_INTS, hipHostMallocDefault));
+    BHS_TRY(ensure(h, h->maskCtl, sizeof(int) * MS_INTS));
+    BHS_TRY(ensure(h, h->maskQueue, sizeof(int2) * (size_t)kMaskBins * (size_t)std::max(m, 1)));
+    int* ctl = (int*)h->maskCtl.p;
+    const int2* queue = (const int2*)h->maskQueue.p;
+    const int cap = 1 << h->maskTableLog2;
+    MaskSpec spec;
+    spec.shortLM = std::min(kMaskShortLM, cap);
+    spec.shortP = kMaskShortP;
+    spec.waveS = std::min(kMaskWaveTab, cap);
+    spec.waveL = cap;
+    spec.hubMin = h->maskHubMin;
+    const int bSorted = h->bSorted ? 1 : 0;
+
+    BHS_HIP(hipEventRecord(h->maskEv[0], h->stream));
+    BHS_HIP(hipMemsetAsync(ctl, 0, sizeof(int) * MS_INTS, h->stream));
+    EventPair* ep = nullptr;
+    BHS_TRY(timed_begin(h, "masked_scan", &ep));
+    const long long gs = std::max<long long>(1, ((long long)m + kMaskScanRows - 1) / kMaskScanRows);
+    hipLaunchKernelGGL(k_masked_scan, dim3((unsigned)gs), dim3(256), 0, h->stream, m, h->n, nnzM, dMp, dMj, h->dAp, h->dAj,
+                       h->dBp, spec, ctl, (int2*)h->maskQueue.p);
+    BHS_HIP(hipGetLastError());
+    BHS_TRY(timed_end(h, ep));
+    const int scanStat = ep->stat;
+    h->stats[scanStat].launches++;
+    h->stats[scanStat].rows += m;
+    int* hs = h->maskHost;
+    BHS_HIP(hipMemcpyAsync(hs, ctl, sizeof(int) * MS_INTS, hipMemcpyDeviceToHost, h->stream));
+    BHS_TRY(wait_stream(h));
+    if (hs[MS_ERR]) return BHS_ERR_INVALID_ARG;                    // (nothing has touched valC)
+    unsigned long long total = 0, hubMax = 0, sums[kMaskBins];
+    memcpy(&total, hs + MS_TOTAL, 8);
+    memcpy(&hubMax, hs + MS_HUBMAX, 8);
+    memcpy(sums, hs + MS_SUMS, sizeof(sums));
+    h->stats[scanStat].products += (int64_t)total;
+    int count[kMaskBins];
+    memcpy(count, hs + MS_COUNT, sizeof(count));
+
+    auto family = [&](const char* name, int bin, auto&& launch) -> int {
+        EventPair* e = nullptr;
+        BHS_TRY(timed_begin(h, name, &e));
+        const int launches = launch();
+        BHS_HIP(hipGetLastError());
+        BHS_TRY(timed_end(h, e));
+        StatRec& r = h->stats[e->stat];
+        r.launches += launches;
+        r.rows += count[bin];
+        r.products += (int64_t)sums[bin];
+        return BHS_SUCCESS;
+    };
+    const int* Mp = dMp;
+    if (count[kMaskShort]) {
+        const int nq = count[kMaskShort];
+        BHS_TRY(family("masked_short", kMaskShort, [&] {
+            hipLaunchKernelGGL((k_masked_lds<16, kMaskShortLM, 256>), dim3((unsigned)((nq + 15) / 16)), dim3(256), 0, h->stream, nq,
+                               queue + (size_t)kMaskShort * m, Mp, dMj, h->dAp, h->dAj, h->dAx, h->dBp, h->dBj, h->dBx, bSorted, dValC);
+            return 1;
+        }));
+    }
+    if (count[kMaskWaveS] || count[kMaskWaveL]) {
+        const int nS = count[kMaskWaveS], nL = count[kMaskWaveL];
+        EventPair* e = nullptr;
+        BHS_TRY(timed_begin(h, "masked_wave", &e));
+        if (nS)
+            hipLaunchKernelGGL((k_masked_lds<64, kMaskWaveTab, 256>), dim3((unsigned)((nS + 3) / 4)), dim3(256), 0, h->stream, nS,
+                               queue + (size_t)kMaskWaveS * m, Mp, dMj, h->dAp, h->dAj, h->dAx, h->dBp, h->dBj, h->dBx, bSorted, dValC);
+        if (nL)
+            hipLaunchKernelGGL((k_masked_lds<64, kMaskHubLds, 64>), dim3((unsigned)nL), dim3(64), 0, h->stream, nL,
+                               queue + (size_t)kMaskWaveL * m, Mp, dMj, h->dAp, h->dAj, h->dAx, h->dBp, h->dBj, h->dBx, bSorted, dValC);
+        BHS_HIP(hipGetLastError());
+        BHS_TRY(timed_end(h, e));
+        StatRec& r = h->stats[e->stat];
+        r.launches += (nS ? 1 : 0) + (nL ? 1 : 0);
+        r.rows += nS + nL;
+        r.products += (int64_t)(sums[kMaskWaveS] + sums[kMaskWaveL]);
+    }
+    if (count[kMaskLong]) {
+        const int nq = count[kMaskLong];
+        BHS_TRY(family("masked_long", kMaskLong, [&] {
+            hipLaunchKernelGGL(k_masked_long, dim3((unsigned)nq), dim3(256), 0, h->stream, nq, queue + (size_t)kMaskLong * m, Mp,
+                               dMj, h->dAp, h->dAj, h->dAx, h->dBp, h->dBj, h->dBx, bSorted, dValC);
+            return 1;
+        }));
+    }
+    if (count[kMaskHub]) {
+        const int nq = count[kMaskHub];
+        const int parts = (int)std::max<unsigned long long>(1, std::min<unsigned long long>(kMaskHubMaxParts, (hubMax + kMaskHubItem - 1) / kMaskHubItem));
+        const unsigned gy = (unsigned)std::min(nq, 65535);
+        BHS_TRY(family("masked_hub", kMaskHub, [&] {
+            const int2* q = queue + (size_t)kMaskHub * m;
+            hipLaunchKernelGGL(k_masked_zero, dim3(gy), dim3(256), 0, h->stream, nq, q, Mp, dValC);
+            hipLaunchKernelGGL(k_masked_hub, dim3((unsigned)parts, gy), dim3(256), 0, h->stream, nq, q, Mp, dMj, h->dAp, h->dAj,
+                               h->dAx, h->dBp, h->dBj, h->dBx, bSorted, std::min(kMaskHubLds, cap), dValC);
+            return 2;
+        }));
+    }
+    BHS_HIP(hipEventRecord(h->maskEv[1], h->stream));
+    BHS_TRY(wait_stream(h));
+    if (nnzCt_out) *nnzCt_out = (int64_t)total;
+    if (ms_out) {
+        float ms = 0;
+        BHS_HIP(hipEventElapsedTime(&ms, h->maskEv[0], h->maskEv[1]));
+        *ms_out = ms;
+    }
+    for (size_t i = 0; i < h->evUsed; ++i) {
+        float ms = 0;
+        BHS_HIP(hipEventElapsedTime(&ms, h->evPool[i].a, h->evPool[i].b));
+        h->stats[h->evPool[i].stat].ms += ms;
+    }
+    return BHS_SUCCESS;
+}
+
+// after a failed call: nothing of it stays queued (the pipeline's own state is not touched)
+void settle(bhs_handle* h)
+{
+    (void)hipStreamSynchronize(h->stream);
+    (void)hipGetLastError();
+}
+
+int masked_check(bhs_handle* h, int nnzM)
+{
+    if (!h) return BHS_ERR_INVALID_ARG;
+    if (!h->hasData) return BHS_ERR_NOT_READY;
+    if (h->ps.open || nnzM < 0) return BHS_ERR_INVALID_ARG;          // (a split multiply owns the stream until its finish)
+    return BHS_SUCCESS;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bhs_spgemm_masked_device(bhs_handle* h, const int* d_rowPtrM, const int* d_colIndM, int nnzM, bhs_value_t* d_valC,
+                             int64_t* nnzCt_out, double* ms_out)
+{
+    BHS_TRY(masked_check(h, nnzM));
+    if (!d_rowPtrM || (nnzM > 0 && (!d_colIndM || !d_valC))) return BHS_ERR_INVALID_ARG;
+    BHS_HIP(hipSetDevice(h->device));
+    const int rc = masked_run(h, d_rowPtrM, d_colIndM, nnzM, (value_t*)d_valC, nnzCt_out, ms_out);
+    if (rc) settle(h);
+    return rc;
+}
+
+int bhs_spgemm_masked(bhs_handle* h, const int* rowPtrM, const int* colIndM, int nnzM, bhs_value_t* valC, int64_t* nnzCt_out,
+                      double* ms_out)
+{
+    BHS_TRY(masked_check(h, nnzM));
+    if (!rowPtrM || (nnzM > 0 && (!colIndM || !valC))) return BHS_ERR_INVALID_ARG;
+    BHS_HIP(hipSetDevice(h->device));
+    BHS_TRY(ensure(h, h->maskM[0], sizeof(int) * ((size_t)h->m + 1)));
+    BHS_TRY(ensure(h, h->maskM[1], sizeof(int) * (size_t)std::max(nnzM, 1)));
+    BHS_TRY(ensure(h, h->maskM[2], sizeof(value_t) * (size_t)std::max(nnzM, 1)));
+    BHS_HIP(hipMemcpyAsync(h->maskM[0].p, rowPtrM, sizeof(int) * ((size_t)h->m + 1), hipMemcpyHostToDevice, h->stream));
+    if (nnzM) BHS_HIP(hipMemcpyAsync(h->maskM[1].p, colIndM, sizeof(int) * (size_t)nnzM, hipMemcpyHostToDevice, h->stream));
+    int rc = masked_run(h, (const int*)h->maskM[0].p, (const int*)h->maskM[1].p, nnzM, (value_t*)h->maskM[2].p, nnzCt_out, ms_out);
+    if (rc == BHS_SUCCESS && nnzM) {
+        BHS_HIP(hipMemcpyAsync(valC, h->maskM[2].p, sizeof(value_t) * (size_t)nnzM, hipMemcpyDeviceToHost, h->stream));
+        BHS_HIP(hipStreamSynchronize(h->stream));
+    }
+    if (rc) settle(h);
+    return rc;
+}
+
+}  // extern "C"

@@ -40,6 +40,7 @@
 #include "bhs_class_fused.hip.h"
 #include "bhs_class_tile.hip.h"
 #include "bhs_class_big.hip.h"
+#include "bhs_masked.hip.h"
 
 #include <algorithm>
 #include <chrono>
@@ -342,6 +343,13 @@ struct bhs_handle {
     const int* resCj = nullptr;          // the colIndC array the finished multiply wrote (own or bound): get_C serves no other
     value_t* extCx = nullptr;
     long long extCap = 0;
+    // the masked multiply (bhs_host_masked.inc.h): buffers of its own, so that it leaves the ordinary multiply's state alone
+    DevBuf maskCtl, maskQueue;           // counters; per-bin queues of (row, products)
+    DevBuf maskM[3];                     // bhs_spgemm_masked: device copies of rowPtrM, colIndM and valC
+    int* maskHost = nullptr;             // pinned mirror of maskCtl
+    hipEvent_t maskEv[2] = {nullptr, nullptr};
+    int maskTableLog2 = 11;              // option "masked_max_table_log2": mask rows beyond 2^v entries take k_masked_long
+    long long maskHubMin = 1 << 17;      // option "masked_hub_min_products": rows of this many products go to k_masked_hub
 };
 
 namespace {
@@ -473,3 +481,4 @@ int timed_end(bhs_handle* h, EventPair* p)
 }  // namespace
 
 #include "bhs_host_cabi.inc.h"
+#include "bhs_host_masked.inc.h"

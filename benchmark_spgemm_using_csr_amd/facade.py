@@ -58,6 +58,7 @@ class bhsparse(object):
         self.nnzC = 0
         self.stage_ms = [0.0] * 4
         self.time_ms = 0.0
+        self.masked_ms = 0.0
         self.quiet = True
 
     # -- bhsparse.h:91-125 -------------------------------------------------
@@ -144,6 +145,45 @@ class bhsparse(object):
             print("[ HIP ] SpGEMM time: %g ms. Gflops = %g" %
                   (self.time_ms, 2.0 * self.nnzCt / (self.time_ms * 1.0e6)))
         return BHSPARSE_SUCCESS
+
+    # -- extension (not in the reference): the masked multiply C<M> = A·B (bhs_spgemm_masked, include/bhsparse_hip.h)
+    def spgemm_masked(self, rowPtrM, colIndM, valC=None):
+        """valC[p] = (A·B)(i, colIndM[p]) for every entry p of row i of the pattern M (numpy int32 CSR, m x n, rows strictly
+        ascending), 0 where no product lands.  Returns valC (allocated when None).  Raises BhsparseError on failure (an
+        invalid M: code BHS_ERR_INVALID_ARG, valC untouched).  Sets nnzCt (products of A·B) and masked_ms (device time)."""
+        if self._h is None:
+            raise BhsparseError("bhs_spgemm_masked", _lib.BHS_ERR_NOT_READY)
+        rowPtrM = np.ascontiguousarray(rowPtrM, np.int32)
+        colIndM = np.ascontiguousarray(colIndM, np.int32)
+        if rowPtrM.size < self._m + 1:
+            raise BhsparseError("bhs_spgemm_masked", _lib.BHS_ERR_INVALID_ARG)
+        nnzM = colIndM.size
+        if valC is None:
+            valC = np.empty(nnzM, self._vdt)
+        elif not (isinstance(valC, np.ndarray) and valC.dtype == self._vdt and valC.size >= nnzM and valC.flags.c_contiguous):
+            raise BhsparseError("bhs_spgemm_masked", _lib.BHS_ERR_INVALID_ARG)
+        nnzCt, ms = C.c_int64(0), C.c_double(0)
+        err = self._lib.bhs_spgemm_masked(self._h, _ptr(rowPtrM), _ptr(colIndM) if nnzM else None, nnzM,
+                                          _ptr(valC) if nnzM else None, C.byref(nnzCt), C.byref(ms))
+        if err != BHSPARSE_SUCCESS:
+            raise BhsparseError("bhs_spgemm_masked", err)
+        self.nnzCt, self.masked_ms = int(nnzCt.value), float(ms.value)
+        return valC
+
+    def spgemm_masked_device(self, d_rowPtrM, d_colIndM, nnzM, d_valC):
+        """The same on device arrays (torch tensors on this handle's GPU, or raw device addresses); valC is written in
+        place.  Returns the status code (0 on success) and sets nnzCt / masked_ms."""
+        if self._h is None:
+            return _lib.BHS_ERR_NOT_READY
+        if any(hasattr(t, "is_cuda") and t.is_cuda for t in (d_rowPtrM, d_colIndM, d_valC)):
+            import torch
+            torch.cuda.synchronize()                       # the library works on its own stream (see initData_device)
+        nnzCt, ms = C.c_int64(0), C.c_double(0)
+        err = self._lib.bhs_spgemm_masked_device(self._h, _ptr(d_rowPtrM), _ptr(d_colIndM), int(nnzM), _ptr(d_valC),
+                                                 C.byref(nnzCt), C.byref(ms))
+        if err == BHSPARSE_SUCCESS:
+            self.nnzCt, self.masked_ms = int(nnzCt.value), float(ms.value)
+        return err
 
     def get_nnzC(self):
         if self._h is None:
@@ -318,3 +358,34 @@ def spgemm_csr(m, k, n, Ap, Aj, Ax, Bp, Bj, Bx, device=0, warmups=0, options=Non
     finally:
         bh.freePlatform()
     return Cp, Cj, Cx, info
+
+
+def spgemm_masked_csr(m, k, n, Ap, Aj, Ax, Bp, Bj, Bx, Mp, Mj, options=None, value_dtype=np.float64, device=0):
+    """Convenience: the masked multiply once on host CSR arrays.  Returns (valC value_dtype[nnzM], info); the result's
+    pattern is the caller's (Mp, Mj)."""
+    plats = [False] * NUM_PLATFORMS
+    plats[BHSPARSE_HIP] = True
+    bh = bhsparse(value_dtype=value_dtype)
+    err = bh.initPlatform(plats, device=device)
+    if err:
+        raise BhsparseError("initPlatform", err)
+    try:
+        for key, val in (options or {}).items():
+            err = bh.set_option(key, val)
+            if err:
+                raise BhsparseError("set_option(%s)" % key, err)
+        Ap, Aj, Ax = (np.ascontiguousarray(Ap, np.int32), np.ascontiguousarray(Aj, np.int32),
+                      np.ascontiguousarray(Ax, value_dtype))
+        Bp, Bj, Bx = (np.ascontiguousarray(Bp, np.int32), np.ascontiguousarray(Bj, np.int32),
+                      np.ascontiguousarray(Bx, value_dtype))
+        err = bh.initData(m, k, n, len(Aj), Ax, Ap, Aj, len(Bj), Bx, Bp, Bj, None)
+        if err:
+            raise BhsparseError("initData", err)
+        valC = bh.spgemm_masked(Mp, Mj)
+        info = {"nnzCt": bh.nnzCt, "ms": bh.masked_ms, "kernels": bh.kernel_stats()}
+        err = bh.free_mem()
+        if err:
+            raise BhsparseError("free_mem", err)
+    finally:
+        bh.freePlatform()
+    return valC, info

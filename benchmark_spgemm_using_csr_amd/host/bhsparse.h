@@ -40,6 +40,11 @@ public:
     // the C-ABI handle behind this object, for the multi-GPU layer (include/bhsparse_dist.h)
     bhs_handle *handle() const { return _h; }
 
+    // EXTENSION, not part of the reference's API: the masked multiply (bhs_spgemm_masked, include/bhsparse_hip.h) on
+    // the data of initData.  csrValC[p] = (A·B)(i, csrColIndM[p]) for every entry p of row i of the caller's pattern M
+    // (m x n, rows strictly ascending; 0 where no product lands).  Host arrays; does not disturb get_C's result.
+    int spgemm_masked(int *csrRowPtrM, int *csrColIndM, int nnzM, value_type *csrValC);
+
 private:
     bool       *_spgemm_platform;
     bhs_handle *_h;
@@ -97,6 +102,12 @@ inline int bhsparse::spgemm()
     std::cout << "[ HIP ] SpGEMM time: " << time << " ms. Gflops = "
               << 2.0 * (double)_nnzCt_full / (time * 1.0e+6) << std::endl;
     return err;
+}
+
+inline int bhsparse::spgemm_masked(int *csrRowPtrM, int *csrColIndM, int nnzM, value_type *csrValC)
+{
+    if (!_h) return BHS_ERR_NOT_READY;
+    return bhs_spgemm_masked(_h, csrRowPtrM, csrColIndM, nnzM, csrValC, 0, 0);
 }
 
 inline int bhsparse::get_nnzC()

@@ -135,6 +135,39 @@ BHS_API int bhs_spgemm_finish(bhs_handle *h, double stage_ms_out[4]);
 /* the HIP stream (hipStream_t) every kernel of this handle is enqueued on */
 BHS_API int bhs_get_stream(bhs_handle *h, void **stream_out);
 
+/* ---- masked multiply ------------------------------------------------------
+ * C<M> = A·B on a pattern the caller already holds (no reference counterpart): for every entry p of row i of M,
+ * valC[p] = sum over k of A(i,k) B(k, colIndM[p]); products outside M are dropped, and an entry no product lands on
+ * (or whose products cancel) reads 0.  The caller's rowPtrM / colIndM are the result's rowPtrC / colIndC: no symbolic
+ * stage, no scan, no sort, no column indices written (bhs_masked.hip.h).
+ *   A, B     the data bound by bhs_set_data[_device], with bhs_spgemm's preconditions (a private copy sorted by "sort_b"
+ *            is what is multiplied)
+ *   M        m x n CSR, 0-based, int32, rows STRICTLY ascending, no values.  Checked on the device before valC is written:
+ *            rowPtrM[0] != 0, a decreasing rowPtrM, rowPtrM[m] != nnzM, a column outside [0, n) or a row not strictly
+ *            ascending returns BHS_ERR_INVALID_ARG with valC untouched
+ *   valC     nnzM values (device: d_valC, caller-owned; host entry: copied back)
+ *   nnzCt_out  products of A·B over all rows, the figure bhs_spgemm reports (GFLOP/s numerator); may be NULL
+ *   ms_out   device time of the whole call, validation included; may be NULL
+ * Synchronous.  BHS_ERR_NOT_READY without data, BHS_ERR_INVALID_ARG between bhs_spgemm_symbolic and bhs_spgemm_finish.
+ * The call leaves the handle as it was: C of the last bhs_spgemm (bhs_get_C, bhs_get_rowptrC, the pointers of
+ * bhs_get_C_device), "class_state", the speculative-launch figures and every option stay; only bhs_get_kernel_stats
+ * now reports the masked call's kernel families (masked_scan, masked_short, masked_wave, masked_long, masked_hub).
+ * Results are bit-exact where every partial sum is exact (integer values); otherwise the order of the additions is
+ * not fixed from run to run (as with bhs_spgemm's LDS tables).
+ *
+ * Reuse workflow (FEM time steps, Newton loops, AMG with fixed coarsening): bind A and B with bhs_set_data_device, form
+ * C's pattern once (bhs_spgemm, bhs_get_C_device), then rewrite the VALUES of A and B in place as often as needed and
+ * call bhs_spgemm_masked_device on that pattern: the masked multiply reads valA / valB during the call and caches
+ * nothing that depends on values.  The patterns of A and B must not change, and B's rows must have been ascending at
+ * hand-over (bhs_get_info "b_sorted" with no private sorted copy: a copy made by "sort_b" does not see later writes).
+ * Tunables ("masked_" keys of bhs_set_option): "masked_max_table_log2" (4..11, default 11) caps the LDS table: mask rows
+ * beyond 2^v entries take the HBM kernel; "masked_hub_min_products" (default 131072, 0 never): rows with this many
+ * products are split across workgroups.                                                                             */
+BHS_API int bhs_spgemm_masked_device(bhs_handle *h, const int *d_rowPtrM, const int *d_colIndM, int nnzM,
+                                     bhs_value_t *d_valC, int64_t *nnzCt_out, double *ms_out);
+BHS_API int bhs_spgemm_masked(bhs_handle *h, const int *rowPtrM, const int *colIndM, int nnzM,
+                              bhs_value_t *valC, int64_t *nnzCt_out, double *ms_out);   /* host arrays, copied */
+
 /* replaces bhsparse::get_nnzC (bhsparse.h: get_nnzC -> bhsparse_cuda::get_nnzC). */
 BHS_API int bhs_get_nnzC(bhs_handle *h, int *nnzC_out);
 

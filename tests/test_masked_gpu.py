@@ -1,0 +1,509 @@
+"""The masked multiply C<M> = A·B (bhs_spgemm_masked[_device]) on the GPU.
+
+Reference: the oracle's full C gathered onto M's pattern (0 where (i, j) is not an entry of A·B), compared with
+oracle.compare on M's pattern.  Integer-valued inputs must match bit for bit."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from conftest import ROOT
+from helpers import poisson_case, random_csr
+
+from benchmark_spgemm_using_csr_amd import _lib, gallery
+from benchmark_spgemm_using_csr_amd.facade import (BHSPARSE_HIP, NUM_PLATFORMS, BhsparseError, bhsparse,
+                                                   spgemm_masked_csr)
+
+pytestmark = pytest.mark.gpu
+
+
+# ---------------------------------------------------------------- reference side
+def gather(ref, n, Mp, Mj):
+    """(A·B)(i, Mj[p]) for every entry p of M, 0 where A·B has no such entry."""
+    Cp, Cj, Cx = ref
+    m = len(Mp) - 1
+    ckey = np.repeat(np.arange(m, dtype=np.int64), np.diff(np.asarray(Cp, np.int64))) * n + Cj.astype(np.int64)
+    mkey = np.repeat(np.arange(m, dtype=np.int64), np.diff(np.asarray(Mp, np.int64))) * n + np.asarray(Mj, np.int64)
+    out = np.zeros(len(mkey), np.float64)
+    if len(ckey) and len(mkey):
+        pos = np.minimum(np.searchsorted(ckey, mkey), len(ckey) - 1)
+        hit = ckey[pos] == mkey
+        out[hit] = Cx[pos[hit]]
+    return out
+
+
+def check(oracle, m, k, n, A, B, Mp, Mj, valC, exact=True):
+    ref = oracle.spgemm(m, k, n, *A, *B)
+    expected = gather(ref, n, Mp, Mj)
+    Mp64 = np.asarray(Mp, np.int64)
+    res = oracle.compare((Mp64, np.asarray(Mj, np.int32), expected), (np.asarray(Mp, np.int32), np.asarray(Mj, np.int32),
+                                                                       np.asarray(valC, np.float64)))
+    assert res["ok"], res
+    if exact:
+        assert np.array_equal(np.asarray(valC, np.float64), expected)
+    return expected
+
+
+def pattern_of(oracle, m, k, n, A, B):
+    Cp, Cj, _ = oracle.spgemm(m, k, n, *A, *B)
+    return np.asarray(Cp, np.int32), np.asarray(Cj, np.int32)
+
+
+def random_mask(rng, m, n, inside, frac_in=0.5, extra_per_row=3, empty_rows=()):
+    """Part of pattern(A·B) (inside = (Cp, Cj)) plus random entries, rows strictly ascending."""
+    Cp, Cj = inside
+    keep = rng.random(len(Cj)) < frac_in
+    rows = [np.repeat(np.arange(m), np.diff(Cp.astype(np.int64)))[keep]]
+    cols = [Cj[keep].astype(np.int64)]
+    if n > 0 and extra_per_row:
+        r = np.repeat(np.arange(m), extra_per_row)
+        rows.append(r)
+        cols.append(rng.integers(0, n, len(r)))
+    rr = np.concatenate(rows).astype(np.int64)
+    cc = np.concatenate(cols).astype(np.int64)
+    for e in empty_rows:
+        sel = rr != e
+        rr, cc = rr[sel], cc[sel]
+    return gallery._csr_from_pairs(m, n, rr, cc) if m > 0 else (np.zeros(1, np.int32), np.zeros(0, np.int32))
+
+
+def new_handle(dtype=np.float64, options=None):
+    plats = [False] * NUM_PLATFORMS
+    plats[BHSPARSE_HIP] = True
+    bh = bhsparse(value_dtype=dtype)
+    assert bh.initPlatform(plats) == 0
+    for key, val in (options or {}).items():
+        assert bh.set_option(key, val) == 0, key
+    return bh
+
+
+def bind(bh, m, k, n, A, B, dtype=np.float64):
+    Ap, Aj, Ax = A
+    Bp, Bj, Bx = B
+    arrs = [np.ascontiguousarray(x, t) for x, t in ((Ax, dtype), (Ap, np.int32), (Aj, np.int32),
+                                                    (Bx, dtype), (Bp, np.int32), (Bj, np.int32))]
+    Cp = np.zeros(m + 1, np.int32)
+    assert bh.initData(m, k, n, len(arrs[2]), arrs[0], arrs[1], arrs[2], len(arrs[5]), arrs[3], arrs[4], arrs[5], Cp) == 0
+    return Cp
+
+
+def full_product(bh):
+    assert bh.spgemm() == 0
+    nnz = bh.get_nnzC()
+    Cj = np.empty(nnz, np.int32)
+    Cx = np.empty(nnz, bh._vdt)
+    assert bh.get_C(Cj, Cx) == 0
+    return bh._rowptrC.copy(), Cj, Cx
+
+
+def families(bh):
+    return {s["name"]: s for s in bh.kernel_stats()}
+
+
+def square(m, rp, col, val):
+    return m, m, m, (rp, col, val), (rp, col, val)
+
+
+# ---------------------------------------------------------------- M = pattern(A·B): the reuse workflow
+REUSE_CASES = {
+    "p5_16_class": (lambda: square(*poisson_case("poisson5pt", 16, 16)), {"class_path": 2}),
+    "p5_16_general": (lambda: square(*poisson_case("poisson5pt", 16, 16)), {"class_path": 0}),
+    "p27_6_class": (lambda: square(*poisson_case("poisson27pt", 6, 6, 6)), {"class_path": 2}),
+    "p27_8_general": (lambda: square(*poisson_case("poisson27pt", 8, 8, 8)), {"class_path": 0}),
+}
+
+
+def _rect():
+    rng = np.random.default_rng(7)
+    A = random_csr(300, 200, 0.03, rng, empty_rows=(0, 5, 77))
+    B = random_csr(200, 250, 0.04, rng, empty_rows=(3,))
+    return 300, 200, 250, A, B
+
+
+def _weblike():
+    rp, col = gallery.weblike_csr(m=20000, max_row=600, max_host=400)
+    val = gallery.fill_values(len(col))
+    return square(len(rp) - 1, rp, col, val)
+
+
+REUSE_CASES["rect_rand"] = (_rect, {})
+REUSE_CASES["weblike_20k"] = (_weblike, {})
+
+
+@pytest.mark.parametrize("case", sorted(REUSE_CASES))
+def test_masked_on_pattern_of_product_matches_spgemm(case, oracle):
+    make, opts = REUSE_CASES[case]
+    m, k, n, A, B = make()
+    bh = new_handle(options=opts)
+    try:
+        bind(bh, m, k, n, A, B)
+        Cp, Cj, Cx = full_product(bh)
+        nnzct = bh.nnzCt
+        valC = bh.spgemm_masked(Cp, Cj)
+        assert np.array_equal(valC, Cx)                   # bit for bit on integer values
+        assert bh.nnzCt == nnzct                          # the same product count as the full multiply
+        assert bh.masked_ms > 0
+        fam = families(bh)
+        assert fam["masked_scan"]["launches"] == 1 and fam["masked_scan"]["rows"] == m
+        assert sum(s["rows"] for nm, s in fam.items() if nm != "masked_scan") == int(np.count_nonzero(np.diff(Cp)))
+        assert not any(nm.startswith(("numeric", "symbolic")) for nm in fam)
+    finally:
+        bh.freePlatform()
+    check(oracle, m, k, n, A, B, Cp, Cj, valC)
+
+
+@pytest.mark.parametrize("sort_b", [1, 0])
+def test_masked_with_unsorted_b(sort_b, oracle):
+    rng = np.random.default_rng(11)
+    m, k, n = 400, 300, 350
+    A = random_csr(m, k, 0.02, rng)
+    Bp, Bj, Bx = random_csr(k, n, 0.03, rng)
+    Bj, Bx = Bj.copy(), Bx.copy()
+    for i in range(k):                                    # reverse every row: B arrives unsorted
+        Bj[Bp[i]:Bp[i + 1]] = Bj[Bp[i]:Bp[i + 1]][::-1]
+        Bx[Bp[i]:Bp[i + 1]] = Bx[Bp[i]:Bp[i + 1]][::-1]
+    B = (Bp, Bj, Bx)
+    Mp, Mj = random_mask(rng, m, n, pattern_of(oracle, m, k, n, A, B), frac_in=0.7)
+    bh = new_handle(options={"sort_b": sort_b})
+    try:
+        bind(bh, m, k, n, A, B)
+        assert bh.get_info("b_sorted") == sort_b
+        valC = bh.spgemm_masked(Mp, Mj)
+        Cp, Cj, Cx = full_product(bh)
+        full = bh.spgemm_masked(Cp, Cj)
+        assert np.array_equal(full, Cx)
+    finally:
+        bh.freePlatform()
+    check(oracle, m, k, n, A, B, Mp, Mj, valC)
+
+
+# ---------------------------------------------------------------- random masks, edge cases
+def test_masked_random_mask_inside_and_outside(oracle):
+    rng = np.random.default_rng(3)
+    m, k, n = 500, 400, 450
+    A = random_csr(m, k, 0.02, rng, empty_rows=(1, 2, 3, 100))
+    B = random_csr(k, n, 0.02, rng, empty_rows=(7,))
+    Mp, Mj = random_mask(rng, m, n, pattern_of(oracle, m, k, n, A, B), frac_in=0.5, extra_per_row=4,
+                         empty_rows=(0, 10, 499))
+    valC, info = spgemm_masked_csr(m, k, n, *A, *B, Mp, Mj)
+    exp = check(oracle, m, k, n, A, B, Mp, Mj, valC)
+    assert np.count_nonzero(exp == 0) > 0 and np.count_nonzero(exp) > 0      # both kinds of entries were there
+
+
+def test_masked_empty_mask_and_empty_matrix(oracle):
+    rng = np.random.default_rng(5)
+    m, k, n = 60, 50, 40
+    A = random_csr(m, k, 0.1, rng)
+    B = random_csr(k, n, 0.1, rng)
+    valC, info = spgemm_masked_csr(m, k, n, *A, *B, np.zeros(m + 1, np.int32), np.zeros(0, np.int32))
+    assert valC.size == 0 and info["nnzCt"] > 0
+    z = (np.zeros(1, np.int32), np.zeros(0, np.int32), np.zeros(0))
+    valC, info = spgemm_masked_csr(0, k, n, *z, *B, np.zeros(1, np.int32), np.zeros(0, np.int32))
+    assert valC.size == 0 and info["nnzCt"] == 0
+
+
+def test_masked_real_values(oracle):
+    rng = np.random.default_rng(17)
+    m, k, n = 700, 500, 600
+    A = random_csr(m, k, 0.02, rng, values="real")
+    B = random_csr(k, n, 0.02, rng, values="real")
+    Mp, Mj = random_mask(rng, m, n, pattern_of(oracle, m, k, n, A, B), frac_in=0.8)
+    valC, _ = spgemm_masked_csr(m, k, n, *A, *B, Mp, Mj)
+    check(oracle, m, k, n, A, B, Mp, Mj, valC, exact=False)
+
+
+# ---------------------------------------------------------------- triangle counting
+def test_triangle_count_rmat():
+    rp, col = gallery.rmat_csr(scale=11, edge_factor=8, seed=123)
+    n = len(rp) - 1
+    r = np.repeat(np.arange(n), np.diff(rp))
+    rows = np.concatenate([r, col]).astype(np.int64)
+    cols = np.concatenate([col, r]).astype(np.int64)
+    low = rows > cols                                     # symmetrised, strict lower triangle
+    Lp, Lj = gallery._csr_from_pairs(n, n, rows[low], cols[low])
+    Lx = np.ones(len(Lj))
+    valC, info = spgemm_masked_csr(n, n, n, Lp, Lj, Lx, Lp, Lj, Lx, Lp, Lj)
+    dense = np.zeros((n, n))
+    dense[np.repeat(np.arange(n), np.diff(Lp)), Lj] = 1.0
+    brute = int(round(((dense @ dense) * dense).sum()))
+    assert brute > 0
+    assert int(valC.sum()) == brute
+    assert info["nnzCt"] == int(np.diff(Lp)[Lj].sum())
+
+
+# ---------------------------------------------------------------- every kernel family
+def _fam_case(kind):
+    rng = np.random.default_rng({"short": 1, "wave": 2, "wave_big": 3, "long": 4, "hub": 5, "hub_lds": 6, "hub_slice": 7}[kind])
+    if kind == "short":
+        return square(*poisson_case("poisson5pt", 20, 20)), {}
+    if kind == "wave":
+        return square(*poisson_case("poisson27pt", 7, 7, 7)), {}
+    if kind == "wave_big":                                # mask rows of ~550 entries: the 2048-entry table
+        m, k, n = 64, 400, 3000
+        return (m, k, n, random_csr(m, k, 30 / k, rng), random_csr(k, n, 20 / n, rng)), {}
+    if kind == "long":                                    # one mask row of >= 20 k entries
+        m, k, n = 8, 2000, 50000
+        A = random_csr(m, k, 0.25, rng)
+        B = random_csr(k, n, 0.002, rng)
+        return (m, k, n, A, B), {}
+    if kind == "hub":                                     # one row of >= 131072 products (mask row beyond LDS)
+        m, k, n = 4, 400, 20000
+        Ap = np.array([0, 400, 401, 401, 403], np.int32)
+        Aj = np.concatenate([np.arange(400), [5], [1, 2]]).astype(np.int32)
+        Ax = rng.integers(1, 10, len(Aj)).astype(np.float64)
+        B = random_csr(k, n, 400 / n, rng)
+        return (m, k, n, (Ap, Aj, Ax), B), {}
+    if kind == "hub_slice":                               # a hub row of two A entries: its parts take slices of B rows
+        m, k, n = 3, 2, 100000
+        Ap = np.array([0, 2, 3, 3], np.int32)
+        Aj = np.array([0, 1, 1], np.int32)
+        Ax = np.array([3.0, 5.0, 7.0])
+        return (m, k, n, (Ap, Aj, Ax), random_csr(k, n, 0.8, rng)), {}
+    if kind == "hub_lds":                                 # hub rows whose mask rows fit LDS (threshold lowered)
+        m, k, n = 300, 200, 1500
+        return (m, k, n, random_csr(m, k, 0.1, rng), random_csr(k, n, 0.01, rng)), {"masked_hub_min_products": 200}
+    raise ValueError(kind)
+
+
+@pytest.mark.parametrize("kind,family", [("short", "masked_short"), ("wave", "masked_wave"), ("wave_big", "masked_wave"),
+                                         ("long", "masked_long"), ("hub", "masked_hub"), ("hub_lds", "masked_hub"),
+                                         ("hub_slice", "masked_hub")])
+def test_every_kernel_family_is_reached(kind, family, oracle):
+    (m, k, n, A, B), opts = _fam_case(kind)
+    rng = np.random.default_rng(99)
+    Mp, Mj = random_mask(rng, m, n, pattern_of(oracle, m, k, n, A, B), frac_in=0.9, extra_per_row=5)
+    if kind == "long":
+        assert np.diff(Mp).max() >= 20000
+    valC, info = spgemm_masked_csr(m, k, n, *A, *B, Mp, Mj, options=opts)
+    fam = {s["name"]: s for s in info["kernels"]}
+    assert family in fam and fam[family]["launches"] >= 1, fam
+    assert fam[family]["rows"] >= 1 and fam[family]["products"] >= 1
+    if kind == "hub":
+        assert fam["masked_hub"]["products"] >= 131072
+    check(oracle, m, k, n, A, B, Mp, Mj, valC)
+
+
+@pytest.mark.parametrize("log2", [4, 5, 8])
+def test_table_cap_option_forces_the_long_path(log2, oracle):
+    m, k, n, A, B = square(*poisson_case("poisson27pt", 6, 6, 6))
+    Cp, Cj = pattern_of(oracle, m, k, n, A, B)
+    valC, info = spgemm_masked_csr(m, k, n, *A, *B, Cp, Cj, options={"masked_max_table_log2": log2})
+    fam = {s["name"]: s for s in info["kernels"]}
+    if log2 < 7:                                          # rows of 27^2 products reach up to 125 columns
+        assert fam["masked_long"]["launches"] == 1
+    check(oracle, m, k, n, A, B, Cp, Cj, valC)
+
+
+def test_option_keys_are_checked():
+    bh = new_handle()
+    try:
+        assert bh.set_option("masked_max_table_log2", 3) == _lib.BHS_ERR_INVALID_ARG
+        assert bh.set_option("masked_max_table_log2", 12) == _lib.BHS_ERR_INVALID_ARG
+        assert bh.set_option("masked_max_table_log2", 11) == 0
+        assert bh.set_option("masked_hub_min_products", 0) == 0
+    finally:
+        bh.freePlatform()
+
+
+# ---------------------------------------------------------------- f32 library
+def test_f32_pattern_of_product_and_random_mask(oracle):
+    m, k, n, A, B = square(*poisson_case("poisson27pt", 6, 6, 6))
+    bh = new_handle(dtype=np.float32)
+    try:
+        bind(bh, m, k, n, A, B, dtype=np.float32)
+        Cp, Cj, Cx = full_product(bh)
+        valC = bh.spgemm_masked(Cp, Cj)
+        assert valC.dtype == np.float32 and np.array_equal(valC, Cx)
+    finally:
+        bh.freePlatform()
+    check(oracle, m, k, n, A, B, Cp, Cj, valC)
+    rng = np.random.default_rng(21)
+    m, k, n = 500, 400, 450
+    A = random_csr(m, k, 0.02, rng)
+    B = random_csr(k, n, 0.02, rng)
+    Mp, Mj = random_mask(rng, m, n, pattern_of(oracle, m, k, n, A, B))
+    valC, _ = spgemm_masked_csr(m, k, n, *A, *B, Mp, Mj, value_dtype=np.float32)
+    assert valC.dtype == np.float32
+    check(oracle, m, k, n, A, B, Mp, Mj, valC)
+
+
+# ---------------------------------------------------------------- in-place value update on device data
+def test_in_place_value_update_through_device_data(oracle):
+    import torch
+    rng = np.random.default_rng(31)
+    m, k, n = 800, 600, 700
+    Ap, Aj, Ax = random_csr(m, k, 0.01, rng)
+    Bp, Bj, Bx = random_csr(k, n, 0.01, rng)
+    Mp, Mj = random_mask(rng, m, n, pattern_of(oracle, m, k, n, (Ap, Aj, Ax), (Bp, Bj, Bx)), frac_in=0.8)
+    dev = torch.device("cuda")
+    t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dt)).to(dev)   # noqa: E731
+    dAp, dAj, dAx, dBp, dBj, dBx = (t(Ap, np.int32), t(Aj, np.int32), t(Ax, np.float64), t(Bp, np.int32), t(Bj, np.int32),
+                                    t(Bx, np.float64))
+    dMp, dMj = t(Mp, np.int32), t(Mj, np.int32)
+    dC = torch.zeros(len(Mj), dtype=torch.float64, device=dev)
+    bh = new_handle()
+    try:
+        assert bh.initData_device(m, k, n, len(Aj), dAx, dAp, dAj, len(Bj), dBx, dBp, dBj) == 0
+        assert bh.get_info("b_sorted") == 1
+        assert bh.spgemm_masked_device(dMp, dMj, len(Mj), dC) == 0
+        check(oracle, m, k, n, (Ap, Aj, Ax), (Bp, Bj, Bx), Mp, Mj, dC.cpu().numpy())
+        Ax2 = rng.integers(1, 10, len(Aj)).astype(np.float64)
+        Bx2 = rng.integers(1, 10, len(Bj)).astype(np.float64)
+        dAx.copy_(torch.from_numpy(Ax2))
+        dBx.copy_(torch.from_numpy(Bx2))
+        assert bh.spgemm_masked_device(dMp, dMj, len(Mj), dC) == 0
+        check(oracle, m, k, n, (Ap, Aj, Ax2), (Bp, Bj, Bx2), Mp, Mj, dC.cpu().numpy())
+        assert bh.free_mem() == 0
+    finally:
+        bh.freePlatform()
+
+
+# ---------------------------------------------------------------- the handle's state
+@pytest.mark.parametrize("opts", [{"class_path": 2}, {"class_path": 0}])
+def test_handle_state_untouched(opts, oracle):
+    m, k, n, A, B = square(*poisson_case("poisson27pt", 8, 8, 8))
+    rng = np.random.default_rng(41)
+    Mp, Mj = random_mask(rng, m, n, pattern_of(oracle, m, k, n, A, B))
+    bh = new_handle(options=opts)
+    try:
+        bind(bh, m, k, n, A, B)
+        Cp, Cj, Cx = full_product(bh)
+        state = bh.get_info("class_state")
+        ptrs = bh.get_C_device()
+        valC = bh.spgemm_masked(Mp, Mj)
+        Cj2 = np.empty_like(Cj)
+        Cx2 = np.empty_like(Cx)
+        assert bh.get_C(Cj2, Cx2) == 0
+        assert np.array_equal(Cj2, Cj) and np.array_equal(Cx2, Cx) and np.array_equal(bh.get_rowptrC(), Cp)
+        assert bh.get_C_device() == ptrs
+        assert bh.get_info("class_state") == state
+        Cp3, Cj3, Cx3 = full_product(bh)
+        assert np.array_equal(Cp3, Cp) and np.array_equal(Cj3, Cj) and np.array_equal(Cx3, Cx)
+        assert bh.get_info("class_state") == state
+    finally:
+        bh.freePlatform()
+    check(oracle, m, k, n, A, B, Mp, Mj, valC)
+
+
+# ---------------------------------------------------------------- invalid masks
+def _bad_masks(m, n, Mp, Mj):
+    i = int(np.argmax(np.diff(Mp) >= 2))
+    s = Mp[i]
+    unsorted = Mj.copy()
+    unsorted[s], unsorted[s + 1] = unsorted[s + 1], unsorted[s]
+    dup = Mj.copy()
+    dup[s + 1] = dup[s]
+    big = Mj.copy()
+    big[-1] = n
+    neg = Mj.copy()
+    neg[0] = -1
+    nonmono = Mp.copy()
+    nonmono[m // 2] = nonmono[m // 2 + 1] + 1
+    first = Mp.copy()
+    first[0] = 1
+    return {"unsorted_row": (Mp, unsorted, len(Mj)), "duplicate": (Mp, dup, len(Mj)), "column_ge_n": (Mp, big, len(Mj)),
+            "negative_column": (Mp, neg, len(Mj)), "non_monotone": (nonmono, Mj, len(Mj)),
+            "rowptr0": (first, Mj, len(Mj)), "wrong_nnz": (Mp, Mj, len(Mj) - 1)}
+
+
+def test_invalid_masks_are_rejected_and_leave_valc_alone(oracle):
+    import torch
+    m, k, n, A, B = square(*poisson_case("poisson5pt", 12, 12))
+    Mp, Mj = pattern_of(oracle, m, k, n, A, B)
+    bh = new_handle()
+    try:
+        bind(bh, m, k, n, A, B)
+        for name, (p, j, nnz) in _bad_masks(m, n, Mp, Mj).items():
+            sentinel = np.full(len(Mj), 12345.0)
+            out = sentinel.copy()
+            with pytest.raises(BhsparseError) as e:
+                if nnz == len(j):
+                    bh.spgemm_masked(p, j, out)
+                else:
+                    raise BhsparseError("x", bh._lib.bhs_spgemm_masked(bh._h, p.ctypes.data, j.ctypes.data, nnz,
+                                                                       out.ctypes.data, None, None))
+            assert e.value.code == _lib.BHS_ERR_INVALID_ARG, name
+            assert np.array_equal(out, sentinel), name
+            dC = torch.full((len(Mj),), 12345.0, dtype=torch.float64, device="cuda")
+            rc = bh.spgemm_masked_device(torch.from_numpy(np.ascontiguousarray(p)).cuda(),
+                                         torch.from_numpy(np.ascontiguousarray(j)).cuda(), nnz, dC)
+            assert rc == _lib.BHS_ERR_INVALID_ARG, name
+            assert torch.all(dC == 12345.0).item(), name
+        good = bh.spgemm_masked(Mp, Mj)                   # the handle still works
+        check(oracle, m, k, n, A, B, Mp, Mj, good)
+    finally:
+        bh.freePlatform()
+
+
+def test_masked_during_split_multiply_and_without_data(oracle):
+    m, k, n, A, B = square(*poisson_case("poisson5pt", 12, 12))
+    Mp, Mj = pattern_of(oracle, m, k, n, A, B)
+    bh = new_handle()
+    try:
+        with pytest.raises(BhsparseError) as e:
+            bh.spgemm_masked(Mp, Mj)
+        assert e.value.code == _lib.BHS_ERR_NOT_READY
+        bind(bh, m, k, n, A, B)
+        assert bh.spgemm_symbolic() == 0
+        with pytest.raises(BhsparseError) as e:
+            bh.spgemm_masked(Mp, Mj)
+        assert e.value.code == _lib.BHS_ERR_INVALID_ARG
+        assert bh.spgemm_numeric(0, m) == 0 and bh.spgemm_finish() == 0
+        valC = bh.spgemm_masked(Mp, Mj)
+        assert bh.free_mem() == 0
+        with pytest.raises(BhsparseError) as e:
+            bh.spgemm_masked(Mp, Mj)
+        assert e.value.code == _lib.BHS_ERR_NOT_READY
+    finally:
+        bh.freePlatform()
+    check(oracle, m, k, n, A, B, Mp, Mj, valC)
+
+
+# ---------------------------------------------------------------- the C++ facade's extension
+def test_cpp_facade_masked_demo():
+    demo_dir = os.path.join(ROOT, "tests", "masked")
+    subprocess.check_call(["make", "-C", demo_dir, "-s"])
+    r = subprocess.run([os.path.join(demo_dir, "masked_demo")], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "masked OK" in r.stdout
+
+
+# ---------------------------------------------------------------- random soak
+def _soak_case(seed, oracle):
+    rng = np.random.default_rng(10000 + seed)
+    shape = rng.integers(0, 4)
+    if shape == 0:                                        # small rows: short and wave bins
+        m, k, n = (int(x) for x in rng.integers(1, 400, 3))
+        A = random_csr(m, k, float(rng.uniform(0.0, 0.05)), rng, values=rng.choice(["int", "signed"]))
+        B = random_csr(k, n, float(rng.uniform(0.0, 0.05)), rng, values=rng.choice(["int", "signed"]))
+    elif shape == 1:                                      # stencils
+        nm = str(rng.choice(["poisson5pt", "poisson9pt", "poisson7pt", "poisson27pt"]))
+        nx = int(rng.integers(2, 12))
+        m, k, n, A, B = square(*poisson_case(nm, nx, nx, nx if nm in ("poisson7pt", "poisson27pt") else 1))
+    elif shape == 2:                                      # longer rows: big wave table, long rows
+        m, k, n = int(rng.integers(4, 60)), int(rng.integers(50, 600)), int(rng.integers(1000, 8000))
+        A = random_csr(m, k, float(rng.uniform(0.05, 0.3)), rng)
+        B = random_csr(k, n, float(rng.uniform(0.005, 0.03)), rng)
+    else:                                                 # skewed
+        m = int(rng.integers(50, 500))
+        rp, col = gallery.powerlaw_csr(m, m, m * 4, max_row=m // 2, seed=int(rng.integers(1 << 30)))
+        val = rng.integers(1, 10, len(col)).astype(np.float64)
+        m, k, n, A, B = square(m, rp, col, val)
+    opts = {}
+    if rng.random() < 0.3:
+        opts["masked_max_table_log2"] = int(rng.integers(4, 12))
+    if rng.random() < 0.3:
+        opts["masked_hub_min_products"] = int(rng.integers(1, 2000))
+    Mp, Mj = random_mask(rng, m, n, pattern_of(oracle, m, k, n, A, B), frac_in=float(rng.uniform(0, 1)),
+                         extra_per_row=int(rng.integers(0, 6)))
+    valC, _ = spgemm_masked_csr(m, k, n, *A, *B, Mp, Mj, options=opts)
+    check(oracle, m, k, n, A, B, Mp, Mj, valC)
+
+
+SOAK_N = 300 if os.environ.get("BHS_SOAK") == "1" else 30
+
+
+@pytest.mark.parametrize("seed", list(range(SOAK_N)))
+def test_masked_soak(seed, oracle):
+    _soak_case(seed, oracle)
