@@ -620,6 +620,9 @@ bool bin_takes_lds_bitmap(const bhs_handle* h, const KernelCfg& c)
     // (symbolic: the workgroup-per-row bin of 32768 slots -- 128 KB of LDS for a hash table where the bitmap's first pass and a
     // popcount do: option "sym_bitmap_min_log2", 16: never)
     if (!NUM) return c.block > 64 && c.log2ts >= h->symBitmapMinLog2 && h->forcePath == 0;
+    // (the float build: the bitmap kernel adds a column's products, each rounded to float, with float atomics into the row of
+    // C -- the workgroup bins keep their tables, which add in double and round once per entry: INTEGRATION.md §7)
+    if (sizeof(value_t) < sizeof(acc_t)) return false;
     return c.block > 64 && c.log2ts >= h->ldsBitmapMinLog2 && h->forcePath == 0;
 }
 

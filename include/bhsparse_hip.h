@@ -153,7 +153,10 @@ BHS_API int bhs_get_stream(bhs_handle *h, void **stream_out);
  * bhs_get_C_device), "class_state", the speculative-launch figures and every option stay; only bhs_get_kernel_stats
  * now reports the masked call's kernel families (masked_scan, masked_short, masked_wave, masked_long, masked_hub).
  * Results are bit-exact where every partial sum is exact (integer values); otherwise the order of the additions is
- * not fixed from run to run (as with bhs_spgemm's LDS tables).
+ * not fixed from run to run (as with bhs_spgemm's LDS tables).  Products and sums are formed in double.  In the float
+ * build (bhs_value_t float) masked_short and masked_wave round once per entry; masked_long adds every product, rounded
+ * to float, to valC with a float atomic, and masked_hub adds each part's sum (double in LDS where the mask row fits
+ * 2048 entries, else each product), rounded to float, with float atomics.
  *
  * Reuse workflow (FEM time steps, Newton loops, AMG with fixed coarsening): bind A and B with bhs_set_data_device, form
  * C's pattern once (bhs_spgemm, bhs_get_C_device), then rewrite the VALUES of A and B in place as often as needed and

@@ -93,15 +93,31 @@ STAGES = {0: "nnzC NO PASS", 1: "RowPtrC NO PASS", 2: "ColIndC/csrValC NO PASS",
 
 def compare(ref, got, rel_tol=1e-6):
     """ref=(Cp int64, Cj, Cx) from spgemm(); got=(rowPtrC int32, colIndC, valC) from the HIP path.
-    Mirrors compData's order of checks (ref_spgemm.h:79-126). Returns dict."""
+    Mirrors compData's order of checks (ref_spgemm.h:79-126). Returns dict.
+
+    compData's test |ref - got| > tol*|ref| is false whenever either side is NaN, and whenever ref is +-Inf.  So on top
+    of it an entry whose column matches counts as a value error where one side is NaN and the other is not, or where
+    either side is +-Inf and the two differ."""
     rCp, rCj, rCx = ref
     gCp, gCj, gCx = got
     m = len(rCp) - 1
     out = np.zeros(4, np.int64)
     nn = int(gCp[-1]) if len(gCp) else 0
-    lib().oracle_compare(m, int(rCp[-1]), _c(rCp, np.int64), _c(rCj, np.int32), _c(rCx, np.float64),
-                         nn, _c(gCp, np.int32), _c(gCj, np.int32), _c(gCx, np.float64),
-                         float(rel_tol), out)
+    rCj, rCx, gCj, gCx = _c(rCj, np.int32), _c(rCx, np.float64), _c(gCj, np.int32), _c(gCx, np.float64)
+    lib().oracle_compare(m, int(rCp[-1]), _c(rCp, np.int64), rCj, rCx,
+                         nn, _c(gCp, np.int32), gCj, gCx, float(rel_tol), out)
+    if out[0] >= 2:
+        same = rCj[:nn] == gCj[:nn]
+        r, g = rCx[:nn][same], gCx[:nn][same]
+        with np.errstate(invalid="ignore"):
+            bad = (np.isnan(r) != np.isnan(g)) | ((np.isinf(r) | np.isinf(g)) & (r != g) & ~(np.isnan(r) & np.isnan(g)))
+        nbad = int(np.count_nonzero(bad))
+        if nbad:
+            # (entries the C check already counted -- e.g. Inf against a finite value -- are not counted twice)
+            with np.errstate(invalid="ignore"):
+                counted = np.abs(r - g) > np.abs(rel_tol * r)
+            out[3] += int(np.count_nonzero(bad & ~counted))
+            out[0] = 2
     return {"stage": int(out[0]), "verdict": STAGES[int(out[0])], "rowptr_err": int(out[1]),
             "col_err": int(out[2]), "val_err": int(out[3]), "ok": int(out[0]) == 3}
 

@@ -10,6 +10,7 @@ import pytest
 
 from conftest import ROOT
 from helpers import poisson_case, random_csr
+from valuecheck import check_bounded
 
 from benchmark_spgemm_using_csr_amd import _lib, gallery
 from benchmark_spgemm_using_csr_amd.facade import (BHSPARSE_HIP, NUM_PLATFORMS, BhsparseError, bhsparse,
@@ -211,6 +212,7 @@ def test_masked_real_values(oracle):
     Mp, Mj = random_mask(rng, m, n, pattern_of(oracle, m, k, n, A, B), frac_in=0.8)
     valC, _ = spgemm_masked_csr(m, k, n, *A, *B, Mp, Mj)
     check(oracle, m, k, n, A, B, Mp, Mj, valC, exact=False)
+    check_bounded(oracle, m, k, n, A, B, valC, "f64", mask=(Mp, Mj))
 
 
 # ---------------------------------------------------------------- triangle counting
@@ -470,7 +472,8 @@ def test_cpp_facade_masked_demo():
 
 
 # ---------------------------------------------------------------- random soak
-def _soak_case(seed, oracle):
+def _soak_inputs(seed, oracle):
+    """The soak's draw: ((m, k, n), A, B, Mp, Mj, options)."""
     rng = np.random.default_rng(10000 + seed)
     shape = rng.integers(0, 4)
     if shape == 0:                                        # small rows: short and wave bins
@@ -497,6 +500,11 @@ def _soak_case(seed, oracle):
         opts["masked_hub_min_products"] = int(rng.integers(1, 2000))
     Mp, Mj = random_mask(rng, m, n, pattern_of(oracle, m, k, n, A, B), frac_in=float(rng.uniform(0, 1)),
                          extra_per_row=int(rng.integers(0, 6)))
+    return (m, k, n), A, B, Mp, Mj, opts
+
+
+def _soak_case(seed, oracle):
+    (m, k, n), A, B, Mp, Mj, opts = _soak_inputs(seed, oracle)
     valC, _ = spgemm_masked_csr(m, k, n, *A, *B, Mp, Mj, options=opts)
     check(oracle, m, k, n, A, B, Mp, Mj, valC)
 

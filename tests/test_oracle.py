@@ -114,6 +114,43 @@ def test_compare_reports_like_compData(oracle):
     assert oracle.compare(ref, (badp, good[1], good[2]))["stage"] == 1
 
 
+@pytest.mark.parametrize("rel_tol", [0.0, 1e-6])
+def test_compare_sees_non_finite_values(oracle, rel_tol):
+    """compData's |ref - got| > tol*|ref| is false for a NaN result: compare() must still count it."""
+    g = load_golden("p5_16.npz")
+    ref = (g["Cp"], g["Cj"], g["Cx"].copy())
+    got = lambda x: (g["Cp"].astype(np.int32), g["Cj"], x)              # noqa: E731
+    # NaN where the reference is finite fails
+    x = ref[2].copy(); x[7] = np.nan
+    r = oracle.compare(ref, got(x), rel_tol=rel_tol)
+    assert not r["ok"] and r["stage"] == 2 and r["val_err"] == 1 and r["col_err"] == 0
+    # NaN where the reference is NaN passes
+    ref[2][7] = np.nan
+    assert oracle.compare(ref, got(x), rel_tol=rel_tol)["ok"]
+    # ... a finite value where the reference is NaN fails
+    assert not oracle.compare(ref, got(g["Cx"].copy()), rel_tol=rel_tol)["ok"]
+    # +Inf against -Inf fails, +Inf against +Inf passes, a finite value against Inf fails either way round
+    ref[2][7] = np.inf
+    x[7] = -np.inf
+    r = oracle.compare(ref, got(x), rel_tol=rel_tol)
+    assert not r["ok"] and r["val_err"] == 1
+    x[7] = np.inf
+    assert oracle.compare(ref, got(x), rel_tol=rel_tol)["ok"]
+    x[7] = 1.0
+    r = oracle.compare(ref, got(x), rel_tol=rel_tol)
+    assert not r["ok"] and r["val_err"] == 1
+    r = oracle.compare((g["Cp"], g["Cj"], g["Cx"]), got(np.where(np.arange(len(x)) == 3, -np.inf, g["Cx"])), rel_tol=rel_tol)
+    assert not r["ok"] and r["val_err"] == 1
+    # finite results behave as before: equal passes, one entry off beyond the tolerance is one error, within it none
+    y = g["Cx"].copy()
+    assert oracle.compare((g["Cp"], g["Cj"], g["Cx"]), got(y), rel_tol=rel_tol)["ok"]
+    y[5] *= 1 + 1e-4
+    r = oracle.compare((g["Cp"], g["Cj"], g["Cx"]), got(y), rel_tol=rel_tol)
+    assert not r["ok"] and r["stage"] == 2 and r["val_err"] == 1
+    y = g["Cx"].copy(); y[5] *= 1 + 1e-9
+    assert oracle.compare((g["Cp"], g["Cj"], g["Cx"]), got(y), rel_tol=rel_tol)["ok"] == (rel_tol > 0)
+
+
 def test_value_fill_is_deterministic_and_shardable():
     a = gallery.fill_values(1000)
     assert a.min() >= 1 and a.max() <= 9 and np.all(a == np.round(a))

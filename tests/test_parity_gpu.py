@@ -12,6 +12,7 @@ import pytest
 
 from conftest import GOLDEN, load_golden
 from helpers import check_csr_invariants, poisson_case, random_csr
+from valuecheck import check_bounded
 from benchmark_spgemm_using_csr_amd import facade as bhmod
 from benchmark_spgemm_using_csr_amd.facade import spgemm_csr
 
@@ -34,6 +35,8 @@ def _check(oracle, m, k, n, A, B, exact=True, options=None):
         assert res["ok"], ("class path / defaults", res)
         if exact:
             assert np.array_equal(Cx, ref[2])
+        else:
+            check_bounded(oracle, m, k, n, A, B, (Cp, Cj, Cx), "f64", what="class path / defaults: ")
         options = dict(options or {}, class_path=0)
     Cp, Cj, Cx, info = spgemm_csr(m, k, n, Ap, Aj, Ax, Bp, Bj, Bx, options=options)
     assert info["nnzCt"] == oracle.nnzCt(Ap, Aj, Bp)
@@ -42,6 +45,8 @@ def _check(oracle, m, k, n, A, B, exact=True, options=None):
     assert res["ok"], res
     if exact:
         assert np.array_equal(Cx, ref[2])
+    else:
+        check_bounded(oracle, m, k, n, A, B, (Cp, Cj, Cx), "f64")
     check_csr_invariants(m, n, Cp, Cj)
     return Cp, Cj, Cx, info
 
@@ -657,6 +662,7 @@ def test_hub_rows_split_across_workgroups(oracle, case):
     assert np.array_equal(Cp, ref[0]) and np.array_equal(Cj, ref[1])
     if case == "float_values":
         assert oracle.compare(ref, (Cp, Cj, Cx), rel_tol=REL_TOL)["ok"]
+        check_bounded(oracle, m, k, n, A, B, (Cp, Cj, Cx), "f64")
     else:
         assert np.array_equal(Cx.astype(np.float64), ref[2])             # small integers: exact in either build
     check_csr_invariants(m, n, Cp, Cj)
@@ -1440,6 +1446,7 @@ def test_row_class_path(oracle, case):
     assert np.array_equal(Cp, ref[0]) and np.array_equal(Cj, ref[1])
     if case == "float_values":
         assert oracle.compare(ref, (Cp, Cj, Cx), rel_tol=REL_TOL)["ok"]
+        check_bounded(oracle, m, k, n, (A[0], A[1], Ax), (B[0], B[1], Bx), (Cp, Cj, Cx), "f64")
     else:
         assert np.array_equal(Cx.astype(np.float64), ref[2])
     check_csr_invariants(m, n, Cp, Cj)
