@@ -196,17 +196,15 @@ int ensure_b_windows(bhs_handle* h)
     BHS_TRY(ensure(h, h->bWin, (size_t)std::max(h->k, 1) * (size_t)kWwStride * sizeof(unsigned short)));
     unsigned* hist = (unsigned*)h->bWinTab.p;
     int* tab = (int*)h->bWinTab.p + kWwBuckets;
-    EventPair* ep = nullptr;
-    BHS_TRY(timed_begin(h, "b_windows", &ep));
-    BHS_HIP(hipMemsetAsync(hist, 0, kWwBuckets * sizeof(unsigned), h->stream));
-    const long long gh = std::max<long long>(1, std::min<long long>(((long long)h->nnzB + 4095) / 4096, (long long)h->numCU * 4));
-    hipLaunchKernelGGL(k_window_hist, dim3((unsigned)gh), dim3(256), 0, h->stream, (long long)h->nnzB, h->dBj, hist);
-    hipLaunchKernelGGL(k_window_pick, dim3(1), dim3(64), 0, h->stream, h->n, (long long)h->nnzB, (const unsigned*)hist, tab);
-    hipLaunchKernelGGL(k_b_windows16, dim3((unsigned)((h->k + 255) / 256)), dim3(256), 0, h->stream, h->k, (const int*)tab, h->dBp, h->dBj,
-                       (unsigned short*)h->bWin.p);
-    BHS_HIP(hipGetLastError());
-    BHS_TRY(timed_end(h, ep));
-    h->stats[ep->stat].launches++;
+    BHS_TRY(timed(h, "b_windows", 0, [&] {
+        BHS_HIP(hipMemsetAsync(hist, 0, kWwBuckets * sizeof(unsigned), h->stream));
+        const long long gh = std::max<long long>(1, std::min<long long>(((long long)h->nnzB + 4095) / 4096, (long long)h->numCU * 4));
+        hipLaunchKernelGGL(k_window_hist, dim3((unsigned)gh), dim3(256), 0, h->stream, (long long)h->nnzB, h->dBj, hist);
+        hipLaunchKernelGGL(k_window_pick, dim3(1), dim3(64), 0, h->stream, h->n, (long long)h->nnzB, (const unsigned*)hist, tab);
+        hipLaunchKernelGGL(k_b_windows16, dim3((unsigned)((h->k + 255) / 256)), dim3(256), 0, h->stream, h->k, (const int*)tab, h->dBp, h->dBj,
+                           (unsigned short*)h->bWin.p);
+        return 1;
+    }));
     h->ps.bWinBuilt = true;
     return BHS_SUCCESS;
 }

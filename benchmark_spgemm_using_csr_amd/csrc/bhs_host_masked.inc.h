@@ -37,16 +37,13 @@ int masked_run(bhs_handle* h, const int* dMp, const int* dMj, int nnzM, value_t*
 
     BHS_HIP(hipEventRecord(h->maskEv[0], h->stream));
     BHS_HIP(hipMemsetAsync(ctl, 0, sizeof(int) * MS_INTS, h->stream));
-    EventPair* ep = nullptr;
-    BHS_TRY(timed_begin(h, "masked_scan", &ep));
-    const long long gs = std::max<long long>(1, ((long long)m + kMaskScanRows - 1) / kMaskScanRows);
-    hipLaunchKernelGGL(k_masked_scan, dim3((unsigned)gs), dim3(256), 0, h->stream, m, h->n, nnzM, dMp, dMj, h->dAp, h->dAj,
-                       h->dBp, spec, ctl, (int2*)h->maskQueue.p);
-    BHS_HIP(hipGetLastError());
-    BHS_TRY(timed_end(h, ep));
-    const int scanStat = ep->stat;
-    h->stats[scanStat].launches++;
-    h->stats[scanStat].rows += m;
+    int scanStat = 0;
+    BHS_TRY(timed(h, "masked_scan", m, [&] {
+        const long long gs = std::max<long long>(1, ((long long)m + kMaskScanRows - 1) / kMaskScanRows);
+        hipLaunchKernelGGL(k_masked_scan, dim3((unsigned)gs), dim3(256), 0, h->stream, m, h->n, nnzM, dMp, dMj, h->dAp, h->dAj,
+                           h->dBp, spec, ctl, (int2*)h->maskQueue.p);
+        return 1;
+    }, &scanStat));
     int* hs = h->maskHost;
     BHS_HIP(hipMemcpyAsync(hs, ctl, sizeof(int) * MS_INTS, hipMemcpyDeviceToHost, h->stream));
     BHS_TRY(wait_stream(h));
@@ -59,63 +56,51 @@ int masked_run(bhs_handle* h, const int* dMp, const int* dMj, int nnzM, value_t*
     int count[kMaskBins];
     memcpy(count, hs + MS_COUNT, sizeof(count));
 
-    auto family = [&](const char* name, int bin, auto&& launch) -> int {
-        EventPair* e = nullptr;
-        BHS_TRY(timed_begin(h, name, &e));
-        const int launches = launch();
-        BHS_HIP(hipGetLastError());
-        BHS_TRY(timed_end(h, e));
-        StatRec& r = h->stats[e->stat];
-        r.launches += launches;
-        r.rows += count[bin];
-        r.products += (int64_t)sums[bin];
-        return BHS_SUCCESS;
-    };
     const int* Mp = dMp;
+    int stat = 0;
     if (count[kMaskShort]) {
         const int nq = count[kMaskShort];
-        BHS_TRY(family("masked_short", kMaskShort, [&] {
+        BHS_TRY(timed(h, "masked_short", nq, [&] {
             hipLaunchKernelGGL((k_masked_lds<16, kMaskShortLM, 256>), dim3((unsigned)((nq + 15) / 16)), dim3(256), 0, h->stream, nq,
                                queue + (size_t)kMaskShort * m, Mp, dMj, h->dAp, h->dAj, h->dAx, h->dBp, h->dBj, h->dBx, bSorted, dValC);
             return 1;
-        }));
+        }, &stat));
+        h->stats[stat].products += (int64_t)sums[kMaskShort];
     }
     if (count[kMaskWaveS] || count[kMaskWaveL]) {
         const int nS = count[kMaskWaveS], nL = count[kMaskWaveL];
-        EventPair* e = nullptr;
-        BHS_TRY(timed_begin(h, "masked_wave", &e));
-        if (nS)
-            hipLaunchKernelGGL((k_masked_lds<64, kMaskWaveTab, 256>), dim3((unsigned)((nS + 3) / 4)), dim3(256), 0, h->stream, nS,
-                               queue + (size_t)kMaskWaveS * m, Mp, dMj, h->dAp, h->dAj, h->dAx, h->dBp, h->dBj, h->dBx, bSorted, dValC);
-        if (nL)
-            hipLaunchKernelGGL((k_masked_lds<64, kMaskHubLds, 64>), dim3((unsigned)nL), dim3(64), 0, h->stream, nL,
-                               queue + (size_t)kMaskWaveL * m, Mp, dMj, h->dAp, h->dAj, h->dAx, h->dBp, h->dBj, h->dBx, bSorted, dValC);
-        BHS_HIP(hipGetLastError());
-        BHS_TRY(timed_end(h, e));
-        StatRec& r = h->stats[e->stat];
-        r.launches += (nS ? 1 : 0) + (nL ? 1 : 0);
-        r.rows += nS + nL;
-        r.products += (int64_t)(sums[kMaskWaveS] + sums[kMaskWaveL]);
+        BHS_TRY(timed(h, "masked_wave", nS + nL, [&] {
+            if (nS)
+                hipLaunchKernelGGL((k_masked_lds<64, kMaskWaveTab, 256>), dim3((unsigned)((nS + 3) / 4)), dim3(256), 0, h->stream, nS,
+                                   queue + (size_t)kMaskWaveS * m, Mp, dMj, h->dAp, h->dAj, h->dAx, h->dBp, h->dBj, h->dBx, bSorted, dValC);
+            if (nL)
+                hipLaunchKernelGGL((k_masked_lds<64, kMaskHubLds, 64>), dim3((unsigned)nL), dim3(64), 0, h->stream, nL,
+                                   queue + (size_t)kMaskWaveL * m, Mp, dMj, h->dAp, h->dAj, h->dAx, h->dBp, h->dBj, h->dBx, bSorted, dValC);
+            return (nS ? 1 : 0) + (nL ? 1 : 0);
+        }, &stat));
+        h->stats[stat].products += (int64_t)(sums[kMaskWaveS] + sums[kMaskWaveL]);
     }
     if (count[kMaskLong]) {
         const int nq = count[kMaskLong];
-        BHS_TRY(family("masked_long", kMaskLong, [&] {
+        BHS_TRY(timed(h, "masked_long", nq, [&] {
             hipLaunchKernelGGL(k_masked_long, dim3((unsigned)nq), dim3(256), 0, h->stream, nq, queue + (size_t)kMaskLong * m, Mp,
                                dMj, h->dAp, h->dAj, h->dAx, h->dBp, h->dBj, h->dBx, bSorted, dValC);
             return 1;
-        }));
+        }, &stat));
+        h->stats[stat].products += (int64_t)sums[kMaskLong];
     }
     if (count[kMaskHub]) {
         const int nq = count[kMaskHub];
         const int parts = (int)std::max<unsigned long long>(1, std::min<unsigned long long>(kMaskHubMaxParts, (hubMax + kMaskHubItem - 1) / kMaskHubItem));
         const unsigned gy = (unsigned)std::min(nq, 65535);
-        BHS_TRY(family("masked_hub", kMaskHub, [&] {
+        BHS_TRY(timed(h, "masked_hub", nq, [&] {
             const int2* q = queue + (size_t)kMaskHub * m;
             hipLaunchKernelGGL(k_masked_zero, dim3(gy), dim3(256), 0, h->stream, nq, q, Mp, dValC);
             hipLaunchKernelGGL(k_masked_hub, dim3((unsigned)parts, gy), dim3(256), 0, h->stream, nq, q, Mp, dMj, h->dAp, h->dAj,
                                h->dAx, h->dBp, h->dBj, h->dBx, bSorted, std::min(kMaskHubLds, cap), dValC);
             return 2;
-        }));
+        }, &stat));
+        h->stats[stat].products += (int64_t)sums[kMaskHub];
     }
     BHS_HIP(hipEventRecord(h->maskEv[1], h->stream));
     BHS_TRY(wait_stream(h));

@@ -69,6 +69,68 @@ int join_bins(bhs_handle* h)
     return BHS_SUCCESS;
 }
 
+// a stage's bin starts in its queue: the counts' prefix sum (bin 0, the rows without products, has no queue)
+void bin_starts(const int* count, int* start)
+{
+    start[0] = 0;
+    for (int b = 0; b < kMaxBins; ++b) start[b + 1] = start[b] + (b == 0 ? 0 : count[b]);
+}
+
+// The bins of a stage (NUM false: symbolic, the counts into Cp; true: numeric), each on its kernel record, booked in
+// ps.symStat / ps.numStat: the side streams forked (fork_bins; forkAlways: fork whatever the bins), then the lane and hub
+// bins -- symbolic: lane first, numeric: hub first -- and the size bins from the longest rows down, joined.  queue:
+// nullptr where the kernels take their rows straight from rowPtrA (direct launches).  merge: neighbouring bins that all
+// run the same LDS-bitmap kernel (one workgroup per CU: two such kernels side by side only take CUs from each other, and
+// the shorter bins' launch would trail behind) go as ONE queue, taken from its end so that the longest rows start first.
+// beside: where the bins stay unforked, they run on one side stream beside `stream` (mixed mode; its caller joins it).
+// A lane-first symbolic stage's lane kernel also writes ub[] (laneUb), the product total (laneCt) and the block sums.
+template <bool NUM>
+int run_bins(bhs_handle* h, const int* count, const int* start, const int4* queue, bool merge, int laneK, bool forkAlways = false,
+             bool beside = false, int* laneUb = nullptr, unsigned long long* laneCt = nullptr, int* laneBlockSums = nullptr)
+{
+    const int nbins = NUM ? kNumNumBins : kNumSymBins;
+    const KernelCfg* cfg = NUM ? kNumCfg : kSymCfg;
+    int* stat = NUM ? h->ps.numStat : h->ps.symStat;
+    BHS_TRY(fork_bins(h, count, nbins, forkAlways));
+    if (beside && !h->binsForked) {
+        BHS_HIP(hipEventRecord(h->evFork, h->stream));
+        BHS_HIP(hipStreamWaitEvent(h->binStream[0], h->evFork, 0));
+        h->besideStream = h->binStream[0];
+    }
+    auto lane = [&]() -> int {
+        if (!count[kLaneBin]) return BHS_SUCCESS;
+        bin_stream(h, kLaneBin);
+        return timed(h, NUM ? "numeric_lane" : "symbolic_lane", count[kLaneBin], [&] {
+            return one_launch(launch_row_lane<NUM>(h, laneK, queue ? queue + start[kLaneBin] : nullptr, count[kLaneBin], (int*)h->Cp.p,
+                                                   laneUb, laneCt, nullptr, laneBlockSums));
+        }, &stat[kLaneBin]);
+    };
+    if (!NUM) BHS_TRY(lane());
+    if (count[kHubBin]) {
+        bin_stream(h, kHubBin);
+        BHS_TRY(timed(h, NUM ? "numeric_hub_rows" : "symbolic_hub_rows", count[kHubBin], [&] {
+            return one_launch(launch_hub<NUM>(h, queue + start[kHubBin], count[kHubBin], (int*)h->Cp.p));
+        }, &stat[kHubBin]));
+    }
+    if (NUM) BHS_TRY(lane());
+    // (bb's kernel: 0 not the bitmap, 1 the LDS bitmap, 2 / 3 its wave / workgroup windows -- a symbolic bin never takes a window)
+    auto kernel_of = [&](int bb) { return !bin_takes_lds_bitmap<NUM>(h, cfg[bb]) ? 0 : bin_takes_wave_window<NUM>(h, cfg[bb]) ? (cfg[bb].win ? 3 : 2) : 1; };
+    for (int b = nbins - 1; b >= 1; --b) {
+        if (!count[b]) continue;
+        int lo = b, rows = count[b];
+        if (queue && merge && h->mergeBitmapBins && kernel_of(b))
+            while (lo - 1 >= 2 && kernel_of(lo - 1) == kernel_of(b)) { --lo; rows += count[lo]; }
+        bin_stream(h, b);
+        int s = 0;
+        BHS_TRY(timed(h, NUM ? kNumNames[b] : kSymNames[b], rows, [&] {
+            return one_launch(dispatch_bin<NUM>(h, cfg[b], queue ? queue + start[lo] : nullptr, rows, (int*)h->Cp.p, lo < b));
+        }, &s));
+        for (int bb = lo; bb <= b; ++bb) if (count[bb]) stat[bb] = s;
+        b = lo;                                                     // (the merged bins are done)
+    }
+    return join_bins(h);
+}
+
 // Stages 1 and 2 of the general pipeline: upper bound, symbolic bins and queues, the symbolic kernels.  Leaves the
 // per-row counts in Cp and tells stage 3 which choices it made.
 struct SymChoices {
@@ -76,6 +138,9 @@ struct SymChoices {
     bool blockSums = false;           // the lane kernel left the entries of every block of 256 rows (laneBlockSums)
     int laneK = 0, hubRows = 0;
     BinSpec numSpec;
+    int mixRows = 0;                  // mixed mode: the rows without a class, their products and symbolic bins
+    unsigned long long mixProducts = 0;
+    int mixSymCount[kMaxBins];
 };
 
 int symbolic_general(bhs_handle* h, SymChoices& out)
@@ -109,7 +174,6 @@ int symbolic_general(bhs_handle* h, SymChoices& out)
         numSpec.laneMax = std::min(numSpec.laneMax, kLaneNumMax);
     }
     BHS_HIP(hipMemsetAsync(small, 0, sizeof(int) * S_ZERO_END, h->stream));
-    EventPair* ep;
     h->cmpActive = false;
     // (the undecided first multiply on a data set only measures the ratio: bins and symbolic pass stay plain)
     const bool cmpRun = h->compressB && h->bSorted && h->forcePath == 0 && h->maxTableLog2 >= 15 && h->ps.spanWPL == 0 &&
@@ -120,11 +184,7 @@ int symbolic_general(bhs_handle* h, SymChoices& out)
         BHS_TRY(ensure(h, h->cPair, sizeof(int2) * (size_t)std::max(h->nnzB, 1)));
         BHS_TRY(ensure(h, h->cLen, sizeof(int2) * (size_t)std::max(h->k, 1)));
         BHS_TRY(ensure(h, h->symKey, sizeof(int) * (size_t)m));
-        BHS_TRY(timed_begin(h, "compress_b", &ep));
-        BHS_TRY(launch_compress_b(h));
-        BHS_TRY(timed_end(h, ep));
-        h->stats[ep->stat].launches++;
-        h->stats[ep->stat].rows += h->k;
+        BHS_TRY(timed(h, "compress_b", h->k, [&] { return one_launch(launch_compress_b(h)); }));
     }
     const int* symKeys = cmpBins ? (const int*)h->symKey.p : (const int*)h->ub.p;
     // "Lane-first": every row of A has <= laneK entries and every row of B is short, so every row can go through
@@ -155,111 +215,64 @@ int symbolic_general(bhs_handle* h, SymChoices& out)
     }
     bool symDirect = noUpperBound;
     if (!noUpperBound) {
-    BHS_TRY(timed_begin(h, "upper_bound", &ep));
-    BHS_TRY(launch_upper_bound(h, symSpec, cmpBins, symSpec.upper[8]));
-    BHS_TRY(timed_end(h, ep));
-    h->stats[ep->stat].launches++;
-    h->stats[ep->stat].rows += m;
-    // the queues are filled while the host waits for the bin counts (their starts: k_bin_starts, the host's own sum below)
-    const bool earlyFill = h->earlyFill != 0;
-    auto fill_sym = [&]() -> int {
-        long long grid = std::min<long long>(((long long)m + kFillTile - 1) / kFillTile, (long long)h->numCU * 8);
-        BHS_TRY(timed_begin(h, "fill_queues", &ep));
-        hipLaunchKernelGGL(k_fill_queues<false>, dim3((unsigned)grid), dim3(256), 0, h->stream, m,
-                           symKeys, h->dAp, (const int*)h->ub.p, (const int*)(small + S_SYM_START),
-                           small + S_SYM_CURSOR, (int4*)h->queue.p, symSpec,
-                           (unsigned long long*)(small + S_SYM_SUMS));
-        BHS_HIP(hipGetLastError());
-        BHS_TRY(timed_end(h, ep));
-        h->stats[ep->stat].launches++;
-        return BHS_SUCCESS;
-    };
-    if (earlyFill) {
-        hipLaunchKernelGGL(k_bin_starts, dim3(1), dim3(64), 0, h->stream, (const int*)(small + S_SYM_COUNT), small + S_SYM_START);
-        BHS_TRY(fill_sym());
-    }
-    BHS_HIP(hipMemcpyAsync(hs, small, sizeof(int) * S_SMALL_INTS, hipMemcpyDeviceToHost, h->stream));
-    BHS_TRY(wait_stream(h));
-    symStart[0] = 0;
-    for (int b = 0; b < kMaxBins; ++b) {
-        symCount[b] = hs[S_SYM_COUNT + b];
-        symStart[b + 1] = symStart[b] + (b == 0 ? 0 : symCount[b]);
-    }
-    unsigned long long tot;
-    memcpy(&tot, hs + S_TOTAL_CT, 8);
-    h->nnzCt = (long long)tot;
-    if (cmpRun) {
-        unsigned long long pairs;
-        memcpy(&pairs, hs + S_PAIRS, 8);
-        if (h->cmpState == 0) {
-            const double avgP = h->avgRowA * h->avgRowB;          // (the rule of bhs_set_data's count)
-            h->cmpState = ((avgP > 1536.0 && (double)pairs <= 0.6 * (double)h->nnzB) || (double)pairs <= 0.25 * (double)h->nnzB) ? 1 : -1;
+        BHS_TRY(timed(h, "upper_bound", m, [&] { return one_launch(launch_upper_bound(h, symSpec, cmpBins, symSpec.upper[8])); }));
+        // the queues are filled while the host waits for the bin counts (their starts: k_bin_starts, the host's own sum below)
+        const bool earlyFill = h->earlyFill != 0;
+        auto fill_sym = [&]() -> int {
+            long long grid = std::min<long long>(((long long)m + kFillTile - 1) / kFillTile, (long long)h->numCU * 8);
+            return timed(h, "fill_queues", 0, [&] {
+                hipLaunchKernelGGL(k_fill_queues<false>, dim3((unsigned)grid), dim3(256), 0, h->stream, m,
+                                   symKeys, h->dAp, (const int*)h->ub.p, (const int*)(small + S_SYM_START),
+                                   small + S_SYM_CURSOR, (int4*)h->queue.p, symSpec,
+                                   (unsigned long long*)(small + S_SYM_SUMS));
+                return 1;
+            });
+        };
+        if (earlyFill) {
+            hipLaunchKernelGGL(k_bin_starts, dim3(1), dim3(64), 0, h->stream, (const int*)(small + S_SYM_COUNT), small + S_SYM_START);
+            BHS_TRY(fill_sym());
         }
-        h->cmpActive = cmpBins;
-        if (h->verbose > 1) printf("  [compress_b] %llu pairs for %d entries: %s\n", pairs, h->nnzB, h->cmpActive ? "used" : "not used");
+        BHS_HIP(hipMemcpyAsync(hs, small, sizeof(int) * S_SMALL_INTS, hipMemcpyDeviceToHost, h->stream));
+        BHS_TRY(wait_stream(h));
+        for (int b = 0; b < kMaxBins; ++b) symCount[b] = hs[S_SYM_COUNT + b];
+        bin_starts(symCount, symStart);
+        unsigned long long tot;
+        memcpy(&tot, hs + S_TOTAL_CT, 8);
+        h->nnzCt = (long long)tot;
+        if (cmpRun) {
+            unsigned long long pairs;
+            memcpy(&pairs, hs + S_PAIRS, 8);
+            if (h->cmpState == 0) {
+                const double avgP = h->avgRowA * h->avgRowB;          // (the rule of bhs_set_data's count)
+                h->cmpState = ((avgP > 1536.0 && (double)pairs <= 0.6 * (double)h->nnzB) || (double)pairs <= 0.25 * (double)h->nnzB) ? 1 : -1;
+            }
+            h->cmpActive = cmpBins;
+            if (h->verbose > 1) printf("  [compress_b] %llu pairs for %d entries: %s\n", pairs, h->nnzB, h->cmpActive ? "used" : "not used");
+        }
+        // "Direct" stages: when EVERY row of the matrix sits in the lane bin or the quad bin (stencils: poisson5pt,
+        // 7pt, 9pt), that bin's queue would list the rows 0..m-1 in order -- the fill pass is skipped and the kernel
+        // derives its descriptors from rowPtrA (and rowPtrC) itself.
+        symDirect = h->directBins && (symCount[kLaneBin] == m || symCount[1] == m);
+        if (!symDirect && !earlyFill) {
+            memcpy(hs + S_SMALL_INTS, symStart, sizeof(int) * kMaxBins);        // pinned staging: a truly asynchronous H2D
+            BHS_HIP(hipMemcpyAsync(small + S_SYM_START, hs + S_SMALL_INTS, sizeof(int) * kMaxBins, hipMemcpyHostToDevice, h->stream));
+            BHS_TRY(fill_sym());
+        }
     }
-    // "Direct" stages: when EVERY row of the matrix sits in the lane bin or the quad bin (stencils: poisson5pt,
-    // 7pt, 9pt), that bin's queue would list the rows 0..m-1 in order -- the fill pass is skipped and the kernel
-    // derives its descriptors from rowPtrA (and rowPtrC) itself.
-    symDirect = h->directBins && (symCount[kLaneBin] == m || symCount[1] == m);
-    if (!symDirect && !earlyFill) {
-    memcpy(hs + S_SMALL_INTS, symStart, sizeof(int) * kMaxBins);        // pinned staging: a truly asynchronous H2D
-    BHS_HIP(hipMemcpyAsync(small + S_SYM_START, hs + S_SMALL_INTS, sizeof(int) * kMaxBins, hipMemcpyHostToDevice, h->stream));
-    BHS_TRY(fill_sym());
-    }
-    }   // !noUpperBound
     const int4* symQueue = symDirect ? nullptr : (const int4*)h->queue.p;
     BHS_HIP(hipEventRecord(h->ev[1], h->stream));
 
     // ------------------------------------------------------------ stage 2: symbolic
-    int (&symStat)[kMaxBins] = h->ps.symStat;
     for (int b = 0; b < kMaxBins; ++b) h->ps.symStat[b] = h->ps.numStat[b] = -1;
-    BHS_TRY(fork_bins(h, symCount, kNumSymBins));
-    if (symCount[kLaneBin]) {
-        bin_stream(h, kLaneBin);
-        BHS_TRY(timed_begin(h, "symbolic_lane", &ep));
-        int* blockSums = nullptr;                          // (lane-first: the numeric kernel may make rowPtrC from these, pipeline_symbolic)
-        if (laneFirst && h->laneFromCounts && (long long)m <= 256LL * kLaneFromCountsBlocks) {
-            // (the blocks' sums, then -- 8-byte aligned -- their exclusive scan and the total)
-            BHS_TRY(ensure(h, h->laneBlockSums, sizeof(int) * (size_t)kLaneFromCountsBlocks + sizeof(long long) * ((size_t)kLaneFromCountsBlocks + 1)));
-            blockSums = (int*)h->laneBlockSums.p;
-        }
-        BHS_TRY(launch_row_lane<false>(h, laneK, symQueue ? symQueue + symStart[kLaneBin] : nullptr, symCount[kLaneBin], (int*)h->Cp.p,
-                                       laneFirst ? (int*)h->ub.p : nullptr,
-                                       laneFirst ? (unsigned long long*)(small + S_CT_SLOTS) : nullptr, nullptr, blockSums));
-        out.blockSums = blockSums != nullptr;
-        BHS_TRY(timed_end(h, ep));
-        h->stats[ep->stat].launches++;
-        h->stats[ep->stat].rows += symCount[kLaneBin];
-        symStat[kLaneBin] = ep->stat;
+    int* blockSums = nullptr;                          // (lane-first: the numeric kernel may make rowPtrC from these, pipeline_symbolic)
+    if (laneFirst && h->laneFromCounts && (long long)m <= 256LL * kLaneFromCountsBlocks) {
+        // (the blocks' sums, then -- 8-byte aligned -- their exclusive scan and the total)
+        BHS_TRY(ensure(h, h->laneBlockSums, sizeof(int) * (size_t)kLaneFromCountsBlocks + sizeof(long long) * ((size_t)kLaneFromCountsBlocks + 1)));
+        blockSums = (int*)h->laneBlockSums.p;
     }
-    if (symCount[kHubBin]) {
-        bin_stream(h, kHubBin);
-        BHS_TRY(timed_begin(h, "symbolic_hub_rows", &ep));
-        int rc = launch_hub<false>(h, symQueue + symStart[kHubBin], symCount[kHubBin], (int*)h->Cp.p);
-        if (rc) { h->ls = h->stream; return rc; }
-        BHS_TRY(timed_end(h, ep));
-        h->stats[ep->stat].launches++;
-        h->stats[ep->stat].rows += symCount[kHubBin];
-        symStat[kHubBin] = ep->stat;
-    }
-    for (int i = 1; i < kNumSymBins; ++i) {
-        const int b = kNumSymBins - i;                              // longest rows first: they have the longest tails
-        if (!symCount[b]) continue;
-        // (neighbouring bins that all run the LDS-bitmap kernel go as ONE queue, taken from its end: as in the numeric stage)
-        int lo = b, rows = symCount[b];
-        if (symQueue && h->mergeBitmapBins && bin_takes_lds_bitmap<false>(h, kSymCfg[b]))
-            while (lo - 1 >= 2 && bin_takes_lds_bitmap<false>(h, kSymCfg[lo - 1])) { --lo; rows += symCount[lo]; }
-        bin_stream(h, b);
-        BHS_TRY(timed_begin(h, kSymNames[b], &ep));
-        int rc = dispatch_bin<false>(h, kSymCfg[b], symQueue ? symQueue + symStart[lo] : nullptr, rows, (int*)h->Cp.p, lo < b);
-        if (rc) { h->ls = h->stream; return rc; }
-        BHS_TRY(timed_end(h, ep));
-        h->stats[ep->stat].launches++;
-        h->stats[ep->stat].rows += rows;
-        for (int bb = lo; bb <= b; ++bb) { if (symCount[bb]) symStat[bb] = ep->stat; symCount[bb] = 0; }
-    }
-    BHS_TRY(join_bins(h));
+    out.blockSums = blockSums != nullptr;
+    BHS_TRY(run_bins<false>(h, symCount, symStart, symQueue, true, laneK, false, false, laneFirst ? (int*)h->ub.p : nullptr,
+                            laneFirst ? (unsigned long long*)(small + S_CT_SLOTS) : nullptr, blockSums));
     BHS_HIP(hipEventRecord(h->ev[2], h->stream));
 
     out.noUpperBound = noUpperBound;
@@ -320,7 +333,6 @@ int symbolic_class(bhs_handle* h, bool mixed, const BinSpec& symSpec)
     const int m = h->m, k = h->k;
     const int clsA = cls_row_a(h), clsB = cls_row_b(h);           // the longest rows the classifier is sized for
     int* small = (int*)h->small.p;
-    EventPair* ep;
     BHS_TRY(ensure(h, h->classB, sizeof(int) * (size_t)std::max(k, 1)));
     BHS_TRY(ensure(h, h->classC, sizeof(int) * (size_t)std::max(m, 1)));
     BHS_TRY(ensure(h, h->classTab, sizeof(unsigned long long) * 2 * kClassSlots));
@@ -352,7 +364,6 @@ int symbolic_class(bhs_handle* h, bool mixed, const BinSpec& symSpec)
     unsigned long long* tabB = (unsigned long long*)h->classTab.p;
     unsigned long long* tabA = tabB + kClassSlots;
     int* cstats = small + S_CT_SLOTS;
-    BHS_TRY(timed_begin(h, "classify_rows", &ep));
     // lanes per row: the average row, rounded up to a power of two
     // Three launches per matrix: k_class_heads lists the rows that differ from the row before them (and notes for
     // every other row which head it follows), k_class_rows classifies the listed rows, k_class_propagate hands the
@@ -362,16 +373,6 @@ int symbolic_class(bhs_handle* h, bool mixed, const BinSpec& symSpec)
     };
     auto heads_grid = [&](int n, int G) { const long long perBlock = (long long)(kClassHeadsBlock / 64) * class_head_piece(G); return (unsigned)std::max<long long>(1, ((long long)n + perBlock - 1) / perBlock); };
     auto heads_cap = [&](int n, int G) { return (int)(((long long)heads_grid(n, G) + kClassHeadSegs - 1) / kClassHeadSegs) * (kClassHeadsBlock / 64) * class_head_piece(G); };    // slots per list
-    // A as a row block of a larger product (multi-GPU): only the rows of B that A points at need a class
-    const int* bRange = nullptr;
-    if ((long long)m * 2 <= (long long)k) {
-        int* rg = cstats + CS_RANGE;
-        BHS_HIP(hipMemsetD32Async((hipDeviceptr_t)rg, 0x7fffffff, 1, h->stream));
-        BHS_HIP(hipMemsetD32Async((hipDeviceptr_t)(rg + 1), -1, 1, h->stream));
-        const unsigned gr = (unsigned)std::max<long long>(1, std::min<long long>(((long long)h->nnzA + 255) / 256, (long long)h->numCU * 8));
-        hipLaunchKernelGGL(k_class_col_range, dim3(gr), dim3(256), 0, h->stream, (long long)h->nnzA, h->dAj, rg);
-        bRange = rg;
-    }
     int* headsL = (int*)h->classHeads.p;                            // (one list area: B's is used up before A's is written)
     int* nHeadsB = (int*)h->classHeadCnt.p;
     int* nHeadsA = nHeadsB + 16 * kClassHeadSegs;
@@ -434,58 +435,95 @@ int symbolic_class(bhs_handle* h, bool mixed, const BinSpec& symSpec)
     int* countA = mixed ? countB + kClassSlots : nullptr;
     const unsigned histGridB = (unsigned)std::max<long long>(1, std::min<long long>(((long long)k + kMixHistBlock - 1) / kMixHistBlock, (long long)h->numCU * 2));
     const unsigned histGridA = (unsigned)std::max<long long>(1, std::min<long long>(((long long)m + kMixHistBlock - 1) / kMixHistBlock, (long long)h->numCU * 2));
-    int rc = classify(template_int<0>{}, k, h->dBp, h->dBj, (const int*)nullptr, tabB, (int*)h->classB.p, bRange, nHeadsB, GB, clsB, periodB);
-    if (rc == BHS_SUCCESS && mixed) {
-        // a row of B that is the only one of its kind (a perturbed row) loses its class: the rows of A that point at it
-        // would each claim a class of their own in A's table
-        hipLaunchKernelGGL(k_mix_class_hist, dim3(histGridB), dim3(kMixHistBlock), 0, h->stream, k, (const int*)h->classB.p, countB, bRange);
-        hipLaunchKernelGGL(k_mix_prune, dim3(propGrid), dim3(256), 0, h->stream, k, (int*)h->classB.p, (const int*)countB, bRange);
-    }
-    if (rc == BHS_SUCCESS)
-        rc = classify(template_int<1>{}, m, h->dAp, h->dAj, (const int*)h->classB.p, tabA, (int*)h->classC.p, (const int*)nullptr, nHeadsA, GA, clsA, periodA);
-    if (rc != BHS_SUCCESS) return rc;
-    if (mixed) hipLaunchKernelGGL(k_mix_class_hist, dim3(histGridA), dim3(kMixHistBlock), 0, h->stream, m, (const int*)h->classC.p, countA, (const int*)nullptr);
-    BHS_HIP(hipGetLastError());
-    BHS_TRY(timed_end(h, ep));
-    h->stats[ep->stat].launches += h->classHeadsOn == 1 ? 6 : 2;
-    h->stats[ep->stat].rows += (int64_t)m + k;
+    BHS_TRY(timed(h, "classify_rows", (int64_t)m + k, [&] {
+        // A as a row block of a larger product (multi-GPU): only the rows of B that A points at need a class
+        const int* bRange = nullptr;
+        if ((long long)m * 2 <= (long long)k) {
+            int* rg = cstats + CS_RANGE;
+            BHS_HIP(hipMemsetD32Async((hipDeviceptr_t)rg, 0x7fffffff, 1, h->stream));
+            BHS_HIP(hipMemsetD32Async((hipDeviceptr_t)(rg + 1), -1, 1, h->stream));
+            const unsigned gr = (unsigned)std::max<long long>(1, std::min<long long>(((long long)h->nnzA + 255) / 256, (long long)h->numCU * 8));
+            hipLaunchKernelGGL(k_class_col_range, dim3(gr), dim3(256), 0, h->stream, (long long)h->nnzA, h->dAj, rg);
+            bRange = rg;
+        }
+        BHS_TRY(classify(template_int<0>{}, k, h->dBp, h->dBj, (const int*)nullptr, tabB, (int*)h->classB.p, bRange, nHeadsB, GB, clsB, periodB));
+        if (mixed) {
+            // a row of B that is the only one of its kind (a perturbed row) loses its class: the rows of A that point at it
+            // would each claim a class of their own in A's table
+            hipLaunchKernelGGL(k_mix_class_hist, dim3(histGridB), dim3(kMixHistBlock), 0, h->stream, k, (const int*)h->classB.p, countB, bRange);
+            hipLaunchKernelGGL(k_mix_prune, dim3(propGrid), dim3(256), 0, h->stream, k, (int*)h->classB.p, (const int*)countB, bRange);
+        }
+        BHS_TRY(classify(template_int<1>{}, m, h->dAp, h->dAj, (const int*)h->classB.p, tabA, (int*)h->classC.p, (const int*)nullptr, nHeadsA, GA, clsA, periodA));
+        if (mixed) hipLaunchKernelGGL(k_mix_class_hist, dim3(histGridA), dim3(kMixHistBlock), 0, h->stream, m, (const int*)h->classC.p, countA, (const int*)nullptr);
+        return h->classHeadsOn == 1 ? 6 : 2;
+    }));
     BHS_HIP(hipEventRecord(h->ev[1], h->stream));
-    BHS_TRY(timed_begin(h, "class_patterns", &ep));
-    hipLaunchKernelGGL(k_class_patterns, dim3(kClassSlots), dim3(256), 0, h->stream, (const unsigned long long*)tabA,
-                       h->dAp, h->dAj, h->dBp, h->dBj, (int4*)h->classInfo.p,
-                       (unsigned*)h->classMap.p, (unsigned*)h->classMapA.p, (int*)h->classRel.p, (int*)h->classLane.p,
-                       (unsigned*)h->classRing.p, cstats, (const int*)countA);
-    if (bigPossible) {
+    BHS_TRY(timed(h, "class_patterns", 0, [&] {
+        hipLaunchKernelGGL(k_class_patterns, dim3(kClassSlots), dim3(256), 0, h->stream, (const unsigned long long*)tabA,
+                           h->dAp, h->dAj, h->dBp, h->dBj, (int4*)h->classInfo.p,
+                           (unsigned*)h->classMap.p, (unsigned*)h->classMapA.p, (int*)h->classRel.p, (int*)h->classLane.p,
+                           (unsigned*)h->classRing.p, cstats, (const int*)countA);
+        if (!bigPossible) return 1;
         const size_t smemBig = sizeof(int) * 2 * kClassBigMaxP;
         int unused = 0;
         BHS_TRY(kernel_occupancy(h, reinterpret_cast<const void*>(k_class_patterns_big), kClassBigPatThreads, smemBig, &unused));   // (raises its LDS limit)
         hipLaunchKernelGGL(k_class_patterns_big, dim3(kClassSlots), dim3(kClassBigPatThreads), smemBig, h->stream, (const unsigned long long*)tabA,
                            h->dAp, h->dAj, h->dBp, h->dBj, (int4*)h->classInfo.p, (int*)h->classBigIdx.p,
                            (unsigned*)h->classBigMap.p, (int*)h->classRel.p, cstats);
-    }
-    BHS_HIP(hipGetLastError());
-    BHS_TRY(timed_end(h, ep));
-    h->stats[ep->stat].launches += bigPossible ? 2 : 1;
+        return 2;
+    }));
     if (mixed) {
         // the irregular rows: listed, their product counts and symbolic bins
-        BHS_TRY(timed_begin(h, "irregular_rows", &ep));
-        const unsigned gc = (unsigned)std::max<long long>(1, std::min<long long>(((long long)m + kMixCollectTile - 1) / kMixCollectTile, (long long)h->numCU * 8));
-        hipLaunchKernelGGL(k_mix_collect, dim3(gc), dim3(256), 0, h->stream, m, (int*)h->classC.p, (const int4*)h->classInfo.p,
-                           (int*)h->mixList.p, small + S_MIX_COUNT);
-        hipLaunchKernelGGL(k_mix_upper_bound, dim3((unsigned)(h->numCU * 4)), dim3(256), 0, h->stream, (const int*)h->mixList.p,
-                           (const int*)(small + S_MIX_COUNT), h->dAp, h->dAj, h->dBp, (int*)h->ub.p, (int*)h->Cp.p,
-                           (unsigned long long*)(small + S_TOTAL_CT), small + S_SYM_COUNT, symSpec, small + S_MIX_SYM2, coarse_spec(symSpec, kCoarseSym));
-        BHS_HIP(hipGetLastError());
-        BHS_TRY(timed_end(h, ep));
-        h->stats[ep->stat].launches += 2;
+        BHS_TRY(timed(h, "irregular_rows", 0, [&] {
+            const unsigned gc = (unsigned)std::max<long long>(1, std::min<long long>(((long long)m + kMixCollectTile - 1) / kMixCollectTile, (long long)h->numCU * 8));
+            hipLaunchKernelGGL(k_mix_collect, dim3(gc), dim3(256), 0, h->stream, m, (int*)h->classC.p, (const int4*)h->classInfo.p,
+                               (int*)h->mixList.p, small + S_MIX_COUNT);
+            hipLaunchKernelGGL(k_mix_upper_bound, dim3((unsigned)(h->numCU * 4)), dim3(256), 0, h->stream, (const int*)h->mixList.p,
+                               (const int*)(small + S_MIX_COUNT), h->dAp, h->dAj, h->dBp, (int*)h->ub.p, (int*)h->Cp.p,
+                               (unsigned long long*)(small + S_TOTAL_CT), small + S_SYM_COUNT, symSpec, small + S_MIX_SYM2, coarse_spec(symSpec, kCoarseSym));
+            return 2;
+        }));
     }
     BHS_HIP(hipEventRecord(h->ev[2], h->stream));
     return BHS_SUCCESS;
 }
 
-// restart: the same multiply starting over on another path (a refuted speculation, rows without a class): the
-// timers and kernel statistics of the abandoned attempt stay in -- it ran inside this multiply.
-int stage_rowptr_and_open(bhs_handle* h);
+// Does a C of nnzC entries fit the output arrays at hand (the caller's, or the library's pool as it stands)?
+bool c_fits(const bhs_handle* h, long long nnzC)
+{
+    const size_t need = (size_t)std::max<long long>(nnzC, 1);
+    return h->extCj ? nnzC <= h->extCap : (h->Cj.p && h->Cx.p && h->Cj.cap >= need * sizeof(int) && h->Cx.cap >= need * sizeof(value_t));
+}
+
+// the classes' figures (cs[], from the class kernels' statistics) for the numeric kernels' choice
+void take_class_figures(bhs_handle* h, const int* cs)
+{
+    h->ps.classMaxP = cs[CS_MAXP];
+    h->ps.classMaxNnz = cs[CS_MAXNNZ];
+    h->ps.classMaxNA = cs[CS_MAXNA];
+    h->ps.classMaxLB = cs[CS_MAXLB];
+    h->ps.classMaxRing = cs[CS_MAXRING];
+    h->ps.classMaxRing2 = std::max(cs[CS_RINGFULL], cs[CS_RINGONE]);
+    h->ps.classMaxSlab = cs[CS_MAXSLAB];
+    h->ps.classBig = cs[CS_BIGCOUNT];
+    h->ps.classBigMaxP = cs[CS_BIGMAXP];
+}
+
+// Row classes first, for data sets whose rows are short on both sides (the hint from bhs_set_data time is verified on the
+// device row by row)
+// ... and long enough for the classification passes to pay (round 3's kernels, same box): poisson27pt (729 products
+// per row) 4.85 -> 2.1 ms on the class kernels, poisson9pt 1024^2 (81) 0.57 -> 0.47 ms, poisson7pt 128^3 (49) 0.73 ->
+// 0.78 ms, poisson5pt 1024^2 (25) 0.23 -> 0.42 ms: from class_min_products = 64 products per row on
+// ... and enough of them, minTotalProducts: every block of the classifier meets every class once.  (Round 6, class kernels
+// against general pipeline: 16 x 16 entries a row, 25 k rows -- 5.8 M products -- 0.182 / 0.179 ms, 50 k rows 0.192 / 0.266,
+// 100 k rows 0.209 / 0.435; 27 x 8 entries, 50 k rows 0.192 / 0.240; poisson27pt 40^3, 43 M products, 0.219 / 0.249;
+// poisson9pt 512^2, 21 M, 0.192 / 0.194.  Round 3's kernels had put the line at 6e7.)
+bool class_path_first(const bhs_handle* h, double minTotalProducts)
+{
+    return h->classPath && h->forcePath == 0 && h->maxTableLog2 >= 15 && cls_row_a(h) <= kClassMaxRowBig && cls_row_b(h) <= kClassMaxRowBig &&
+           (h->classPath == 2 || (h->avgRowA * h->avgRowB >= (double)h->classMinProducts &&
+                                  (double)h->m * h->avgRowA * h->avgRowB >= minTotalProducts));
+}
 
 // May this multiply's numeric kernel go out on the figures of the last one?  Sets h->ps's class fields from them if so.
 bool class_spec_try(bhs_handle* h)
@@ -495,23 +533,239 @@ bool class_spec_try(bhs_handle* h)
     const int* cs = sp.cs;
     if (cs[CS_FLAGS] || cs[CS_CLASSES] == 0 || cs[CS_BIGCOUNT]) return false;
     if (h->classHeadsOn && h->classPath != 2 && (long long)cs[CS_HEADS] * 4 > (long long)h->m) return false;
-    const size_t need = (size_t)std::max<long long>(sp.nnzC, 1);
-    if (h->extCj ? sp.nnzC > h->extCap : (!h->Cj.p || !h->Cx.p || h->Cj.cap < need * sizeof(int) || h->Cx.cap < need * sizeof(value_t))) return false;
+    if (!c_fits(h, sp.nnzC)) return false;
     h->ps.useClass = true;
-    h->ps.classMaxP = cs[CS_MAXP];
-    h->ps.classMaxNnz = cs[CS_MAXNNZ];
-    h->ps.classMaxNA = cs[CS_MAXNA];
-    h->ps.classMaxLB = cs[CS_MAXLB];
-    h->ps.classMaxRing = cs[CS_MAXRING];
-    h->ps.classMaxRing2 = std::max(cs[CS_RINGFULL], cs[CS_RINGONE]);
-    h->ps.classMaxSlab = cs[CS_MAXSLAB];
-    h->ps.classBig = 0;
-    h->ps.classBigMaxP = cs[CS_BIGMAXP];
+    take_class_figures(h, cs);
     if (!class_ring2_fits(h)) { h->ps.useClass = false; return false; }
     return true;
 }
 
-int pipeline_symbolic(bhs_handle* h, bool restart = false)
+// ... and a lane-first multiply's, on the last one's nnz(C) and "every row in the lane bin" (laneSpec)?
+bool lane_spec_try(const bhs_handle* h, const SymChoices& sc)
+{
+    return sc.laneFirst && h->specNumeric && h->laneSpec.valid && h->laneSpec.laneK == sc.laneK && !h->lazyOut && h->directBins &&
+           (h->laneNumeric == 1 || (h->laneNumeric == 2 && sc.laneK <= 8)) && c_fits(h, h->laneSpec.nnzC);
+}
+
+// The end of pipeline_symbolic: h->ps takes the symbolic stage's choices, ev[3] closes stage 3, rowPtrC goes on its way
+// to the host where the caller wants it there, the multiply is open.
+int open_numeric(bhs_handle* h, const SymChoices& sc)
+{
+    h->ps.noUpperBound = sc.noUpperBound;
+    h->ps.symDirect = sc.symDirect;
+    h->ps.laneK = sc.laneK;
+    h->ps.numSpec = sc.numSpec;
+    BHS_HIP(hipEventRecord(h->ev[3], h->stream));
+    h->rowPtrStaged = false;
+    if (h->wantHostRowPtr) {
+        // rowPtrC is final after the scan: ship it to pinned host memory on a second stream while the
+        // numeric kernels run (the reference does this D2H inside its timed region too, bhsparse_cuda.h:2787)
+        const size_t bytes = sizeof(int) * ((size_t)h->m + 1);
+        BHS_TRY(ensure_host_rowptr(h, bytes));
+        BHS_HIP(hipEventRecord(h->evScanDone, h->stream));
+        BHS_HIP(hipStreamWaitEvent(h->copyStream, h->evScanDone, 0));
+        BHS_HIP(hipMemcpyAsync(h->hostRowPtr, h->Cp.p, bytes, hipMemcpyDeviceToHost, h->copyStream));
+        BHS_HIP(hipEventRecord(h->evCopyDone, h->copyStream));
+        h->rowPtrStaged = true;
+    }
+    h->ps.open = true;
+    return BHS_SUCCESS;
+}
+
+// ... on the figures of the data set's last multiply (nnzC, nnzCt): the device checks them, pipeline_finish sees its verdict
+int open_speculative(bhs_handle* h, const SymChoices& sc, bool lane, long long nnzC, long long nnzCt)
+{
+    h->ps.specLaunched = true;
+    h->ps.specLane = lane;
+    h->specLaunches++;
+    h->nnzC = nnzC;
+    h->nnzCt = nnzCt;                  // (pipeline_finish puts this multiply's own count here)
+    return open_numeric(h, sc);
+}
+
+// A verdict inside pipeline_symbolic: the same multiply starts over on the path the handle state now names (rows without
+// a class, a refuted direct launch).  Never leaves pipeline_symbolic.
+constexpr int kRestart = -1001;
+
+// Mixed mode (bhs_class_mix.hip.h): the first of its two read-backs and its verdict, then the symbolic pass of the rows
+// without a class, bin by bin: exact counts into Cp[row] (the general pipeline's stage 2 on the listed rows).
+int symbolic_mixed(bhs_handle* h, BinSpec symSpec, SymChoices& sc)
+{
+    const int m = h->m;
+    int* small = (int*)h->small.p;
+    int* hs = h->hostSmall;
+    // what the classes look like and how many rows have none
+    BHS_HIP(hipMemcpyAsync(hs, small, sizeof(int) * S_SMALL_INTS, hipMemcpyDeviceToHost, h->stream));
+    BHS_TRY(wait_stream(h));
+    const int* cs = hs + S_CT_SLOTS;
+    const int mixRows = sc.mixRows = hs[S_MIX_COUNT];
+    memcpy(&sc.mixProducts, hs + S_TOTAL_CT, 8);
+    auto to_general = [&](const char* why) {
+        h->classState = -1;
+        if (h->verbose > 1) printf("  [row classes, mixed: %s (%d of %d rows without a class, %d classes, %d rows start a stretch): general pipeline]\n", why, mixRows, m, cs[CS_CLASSES], cs[CS_HEADS]);
+        return kRestart;
+    };
+    if (hs[S_ERR]) return BHS_ERR_INTERNAL;
+    if (cs[CS_CLASSES] == 0) return to_general("no class");
+    if (mixRows > 0) {
+        if ((long long)mixRows * 100 > (long long)h->mixMaxPct * m) return to_general("too many rows without a class");
+        take_class_figures(h, cs);
+        // (the kernels that pass an irregular row by: the ring kernel, and k_class_numeric_big for block-structured grids)
+        if (!cs[CS_BIGCOUNT] && (h->classNumeric < 2 || !class_ring2_fits(h))) return to_general("classes beyond the ring kernel");
+    }
+    // (an irregular row is a head, and so is the row behind it: they are not what the verdict below is about)
+    if (h->classHeadsOn && h->classPath != 2 && !cs[CS_BIGCOUNT] && ((long long)cs[CS_HEADS] - 2LL * mixRows) * 4 > (long long)m)
+        return to_general("rows classify each for itself");
+    if (mixRows == 0) { h->classMixed = 0; h->mixProbed = true; }   // (every row has a class worth its pattern: the clean flow from the next multiply on)
+    if (h->verbose > 1) printf("  [row classes, mixed: %d of %d rows without a class -> the general pipeline's kernels; %d classes]\n", mixRows, m, cs[CS_CLASSES]);
+    if (mixRows == 0) return BHS_SUCCESS;
+    // a handful of rows (fewer than one in sixteen): the ladder with fewer steps -- a launch costs more than a table
+    // that is too large for a few hundred rows
+    const bool coarse = (long long)mixRows * 16 <= (long long)m && h->maxTableLog2 >= 15;
+    if (coarse) {
+        symSpec = coarse_spec(symSpec, kCoarseSym);
+        sc.numSpec = coarse_spec(sc.numSpec, kCoarseNum);
+    }
+    int symStart[kMaxBins + 1];
+    for (int b = 0; b < kMaxBins; ++b) sc.mixSymCount[b] = hs[(coarse ? S_MIX_SYM2 : S_SYM_COUNT) + b];
+    bin_starts(sc.mixSymCount, symStart);
+    h->nnzCt = (long long)sc.mixProducts;                    // (launch_hub sizes its item list by it)
+    h->cmpActive = false;
+    const long long gridF = std::max<long long>(1, std::min<long long>(((long long)mixRows + 255) / 256, (long long)h->numCU * 8));
+    BHS_TRY(timed(h, "fill_queues", 0, [&] {
+        hipLaunchKernelGGL(k_mix_fill<false>, dim3((unsigned)gridF), dim3(256), 0, h->stream, (const int*)h->mixList.p, (const int*)(small + S_MIX_COUNT),
+                           0, 0x7fffffff, (const int*)h->ub.p, h->dAp, (const int*)h->ub.p, (const int*)(small + (coarse ? S_MIX_SYM2 : S_SYM_COUNT)), small + S_SYM_CURSOR,
+                           (int4*)h->queue.p, symSpec, (unsigned long long*)(small + S_SYM_SUMS));
+        return 1;
+    }));
+    return run_bins<false>(h, sc.mixSymCount, symStart, (const int4*)h->queue.p, false, 0, h->mixFork != 0);
+}
+
+// Stage 3's scan: rowPtrC from the per-row counts, nnz(C) -- and the numeric queues where they can be filled behind it.
+int scan_rowptr(bhs_handle* h, bool useClass, const SymChoices& sc)
+{
+    const int m = h->m;
+    int* small = (int*)h->small.p;
+    const BinSpec& numSpec = sc.numSpec;
+    BHS_TRY(timed(h, "scan_rowptr", 0, [&] {
+        if (useClass) {
+            // one pass: every row's count from its class, scanned with look-back over the tiles before (k_class_scan)
+            const int nTiles = (m + kClassScanTile - 1) / kClassScanTile;
+            // (blockSum holds the tile words, cleared by k_class_reset)
+            hipLaunchKernelGGL(k_class_scan, dim3((unsigned)nTiles), dim3(kClassScanBlock), 0, h->stream, m, (const int*)h->classC.p,
+                               (const int4*)h->classInfo.p, (int*)h->Cp.p, (unsigned long long*)h->blockSum.p,
+                               (long long*)(small + S_TOTAL_C), small + S_CT_SLOTS, sc.mixRows > 0, h->dAp, (const int*)h->ub.p, numSpec, small + S_NUM_COUNT);
+            return 1;
+        }
+        if (h->scanOnePass) {
+            // one pass with look-back over the tiles before (k_scan_onepass); the tile words carry this multiply's epoch
+            const int nTiles = (m + kScan1Tile - 1) / kScan1Tile;
+            h->scanEpoch = (h->scanEpoch + 1) & 0x3FFFFu;
+            if (h->scanEpoch == 0) {                                    // (every 2^18 multiplies the words of 2^18 multiplies ago could match)
+                BHS_HIP(hipMemsetAsync(h->blockSum.p, 0, sizeof(unsigned long long) * (size_t)std::max(nTiles, 1), h->stream));
+                h->scanEpoch = 1;
+            }
+            hipLaunchKernelGGL(k_scan_onepass, dim3((unsigned)nTiles), dim3(kScan1Block), 0, h->stream, m, (int*)h->Cp.p, h->dAp,
+                               (unsigned long long*)h->blockSum.p, h->scanEpoch, small + S_SCAN_TICKET, (long long*)(small + S_TOTAL_C),
+                               small + S_NUM_COUNT, numSpec, small + S_MAXCNT, (const int*)h->ub.p);
+            return 1;
+        }
+        const int nScanBlocks = (int)(((long long)m + 1 + kScanTile - 1) / kScanTile);
+        hipLaunchKernelGGL(k_scan_reduce, dim3(nScanBlocks), dim3(256), 0, h->stream, m, (const int*)h->Cp.p, h->dAp,
+                           (long long*)h->blockSum.p, small + S_NUM_COUNT, numSpec, small + S_MAXCNT, (const int*)h->ub.p);
+        hipLaunchKernelGGL(k_scan_blocksums, dim3(1), dim3(1024), 0, h->stream, nScanBlocks,
+                           (long long*)h->blockSum.p, (long long*)(small + S_TOTAL_C));
+        hipLaunchKernelGGL(k_scan_apply, dim3(nScanBlocks), dim3(256), 0, h->stream, m, (int*)h->Cp.p,
+                           (const long long*)h->blockSum.p);
+        return 3;
+    }));
+    if (useClass && sc.mixRows > 0) {
+        // the irregular rows' numeric bins and queue (rowPtrC is final), on the device while the host waits for nnz(C)
+        const long long gridF = std::max<long long>(1, std::min<long long>(((long long)sc.mixRows + 255) / 256, (long long)h->numCU * 8));
+        BHS_TRY(timed(h, "fill_queues", 0, [&] {
+            hipLaunchKernelGGL(k_mix_fill<true>, dim3((unsigned)gridF), dim3(256), 0, h->stream, (const int*)h->mixList.p, (const int*)(small + S_MIX_COUNT),
+                               0, 0x7fffffff, (const int*)h->Cp.p, h->dAp, (const int*)h->ub.p, (const int*)(small + S_NUM_COUNT), small + S_NUM_CURSOR,
+                               (int4*)h->queue.p, numSpec, (unsigned long long*)(small + S_NUM_SUMS));
+            return 1;
+        }));
+    }
+    // ... the numeric queues likewise, where the symbolic stage went by queues (then the numeric stage will): k_scan_onepass
+    // has left the numeric bins' counts
+    h->ps.numQueueFilled = false;
+    // (not where this data set's last multiply ran its numeric stage straight from the row pointers: a hint, it costs or saves a launch)
+    if (!useClass && h->earlyFill && h->scanOnePass && !sc.noUpperBound && !sc.symDirect && h->numDirectHint != 1) {
+        hipLaunchKernelGGL(k_bin_starts, dim3(1), dim3(64), 0, h->stream, (const int*)(small + S_NUM_COUNT), small + S_NUM_START);
+        long long grid = std::min<long long>(((long long)m + kFillTile - 1) / kFillTile, (long long)h->numCU * 8);
+        BHS_TRY(timed(h, "fill_queues", 0, [&] {
+            hipLaunchKernelGGL(k_fill_queues<true>, dim3((unsigned)grid), dim3(256), 0, h->stream, m,
+                               (const int*)h->Cp.p, h->dAp, (const int*)h->ub.p, (const int*)(small + S_NUM_START),
+                               small + S_NUM_CURSOR, (int4*)h->queue.p, numSpec,
+                               (unsigned long long*)(small + S_NUM_SUMS));
+            return 1;
+        }));
+        h->ps.numQueueFilled = true;
+    }
+    return BHS_SUCCESS;
+}
+
+// The class path's verdict on stage 3's read-back: rows without a class, or classes beyond the tables, send the multiply
+// to mixed mode or the data set to the general pipeline (kRestart); otherwise h->ps takes the classes' figures.
+int class_verdict(bhs_handle* h, bool mixedFlow, const SymChoices& sc)
+{
+    const int m = h->m;
+    const int* hs = h->hostSmall;
+    const int* cs = hs + S_CT_SLOTS;
+    if (!mixedFlow) {
+        // (... or a great many classes: single rows that found room in the table, each with a pattern of its own to work out --
+        // the mixed flow counts the rows of every class and leaves the classes of a few rows out; asked once per data set)
+        bool manyClasses = false;
+        if (!cs[CS_FLAGS] && cs[CS_CLASSES] > kClassManyClasses && !h->mixProbed && !cs[CS_BIGCOUNT] && h->classNumeric >= 2) {
+            take_class_figures(h, cs);                    // (only where the mixed flow's ring kernel can take the classes)
+            manyClasses = class_ring2_fits(h);
+        }
+        if ((cs[CS_FLAGS] || manyClasses) && cs[CS_CLASSES] > 0 && h->mixOn) {
+            // a row without a class, or a class beyond the tables: the same multiply once more, with those rows on the general
+            // pipeline's kernels (mixed mode, bhs_class_mix.hip.h) -- and this data set's next multiplies that way from the start
+            h->classMixed = 1;
+            if (h->verbose > 1) printf("  [row classes: flags %d, %d classes: the multiply again in mixed mode]\n", cs[CS_FLAGS], cs[CS_CLASSES]);
+            return kRestart;
+        }
+        if (cs[CS_FLAGS] || cs[CS_CLASSES] == 0) {
+            // ... with mixed mode off, or no class at all: this data set is for the general pipeline
+            h->classState = -1;
+            if (h->verbose > 1) printf("  [row classes: flags %d, %d classes: general pipeline]\n", cs[CS_FLAGS], cs[CS_CLASSES]);
+            return kRestart;
+        }
+        // The class kernels take rows in stretches -- consecutive rows of one class; a matrix whose rows classify but
+        // each for itself (block-diagonal with dense blocks: every row of a block has its own relative pattern) makes
+        // them change class every row: 3.4 ms against 1.9 ms on the general pipeline for 2^20 rows in blocks of 4..32.
+        // More than a quarter of the rows through the table: this data set goes to the general pipeline (class_path = 2
+        // insists on the classes).
+        if (h->classHeadsOn && h->classPath != 2 && !cs[CS_BIGCOUNT] && (long long)cs[CS_HEADS] * 4 > (long long)m) {
+            h->classState = -1;
+            if (h->verbose > 1) printf("  [row classes: %d of %d rows start a stretch: general pipeline]\n", cs[CS_HEADS], m);
+            return kRestart;
+        }
+    }
+    unsigned long long t = 0, v;
+    for (int i = 0; i < kClassSumSlots; ++i) { memcpy(&v, cs + CS_SUMS + 2 * i, 8); t += v; }
+    h->nnzCt = (long long)t + (long long)sc.mixProducts;         // (the rows with a class, the rows without)
+    h->ps.useClass = true;
+    h->ps.mixed = sc.mixRows > 0;
+    h->ps.mixRows = sc.mixRows;
+    h->ps.mixNumFilled = sc.mixRows > 0;
+    h->ps.mixProducts = (long long)sc.mixProducts;
+    for (int b = 0; b < kMaxBins; ++b) { h->ps.mixSymCount[b] = sc.mixRows > 0 ? sc.mixSymCount[b] : 0; h->ps.mixNumCount[b] = sc.mixRows > 0 ? hs[S_NUM_COUNT + b] : 0; }
+    take_class_figures(h, cs);
+    memcpy(h->classSpec.cs, cs, sizeof(h->classSpec.cs));          // (valid once nnzC is known, below)
+    if (h->verbose > 1) printf("  [row classes: %d classes, <= %d products and <= %d entries per row; slabs of <= %d values]\n", cs[CS_CLASSES], cs[CS_MAXP], cs[CS_MAXNNZ], cs[CS_MAXSLAB]);
+    return BHS_SUCCESS;
+}
+
+// Stages 1 to 3 once: the symbolic stage (class path, mixed mode or general pipeline), the scan, the speculative openings
+// of the numeric half, the read-back with the class path's verdict, the normal opening.  kRestart: once more (restart:
+// the timers and kernel statistics of the abandoned attempt stay in -- it ran inside this multiply).
+int symbolic_attempt(bhs_handle* h, bool restart)
 {
     h->ls = h->stream;
     const int m = h->m;
@@ -543,119 +797,22 @@ int pipeline_symbolic(bhs_handle* h, bool restart = false)
     const int nScanBlocks = (int)(((long long)m + 1 + kScanTile - 1) / kScanTile);
     BHS_TRY(ensure(h, h->blockSum, sizeof(long long) * (size_t)nScanBlocks, true));
 
-    EventPair* ep;
+    // ------------------------------------------------------------ stages 1 and 2: symbolic
     SymChoices sc;
-    // Row classes first, for data sets whose rows are short on both sides (the hint from bhs_set_data time is
-    // verified on the device row by row)
-    // ... and long enough for the classification passes to pay (round 3's kernels, same box): poisson27pt (729 products
-    // per row) 4.85 -> 2.1 ms on the class kernels, poisson9pt 1024^2 (81) 0.57 -> 0.47 ms, poisson7pt 128^3 (49) 0.73 ->
-    // 0.78 ms, poisson5pt 1024^2 (25) 0.23 -> 0.42 ms: from class_min_products = 64 products per row on
-    const bool useClass = h->classPath && h->classState >= 0 && h->forcePath == 0 && h->maxTableLog2 >= 15 &&
-                          cls_row_a(h) <= kClassMaxRowBig && cls_row_b(h) <= kClassMaxRowBig &&
-                          (h->classPath == 2 || (h->avgRowA * h->avgRowB >= (double)h->classMinProducts &&
-                                                 // ... and enough of them: every block of the classifier meets every class once.
-                                                 // (Round 6, class kernels against general pipeline: 16 x 16 entries a row, 25 k
-                                                 // rows -- 5.8 M products -- 0.182 / 0.179 ms, 50 k rows 0.192 / 0.266, 100 k rows
-                                                 // 0.209 / 0.435; 27 x 8 entries, 50 k rows 0.192 / 0.240; poisson27pt 40^3, 43 M
-                                                 // products, 0.219 / 0.249; poisson9pt 512^2, 21 M, 0.192 / 0.194.  Round 3's
-                                                 // kernels had put the line at 6e7.)
-                                                 (double)h->m * h->avgRowA * h->avgRowB >= 1e7));
+    const bool useClass = h->classState >= 0 && class_path_first(h, 1e7);
     // Mixed mode (bhs_class_mix.hip.h): this data set's last multiply met rows without a class -- they go through the general
-    // pipeline's kernels, everything else stays on the class kernels.  mixRows: how many this multiply found.
+    // pipeline's kernels, everything else stays on the class kernels.  sc.mixRows: how many this multiply found.
     const bool mixedFlow = useClass && h->mixOn && h->classMixed;
-    int mixRows = 0;
-    int mixSymCount[kMaxBins], mixSymStart[kMaxBins + 1];
-    unsigned long long mixProducts = 0;
     if (useClass) {
         const int hubMin = mixedFlow ? hub_min_products(h) : 0;
-        BinSpec symSpec = make_spec(kSymCfg, kNumSymBins, h->maxTableLog2, h->symLoadPct, true, 0, hubMin);
+        const BinSpec symSpec = make_spec(kSymCfg, kNumSymBins, h->maxTableLog2, h->symLoadPct, true, 0, hubMin);
         BHS_TRY(symbolic_class(h, mixedFlow, symSpec));
         sc.noUpperBound = true;                 // (no ub[] either: the numeric bins are never built)
         sc.numSpec = make_spec(kNumCfg, kNumNumBins, std::min(h->maxTableLog2, 13), h->numLoadPct, true, 0, hubMin);
-        if (mixedFlow) {
-            // what the classes look like and how many rows have none: the first of the mixed flow's two read-backs
-            BHS_HIP(hipMemcpyAsync(hs, small, sizeof(int) * S_SMALL_INTS, hipMemcpyDeviceToHost, h->stream));
-            BHS_TRY(wait_stream(h));
-            const int* cs = hs + S_CT_SLOTS;
-            mixRows = hs[S_MIX_COUNT];
-            memcpy(&mixProducts, hs + S_TOTAL_CT, 8);
-            auto to_general = [&](const char* why) {
-                h->classState = -1;
-                if (h->verbose > 1) printf("  [row classes, mixed: %s (%d of %d rows without a class, %d classes, %d rows start a stretch): general pipeline]\n", why, mixRows, m, cs[CS_CLASSES], cs[CS_HEADS]);
-                return pipeline_symbolic(h, true);
-            };
-            if (hs[S_ERR]) return BHS_ERR_INTERNAL;
-            if (cs[CS_CLASSES] == 0) return to_general("no class");
-            if (mixRows > 0) {
-                if ((long long)mixRows * 100 > (long long)h->mixMaxPct * m) return to_general("too many rows without a class");
-                h->ps.classMaxNnz = cs[CS_MAXNNZ];
-                h->ps.classMaxNA = cs[CS_MAXNA];
-                h->ps.classMaxRing2 = std::max(cs[CS_RINGFULL], cs[CS_RINGONE]);
-                // (the kernels that pass an irregular row by: the ring kernel, and k_class_numeric_big for block-structured grids)
-                if (!cs[CS_BIGCOUNT] && (h->classNumeric < 2 || !class_ring2_fits(h))) return to_general("classes beyond the ring kernel");
-            }
-            // (an irregular row is a head, and so is the row behind it: they are not what the verdict below is about)
-            if (h->classHeadsOn && h->classPath != 2 && !cs[CS_BIGCOUNT] && ((long long)cs[CS_HEADS] - 2LL * mixRows) * 4 > (long long)m)
-                return to_general("rows classify each for itself");
-            if (mixRows == 0) { h->classMixed = 0; h->mixProbed = true; }   // (every row has a class worth its pattern: the clean flow from the next multiply on)
-            if (h->verbose > 1) printf("  [row classes, mixed: %d of %d rows without a class -> the general pipeline's kernels; %d classes]\n", mixRows, m, cs[CS_CLASSES]);
-        }
-        if (mixRows > 0) {
-            // their symbolic pass, bin by bin: exact counts into Cp[row] (the general pipeline's stage 2 on the listed rows)
-            // a handful of rows (fewer than one in sixteen): the ladder with fewer steps -- a launch costs more than a table
-            // that is too large for a few hundred rows
-            const bool coarse = (long long)mixRows * 16 <= (long long)m && h->maxTableLog2 >= 15;
-            if (coarse) {
-                symSpec = coarse_spec(symSpec, kCoarseSym);
-                sc.numSpec = coarse_spec(sc.numSpec, kCoarseNum);
-            }
-            mixSymStart[0] = 0;
-            for (int b = 0; b < kMaxBins; ++b) {
-                mixSymCount[b] = hs[(coarse ? S_MIX_SYM2 : S_SYM_COUNT) + b];
-                mixSymStart[b + 1] = mixSymStart[b] + (b == 0 ? 0 : mixSymCount[b]);
-            }
-            h->nnzCt = (long long)mixProducts;                    // (launch_hub sizes its item list by it)
-            h->cmpActive = false;
-            const long long gridF = std::max<long long>(1, std::min<long long>(((long long)mixRows + 255) / 256, (long long)h->numCU * 8));
-            BHS_TRY(timed_begin(h, "fill_queues", &ep));
-            hipLaunchKernelGGL(k_mix_fill<false>, dim3((unsigned)gridF), dim3(256), 0, h->stream, (const int*)h->mixList.p, (const int*)(small + S_MIX_COUNT),
-                               0, 0x7fffffff, (const int*)h->ub.p, h->dAp, (const int*)h->ub.p, (const int*)(small + (coarse ? S_MIX_SYM2 : S_SYM_COUNT)), small + S_SYM_CURSOR,
-                               (int4*)h->queue.p, symSpec, (unsigned long long*)(small + S_SYM_SUMS));
-            BHS_HIP(hipGetLastError());
-            BHS_TRY(timed_end(h, ep));
-            h->stats[ep->stat].launches++;
-            const int4* symQueue = (const int4*)h->queue.p;
-            BHS_TRY(fork_bins(h, mixSymCount, kNumSymBins, h->mixFork != 0));
-            if (mixSymCount[kHubBin]) {
-                bin_stream(h, kHubBin);
-                BHS_TRY(timed_begin(h, "symbolic_hub_rows", &ep));
-                int rc = launch_hub<false>(h, symQueue + mixSymStart[kHubBin], mixSymCount[kHubBin], (int*)h->Cp.p);
-                if (rc) { h->ls = h->stream; return rc; }
-                BHS_TRY(timed_end(h, ep));
-                h->stats[ep->stat].launches++;
-                h->stats[ep->stat].rows += mixSymCount[kHubBin];
-                h->ps.symStat[kHubBin] = ep->stat;
-            }
-            for (int i = 1; i < kNumSymBins; ++i) {
-                const int b = kNumSymBins - i;
-                if (!mixSymCount[b]) continue;
-                bin_stream(h, b);
-                BHS_TRY(timed_begin(h, kSymNames[b], &ep));
-                int rc = dispatch_bin<false>(h, kSymCfg[b], symQueue + mixSymStart[b], mixSymCount[b], (int*)h->Cp.p);
-                if (rc) { h->ls = h->stream; return rc; }
-                BHS_TRY(timed_end(h, ep));
-                h->stats[ep->stat].launches++;
-                h->stats[ep->stat].rows += mixSymCount[b];
-                h->ps.symStat[b] = ep->stat;
-            }
-            BHS_TRY(join_bins(h));
-        }
+        if (mixedFlow) BHS_TRY(symbolic_mixed(h, symSpec, sc));
     } else {
         BHS_TRY(symbolic_general(h, sc));
     }
-    const bool noUpperBound = sc.noUpperBound, symDirect = sc.symDirect;
-    const int laneK = sc.laneK;
-    const BinSpec& numSpec = sc.numSpec;
 
     // ------------------------------------------------------------ stage 3: scan, allocate C, numeric queues
     // Round 6, a lane-first multiply whose numeric kernel may go out on the last multiply's nnz(C) (laneSpec): no scan kernel and
@@ -663,93 +820,11 @@ int pipeline_symbolic(bhs_handle* h, bool restart = false)
     // nnz(C) C was sized for (all of them the same verdict; nothing is written otherwise) and make rowPtrC on the way.  Not for
     // callers that want rowPtrC on the host while the numeric kernel runs.
     h->ps.laneFirst = !useClass && sc.laneFirst;
-    if (!useClass && !restart && sc.laneFirst && sc.blockSums && !h->wantHostRowPtr && h->specNumeric && h->laneSpec.valid &&
-        h->laneSpec.laneK == sc.laneK && !h->lazyOut && h->directBins && (h->laneNumeric == 1 || (h->laneNumeric == 2 && sc.laneK <= 8))) {
-        const long long need = std::max<long long>(h->laneSpec.nnzC, 1);
-        const bool room = h->extCj ? h->laneSpec.nnzC <= h->extCap
-                                   : (h->Cj.p && h->Cx.p && h->Cj.cap >= (size_t)need * sizeof(int) && h->Cx.cap >= (size_t)need * sizeof(value_t));
-        if (room) {
-            h->ps.specLaunched = true;
-            h->ps.specLane = true;
-            h->ps.fromCounts = true;
-            h->specLaunches++;
-            h->nnzC = h->laneSpec.nnzC;
-            h->nnzCt = h->laneSpec.nnzCt;                  // (pipeline_finish puts this multiply's own count here)
-            h->ps.noUpperBound = sc.noUpperBound;
-            h->ps.symDirect = sc.symDirect;
-            h->ps.laneK = sc.laneK;
-            h->ps.numSpec = sc.numSpec;
-            BHS_HIP(hipEventRecord(h->ev[3], h->stream));
-            return stage_rowptr_and_open(h);
-        }
+    if (h->ps.laneFirst && !restart && sc.blockSums && !h->wantHostRowPtr && lane_spec_try(h, sc)) {
+        h->ps.fromCounts = true;
+        return open_speculative(h, sc, true, h->laneSpec.nnzC, h->laneSpec.nnzCt);
     }
-    BHS_TRY(timed_begin(h, "scan_rowptr", &ep));
-    if (useClass) {
-        // one pass: every row's count from its class, scanned with look-back over the tiles before (k_class_scan)
-        const int nTiles = (m + kClassScanTile - 1) / kClassScanTile;
-        // (blockSum holds the tile words, cleared by k_class_reset)
-        hipLaunchKernelGGL(k_class_scan, dim3((unsigned)nTiles), dim3(kClassScanBlock), 0, h->stream, m, (const int*)h->classC.p,
-                           (const int4*)h->classInfo.p, (int*)h->Cp.p, (unsigned long long*)h->blockSum.p,
-                           (long long*)(small + S_TOTAL_C), small + S_CT_SLOTS, mixRows > 0, h->dAp, (const int*)h->ub.p, sc.numSpec, small + S_NUM_COUNT);
-        BHS_HIP(hipGetLastError());
-        BHS_TRY(timed_end(h, ep));
-        h->stats[ep->stat].launches += 1;
-        if (mixRows > 0) {
-            // the irregular rows' numeric bins and queue (rowPtrC is final), on the device while the host waits for nnz(C)
-            const BinSpec& ns = sc.numSpec;
-            const long long gridF = std::max<long long>(1, std::min<long long>(((long long)mixRows + 255) / 256, (long long)h->numCU * 8));
-            BHS_TRY(timed_begin(h, "fill_queues", &ep));
-            hipLaunchKernelGGL(k_mix_fill<true>, dim3((unsigned)gridF), dim3(256), 0, h->stream, (const int*)h->mixList.p, (const int*)(small + S_MIX_COUNT),
-                               0, 0x7fffffff, (const int*)h->Cp.p, h->dAp, (const int*)h->ub.p, (const int*)(small + S_NUM_COUNT), small + S_NUM_CURSOR,
-                               (int4*)h->queue.p, ns, (unsigned long long*)(small + S_NUM_SUMS));
-            BHS_HIP(hipGetLastError());
-            BHS_TRY(timed_end(h, ep));
-            h->stats[ep->stat].launches++;
-        }
-    } else {
-    if (h->scanOnePass) {
-        // one pass with look-back over the tiles before (k_scan_onepass); the tile words carry this multiply's epoch
-        const int nTiles = (m + kScan1Tile - 1) / kScan1Tile;
-        h->scanEpoch = (h->scanEpoch + 1) & 0x3FFFFu;
-        if (h->scanEpoch == 0) {                                    // (every 2^18 multiplies the words of 2^18 multiplies ago could match)
-            BHS_HIP(hipMemsetAsync(h->blockSum.p, 0, sizeof(unsigned long long) * (size_t)std::max(nTiles, 1), h->stream));
-            h->scanEpoch = 1;
-        }
-        hipLaunchKernelGGL(k_scan_onepass, dim3((unsigned)nTiles), dim3(kScan1Block), 0, h->stream, m, (int*)h->Cp.p, h->dAp,
-                           (unsigned long long*)h->blockSum.p, h->scanEpoch, small + S_SCAN_TICKET, (long long*)(small + S_TOTAL_C),
-                           small + S_NUM_COUNT, numSpec, small + S_MAXCNT, (const int*)h->ub.p);
-        BHS_HIP(hipGetLastError());
-        BHS_TRY(timed_end(h, ep));
-        h->stats[ep->stat].launches += 1;
-    } else {
-    hipLaunchKernelGGL(k_scan_reduce, dim3(nScanBlocks), dim3(256), 0, h->stream, m, (const int*)h->Cp.p, h->dAp,
-                       (long long*)h->blockSum.p, small + S_NUM_COUNT, numSpec, small + S_MAXCNT, (const int*)h->ub.p);
-    hipLaunchKernelGGL(k_scan_blocksums, dim3(1), dim3(1024), 0, h->stream, nScanBlocks,
-                       (long long*)h->blockSum.p, (long long*)(small + S_TOTAL_C));
-    hipLaunchKernelGGL(k_scan_apply, dim3(nScanBlocks), dim3(256), 0, h->stream, m, (int*)h->Cp.p,
-                       (const long long*)h->blockSum.p);
-    BHS_HIP(hipGetLastError());
-    BHS_TRY(timed_end(h, ep));
-    h->stats[ep->stat].launches += 3;
-    }
-    }
-    // ... the numeric queues likewise, where the symbolic stage went by queues (then the numeric stage will): k_scan_onepass
-    // has left the numeric bins' counts
-    h->ps.numQueueFilled = false;
-    // (not where this data set's last multiply ran its numeric stage straight from the row pointers: a hint, it costs or saves a launch)
-    if (!useClass && h->earlyFill && h->scanOnePass && !sc.noUpperBound && !sc.symDirect && h->numDirectHint != 1) {
-        hipLaunchKernelGGL(k_bin_starts, dim3(1), dim3(64), 0, h->stream, (const int*)(small + S_NUM_COUNT), small + S_NUM_START);
-        long long grid = std::min<long long>(((long long)m + kFillTile - 1) / kFillTile, (long long)h->numCU * 8);
-        BHS_TRY(timed_begin(h, "fill_queues", &ep));
-        hipLaunchKernelGGL(k_fill_queues<true>, dim3((unsigned)grid), dim3(256), 0, h->stream, m,
-                           (const int*)h->Cp.p, h->dAp, (const int*)h->ub.p, (const int*)(small + S_NUM_START),
-                           small + S_NUM_CURSOR, (int4*)h->queue.p, numSpec,
-                           (unsigned long long*)(small + S_NUM_SUMS));
-        BHS_HIP(hipGetLastError());
-        BHS_TRY(timed_end(h, ep));
-        h->stats[ep->stat].launches++;
-        h->ps.numQueueFilled = true;
-    }
+    BHS_TRY(scan_rowptr(h, useClass, sc));
     // The classes' figures of the data set's last multiply stand in for this one's (bhs_class.hip.h, k_class_spec_check): no
     // round trip to the host between the scan and the numeric kernel.  Only for a whole multiply on the ring kernel whose C
     // fits the arrays at hand; pipeline_finish sees the device's verdict.
@@ -760,99 +835,23 @@ int pipeline_symbolic(bhs_handle* h, bool restart = false)
         hipLaunchKernelGGL(k_class_spec_check, dim3(1), dim3(64), 0, h->stream, key, (const int*)(small + S_CT_SLOTS),
                            (const long long*)(small + S_TOTAL_C), (const int*)(small + S_ERR), small + S_SPEC);
         BHS_HIP(hipGetLastError());
-        h->ps.specLaunched = true;
-        h->specLaunches++;
-        h->nnzC = h->classSpec.nnzC;
-        h->nnzCt = h->classSpec.nnzCt;                 // (pipeline_finish puts this multiply's own count here)
-        h->ps.noUpperBound = noUpperBound;
-        h->ps.symDirect = symDirect;
-        h->ps.laneK = laneK;
-        h->ps.numSpec = numSpec;
-        BHS_HIP(hipEventRecord(h->ev[3], h->stream));
-        return stage_rowptr_and_open(h);
+        return open_speculative(h, sc, false, h->classSpec.nnzC, h->classSpec.nnzCt);
     }
     // ... and a lane-first multiply likewise (round 6): the last multiply's nnz(C) and "every row in the lane bin" stand in,
     // k_lane_spec_check compares on the device, pipeline_finish sees the verdict
-    h->ps.laneFirst = !useClass && sc.laneFirst;
-    if (!useClass && !restart && sc.laneFirst && h->specNumeric && h->laneSpec.valid && h->laneSpec.laneK == sc.laneK && !h->lazyOut &&
-        h->directBins && h->scanOnePass && (h->laneNumeric == 1 || (h->laneNumeric == 2 && sc.laneK <= 8))) {
-        const long long need = std::max<long long>(h->laneSpec.nnzC, 1);
-        const bool room = h->extCj ? h->laneSpec.nnzC <= h->extCap
-                                   : (h->Cj.p && h->Cx.p && h->Cj.cap >= (size_t)need * sizeof(int) && h->Cx.cap >= (size_t)need * sizeof(value_t));
-        if (room) {
-            hipLaunchKernelGGL(k_lane_spec_check, dim3(1), dim3(64), 0, h->stream, h->laneSpec.nnzC, m, (const long long*)(small + S_TOTAL_C),
-                               (const int*)(small + S_ERR), (const int*)(small + S_NUM_COUNT), small + S_SPEC);
-            BHS_HIP(hipGetLastError());
-            h->ps.specLaunched = true;
-            h->ps.specLane = true;
-            h->specLaunches++;
-            h->nnzC = h->laneSpec.nnzC;
-            h->nnzCt = h->laneSpec.nnzCt;                  // (pipeline_finish puts this multiply's own count here)
-            h->ps.noUpperBound = noUpperBound;
-            h->ps.symDirect = symDirect;
-            h->ps.laneK = laneK;
-            h->ps.numSpec = numSpec;
-            BHS_HIP(hipEventRecord(h->ev[3], h->stream));
-            return stage_rowptr_and_open(h);
-        }
+    if (h->ps.laneFirst && !restart && h->scanOnePass && lane_spec_try(h, sc)) {
+        hipLaunchKernelGGL(k_lane_spec_check, dim3(1), dim3(64), 0, h->stream, h->laneSpec.nnzC, m, (const long long*)(small + S_TOTAL_C),
+                           (const int*)(small + S_ERR), (const int*)(small + S_NUM_COUNT), small + S_SPEC);
+        BHS_HIP(hipGetLastError());
+        return open_speculative(h, sc, true, h->laneSpec.nnzC, h->laneSpec.nnzCt);
     }
+
+    // ------------------------------------------------------------ the read-back
     BHS_HIP(hipMemcpyAsync(hs, small, sizeof(int) * S_SMALL_INTS, hipMemcpyDeviceToHost, h->stream));
     BHS_TRY(wait_stream(h));
     if (useClass) {
-        const int* cs = hs + S_CT_SLOTS;
-        // (... or a great many classes: single rows that found room in the table, each with a pattern of its own to work out --
-        // the mixed flow counts the rows of every class and leaves the classes of a few rows out; asked once per data set)
-        bool manyClasses = false;
-        if (!mixedFlow && !cs[CS_FLAGS] && cs[CS_CLASSES] > kClassManyClasses && !h->mixProbed && !cs[CS_BIGCOUNT] && h->classNumeric >= 2) {
-            h->ps.classMaxNnz = cs[CS_MAXNNZ];                    // (only where the mixed flow's ring kernel can take the classes)
-            h->ps.classMaxNA = cs[CS_MAXNA];
-            h->ps.classMaxRing2 = std::max(cs[CS_RINGFULL], cs[CS_RINGONE]);
-            manyClasses = class_ring2_fits(h);
-        }
-        if (!mixedFlow && (cs[CS_FLAGS] || manyClasses) && cs[CS_CLASSES] > 0 && h->mixOn) {
-            // a row without a class, or a class beyond the tables: the same multiply once more, with those rows on the general
-            // pipeline's kernels (mixed mode, bhs_class_mix.hip.h) -- and this data set's next multiplies that way from the start
-            h->classMixed = 1;
-            if (h->verbose > 1) printf("  [row classes: flags %d, %d classes: the multiply again in mixed mode]\n", cs[CS_FLAGS], cs[CS_CLASSES]);
-            return pipeline_symbolic(h, true);
-        }
-        if (!mixedFlow && (cs[CS_FLAGS] || cs[CS_CLASSES] == 0)) {
-            // ... with mixed mode off, or no class at all: this data set is for the general pipeline
-            h->classState = -1;
-            if (h->verbose > 1) printf("  [row classes: flags %d, %d classes: general pipeline]\n", cs[CS_FLAGS], cs[CS_CLASSES]);
-            return pipeline_symbolic(h, true);
-        }
-        // The class kernels take rows in stretches -- consecutive rows of one class; a matrix whose rows classify but
-        // each for itself (block-diagonal with dense blocks: every row of a block has its own relative pattern) makes
-        // them change class every row: 3.4 ms against 1.9 ms on the general pipeline for 2^20 rows in blocks of 4..32.
-        // More than a quarter of the rows through the table: this data set goes to the general pipeline (class_path = 2
-        // insists on the classes).
-        if (!mixedFlow && h->classHeadsOn && h->classPath != 2 && !cs[CS_BIGCOUNT] && (long long)cs[CS_HEADS] * 4 > (long long)m) {
-            h->classState = -1;
-            if (h->verbose > 1) printf("  [row classes: %d of %d rows start a stretch: general pipeline]\n", cs[CS_HEADS], m);
-            return pipeline_symbolic(h, true);
-        }
-        unsigned long long t = 0, v;
-        for (int i = 0; i < kClassSumSlots; ++i) { memcpy(&v, cs + CS_SUMS + 2 * i, 8); t += v; }
-        h->nnzCt = (long long)t + (long long)mixProducts;         // (the rows with a class, the rows without)
-        h->ps.useClass = true;
-        h->ps.mixed = mixRows > 0;
-        h->ps.mixRows = mixRows;
-        h->ps.mixNumFilled = mixRows > 0;
-        h->ps.mixProducts = (long long)mixProducts;
-        for (int b = 0; b < kMaxBins; ++b) { h->ps.mixSymCount[b] = mixRows > 0 ? mixSymCount[b] : 0; h->ps.mixNumCount[b] = mixRows > 0 ? hs[S_NUM_COUNT + b] : 0; }
-        h->ps.classMaxP = cs[CS_MAXP];
-        h->ps.classMaxNnz = cs[CS_MAXNNZ];
-        h->ps.classMaxNA = cs[CS_MAXNA];
-        h->ps.classMaxLB = cs[CS_MAXLB];
-        h->ps.classMaxRing = cs[CS_MAXRING];
-        h->ps.classMaxRing2 = std::max(cs[CS_RINGFULL], cs[CS_RINGONE]);
-        h->ps.classMaxSlab = cs[CS_MAXSLAB];
-        h->ps.classBig = cs[CS_BIGCOUNT];
-        h->ps.classBigMaxP = cs[CS_BIGMAXP];
-        memcpy(h->classSpec.cs, cs, sizeof(h->classSpec.cs));          // (valid once nnzC is known, below)
-        if (h->verbose > 1) printf("  [row classes: %d classes, <= %d products and <= %d entries per row; slabs of <= %d values]\n", cs[CS_CLASSES], cs[CS_MAXP], cs[CS_MAXNNZ], cs[CS_MAXSLAB]);
-    } else if (noUpperBound) {                           // product count: the symbolic kernel's 64 partial sums
+        BHS_TRY(class_verdict(h, mixedFlow, sc));
+    } else if (sc.noUpperBound) {                        // product count: the symbolic kernel's 64 partial sums
         unsigned long long t = 0, v;
         for (int i = 0; i < 64; ++i) { memcpy(&v, hs + S_CT_SLOTS + 2 * i, 8); t += v; }
         h->nnzCt = (long long)t;
@@ -866,20 +865,18 @@ int pipeline_symbolic(bhs_handle* h, bool restart = false)
         if (h->ps.spanWPL > 0 && h->spanState >= 0) {             // (a row beyond the span bitmap: the hash kernels from here on)
             h->spanState = -1;
             if (h->verbose > 1) printf("  [a row's column span is beyond the bitmap: hash kernels]\n");
-            return pipeline_symbolic(h, true);
+            return kRestart;
         }
-        if (!noUpperBound || h->specFailed) return BHS_ERR_INTERNAL;
+        if (!sc.noUpperBound || h->specFailed) return BHS_ERR_INTERNAL;
         h->specFailed = true;
         if (h->verbose > 1) printf("  [speculative direct launch refuted on the device: general pipeline]\n");
-        return pipeline_symbolic(h, true);
+        return kRestart;
     }
     if (hs[S_ERR]) return BHS_ERR_INTERNAL;
     if (nnzC > 0x7fffffffLL) return BHS_ERR_NNZ_OVERFLOW;
+
+    // ------------------------------------------------------------ the normal opening
     h->nnzC = nnzC;
-    h->ps.noUpperBound = noUpperBound;
-    h->ps.symDirect = symDirect;
-    h->ps.laneK = laneK;
-    h->ps.numSpec = numSpec;
     h->ps.maxCnt = hs[S_MAXCNT];
     h->ps.hubRows = sc.hubRows;
     for (int b = 0; b < kMaxBins; ++b) h->ps.fullCount[b] = hs[S_NUM_COUNT + b];
@@ -891,28 +888,15 @@ int pipeline_symbolic(bhs_handle* h, bool restart = false)
         BHS_TRY(ensure(h, h->Cx, sizeof(value_t) * (size_t)std::max<long long>(nnzC, 1)));
     }
     if (useClass) { h->classSpec.nnzC = nnzC; h->classSpec.nnzCt = h->nnzCt; h->classSpec.valid = !mixedFlow; }
-    BHS_HIP(hipEventRecord(h->ev[3], h->stream));
-    return stage_rowptr_and_open(h);
+    return open_numeric(h, sc);
 }
 
-// the end of pipeline_symbolic: rowPtrC on its way to the host where the caller wants it there, the multiply open
-int stage_rowptr_and_open(bhs_handle* h)
+// restart: the same multiply starting over on another path (a refuted speculation): as an attempt's kRestart
+int pipeline_symbolic(bhs_handle* h, bool restart = false)
 {
-    const int m = h->m;
-    h->rowPtrStaged = false;
-    if (h->wantHostRowPtr) {
-        // rowPtrC is final after the scan: ship it to pinned host memory on a second stream while the
-        // numeric kernels run (the reference does this D2H inside its timed region too, bhsparse_cuda.h:2787)
-        const size_t bytes = sizeof(int) * ((size_t)m + 1);
-        BHS_TRY(ensure_host_rowptr(h, bytes));
-        BHS_HIP(hipEventRecord(h->evScanDone, h->stream));
-        BHS_HIP(hipStreamWaitEvent(h->copyStream, h->evScanDone, 0));
-        BHS_HIP(hipMemcpyAsync(h->hostRowPtr, h->Cp.p, bytes, hipMemcpyDeviceToHost, h->copyStream));
-        BHS_HIP(hipEventRecord(h->evCopyDone, h->copyStream));
-        h->rowPtrStaged = true;
-    }
-    h->ps.open = true;
-    return BHS_SUCCESS;
+    int rc;
+    while ((rc = symbolic_attempt(h, restart)) == kRestart) restart = true;
+    return rc;
 }
 
 // Stage 4 on the rows [r0, r1) of A / C.  A row range is the same multiply seen through shifted row pointers (the
@@ -927,30 +911,22 @@ int numeric_stage(bhs_handle* h, int r0, int r1)
     const bool full = r0 == 0 && r1 == h->m;
     int* small = (int*)h->small.p;
     int* hs = h->hostSmall;
-    EventPair* ep;
     const BinSpec& numSpec = h->ps.numSpec;
     const int laneK = h->ps.laneK;
-    int (&numStat)[kMaxBins] = h->ps.numStat;
     h->ls = h->stream;
     if (h->ps.specLane) {
         // (a whole multiply: bhs_spgemm_symbolic's lazyOut keeps the two-halves API off this path)
         h->ps.rangesRun++;
-        BHS_TRY(timed_begin(h, "numeric_lane", &ep));
-        if (h->ps.fromCounts) {
+        BHS_TRY(timed(h, "numeric_lane", h->m, [&] {
+            if (!h->ps.fromCounts)
+                return one_launch(launch_row_lane<true>(h, laneK, nullptr, h->m, (int*)h->Cp.p, nullptr, nullptr, (const int*)h->small.p + S_SPEC));
             const int nb = (int)(((long long)h->m + 255) / 256);
             hipLaunchKernelGGL(k_lane_block_prefix, dim3(1), dim3(1024), 0, h->ls, nb, (const int*)h->laneBlockSums.p,
                                reinterpret_cast<long long*>((int*)h->laneBlockSums.p + kLaneFromCountsBlocks));
             BHS_HIP(hipGetLastError());
-        }
-        if (h->ps.fromCounts)
-            BHS_TRY(launch_row_lane<true>(h, laneK, nullptr, h->m, (int*)h->Cp.p, nullptr, nullptr, nullptr, (int*)h->laneBlockSums.p, h->laneSpec.nnzC,
-                                          (int*)h->small.p + S_SPEC));
-        else
-        BHS_TRY(launch_row_lane<true>(h, laneK, nullptr, h->m, (int*)h->Cp.p, nullptr, nullptr, (const int*)h->small.p + S_SPEC));
-        BHS_TRY(timed_end(h, ep));
-        h->stats[ep->stat].launches++;
-        h->stats[ep->stat].rows += h->m;
-        numStat[kLaneBin] = ep->stat;
+            return one_launch(launch_row_lane<true>(h, laneK, nullptr, h->m, (int*)h->Cp.p, nullptr, nullptr, nullptr, (int*)h->laneBlockSums.p,
+                                                    h->laneSpec.nnzC, (int*)h->small.p + S_SPEC));
+        }, &h->ps.numStat[kLaneBin]));
         h->ps.numDirectFull = true;
         return BHS_SUCCESS;
     }
@@ -979,8 +955,7 @@ int numeric_stage(bhs_handle* h, int r0, int r1)
             for (int b = 0; b < kMaxBins; ++b) numCount[b] = hr[b];
             h->ps.mixNumFilled = false;                               // (the queue now holds this range's rows)
         }
-        numStart[0] = 0;
-        for (int b = 0; b < kMaxBins; ++b) numStart[b + 1] = numStart[b] + (b == 0 ? 0 : numCount[b]);
+        bin_starts(numCount, numStart);
         const int4* numQueue = (const int4*)h->queue.p;
         h->ps.midRows = h->ps.longRows = 0;
         for (int b = 2; b < kNumNumBins; ++b)
@@ -997,44 +972,18 @@ int numeric_stage(bhs_handle* h, int r0, int r1)
         // takes k_row_block 0.09 ms) go to ONE side stream and the ring kernel starts beside them at once: its workgroups on
         // the few CUs those hold start late, and with its super-runs handed out by the XCDs' counters (ring_dynamic) nobody
         // waits for them.
-        BHS_TRY(fork_bins(h, numCount, kNumNumBins, anyBin > 0 && h->mixFork != 0));
-        const bool beside = !h->binsForked && anyBin > 0 && h->ps.mixRows <= kMixBesideRows && h->ringDynamic != 0 && !h->ps.classBig;
-        if (beside) {                                            // (their kernels FIRST: what the ring kernel has taken it keeps until it ends)
-            BHS_HIP(hipEventRecord(h->evFork, h->stream));
-            BHS_HIP(hipStreamWaitEvent(h->binStream[0], h->evFork, 0));
-            h->besideStream = h->binStream[0];
-        }
-        if (numCount[kHubBin]) {
-            bin_stream(h, kHubBin);
-            BHS_TRY(timed_begin(h, "numeric_hub_rows", &ep));
-            BHS_TRY(launch_hub<true>(h, numQueue + numStart[kHubBin], numCount[kHubBin], (int*)h->Cp.p));
-            BHS_TRY(timed_end(h, ep));
-            h->stats[ep->stat].launches++;
-            h->stats[ep->stat].rows += numCount[kHubBin];
-            numStat[kHubBin] = ep->stat;
-        }
-        for (int i = 1; i < kNumNumBins; ++i) {
-            const int b = kNumNumBins - i;
-            if (!numCount[b]) continue;
-            bin_stream(h, b);
-            BHS_TRY(timed_begin(h, kNumNames[b], &ep));
-            BHS_TRY(dispatch_bin<true>(h, kNumCfg[b], numQueue + numStart[b], numCount[b], (int*)h->Cp.p, 0));
-            BHS_TRY(timed_end(h, ep));
-            h->stats[ep->stat].launches++;
-            h->stats[ep->stat].rows += numCount[b];
-            numStat[b] = ep->stat;
-        }
-        BHS_TRY(join_bins(h));
+        // (beside: their kernels FIRST -- what the ring kernel has taken it keeps until it ends)
+        BHS_TRY(run_bins<true>(h, numCount, numStart, numQueue, false, laneK, anyBin > 0 && h->mixFork != 0,
+                               anyBin > 0 && h->ps.mixRows <= kMixBesideRows && h->ringDynamic != 0 && !h->ps.classBig));
+        const bool beside = h->besideStream != nullptr;
         h->besideStream = nullptr;
         h->ps.ringBeside = beside;
-        BHS_TRY(timed_begin(h, "numeric_class", &ep));
-        if (h->ps.classBig) BHS_TRY(launch_class_numeric_big(h, r0, r1));
-        else BHS_TRY(launch_class_ring(h, r0, r1));
-        BHS_TRY(timed_end(h, ep));
+        int stat = 0;
+        BHS_TRY(timed(h, "numeric_class", r1 - r0, [&] {
+            return one_launch(h->ps.classBig ? launch_class_numeric_big(h, r0, r1) : launch_class_ring(h, r0, r1));
+        }, &stat));
         h->ps.ringBeside = false;
-        h->stats[ep->stat].launches++;
-        h->stats[ep->stat].rows += r1 - r0;
-        if (full) { h->stats[ep->stat].products += h->nnzCt - h->ps.mixProducts; h->stats[ep->stat].nnzA_rows += h->nnzA; }
+        if (full) { h->stats[stat].products += h->nnzCt - h->ps.mixProducts; h->stats[stat].nnzA_rows += h->nnzA; }
         if (beside) {
             BHS_HIP(hipEventRecord(h->evJoin[0], h->binStream[0]));
             BHS_HIP(hipStreamWaitEvent(h->stream, h->evJoin[0], 0));
@@ -1043,14 +992,13 @@ int numeric_stage(bhs_handle* h, int r0, int r1)
     }
     if (h->ps.useClass) {
         h->ps.rangesRun++;
-        BHS_TRY(timed_begin(h, "numeric_class", &ep));
-        if (h->ps.classBig) BHS_TRY(launch_class_numeric_big(h, r0, r1));
-        else if (h->classNumeric >= 2 && class_ring2_fits(h)) BHS_TRY(launch_class_ring(h, r0, r1));
-        else BHS_TRY(h->classNumeric && class_ring_fits(h) ? launch_class_numeric(h, r0, r1) : launch_class_numeric_atomic(h, r0, r1));
-        BHS_TRY(timed_end(h, ep));
-        h->stats[ep->stat].launches++;
-        h->stats[ep->stat].rows += r1 - r0;
-        if (full) { h->stats[ep->stat].products += h->nnzCt; h->stats[ep->stat].nnz_out += h->nnzC; h->stats[ep->stat].nnzA_rows += h->nnzA; }
+        int stat = 0;
+        BHS_TRY(timed(h, "numeric_class", r1 - r0, [&] {
+            if (h->ps.classBig) return one_launch(launch_class_numeric_big(h, r0, r1));
+            if (h->classNumeric >= 2 && class_ring2_fits(h)) return one_launch(launch_class_ring(h, r0, r1));
+            return one_launch(h->classNumeric && class_ring_fits(h) ? launch_class_numeric(h, r0, r1) : launch_class_numeric_atomic(h, r0, r1));
+        }, &stat));
+        if (full) { h->stats[stat].products += h->nnzCt; h->stats[stat].nnz_out += h->nnzC; h->stats[stat].nnzA_rows += h->nnzA; }
         return BHS_SUCCESS;
     }
     // ---- the range as a view
@@ -1086,8 +1034,7 @@ int numeric_stage(bhs_handle* h, int r0, int r1)
         for (int b = 0; b < kMaxBins; ++b) numCount[b] = hr[b];
         maxCnt = hr[kMaxBins];
     }
-    numStart[0] = 0;
-    for (int b = 0; b < kMaxBins; ++b) numStart[b + 1] = numStart[b] + (b == 0 ? 0 : numCount[b]);
+    bin_starts(numCount, numStart);
     bool numDirect = h->directBins && (numCount[kLaneBin] == m || numCount[1] == m);
     // "Numeric-first": the longest row of C fits a wave-per-row table that is not oversized for the average row
     // (poisson27pt: longest 125, average 121): every row runs that one kernel straight from rowPtrA / rowPtrC -- no
@@ -1107,14 +1054,13 @@ int numeric_stage(bhs_handle* h, int r0, int r1)
         memcpy(hs + S_SMALL_INTS + kMaxBins, numStart, sizeof(int) * kMaxBins);
         BHS_HIP(hipMemcpyAsync(small + S_NUM_START, hs + S_SMALL_INTS + kMaxBins, sizeof(int) * kMaxBins, hipMemcpyHostToDevice, h->stream));
         long long grid = std::min<long long>(((long long)m + kFillTile - 1) / kFillTile, (long long)h->numCU * 8);
-        BHS_TRY(timed_begin(h, "fill_queues", &ep));
-        hipLaunchKernelGGL(k_fill_queues<true>, dim3((unsigned)grid), dim3(256), 0, h->stream, m,
-                           (const int*)h->Cp.p, h->dAp, (const int*)h->ub.p, (const int*)(small + S_NUM_START),
-                           small + S_NUM_CURSOR, (int4*)h->queue.p, numSpec,
-                           (unsigned long long*)(small + S_NUM_SUMS));
-        BHS_HIP(hipGetLastError());
-        BHS_TRY(timed_end(h, ep));
-        h->stats[ep->stat].launches++;
+        BHS_TRY(timed(h, "fill_queues", 0, [&] {
+            hipLaunchKernelGGL(k_fill_queues<true>, dim3((unsigned)grid), dim3(256), 0, h->stream, m,
+                               (const int*)h->Cp.p, h->dAp, (const int*)h->ub.p, (const int*)(small + S_NUM_START),
+                               small + S_NUM_CURSOR, (int4*)h->queue.p, numSpec,
+                               (unsigned long long*)(small + S_NUM_SUMS));
+            return 1;
+        }));
     }
     if (full) { h->ps.numDirectFull = numDirect; h->numDirectHint = numDirect ? 1 : 0; }
     // (what the next multiply of this data set may assume: every row through the lane kernels, this nnz(C))
@@ -1127,45 +1073,7 @@ int numeric_stage(bhs_handle* h, int r0, int r1)
         if (bin_takes_lds_bitmap<true>(h, kNumCfg[b])) (kNumCfg[b].win ? h->ps.longRows : h->ps.midRows) += numCount[b];
     for (int b = 2; b < kNumNumBins; ++b)
         if (numCount[b] && numQueue && bin_takes_wave_window<true>(h, kNumCfg[b])) BHS_TRY(ensure_b_windows(h));
-    BHS_TRY(fork_bins(h, numCount, kNumNumBins));
-    if (numCount[kHubBin]) {
-        bin_stream(h, kHubBin);
-        BHS_TRY(timed_begin(h, "numeric_hub_rows", &ep));
-        BHS_TRY(launch_hub<true>(h, numQueue + numStart[kHubBin], numCount[kHubBin], (int*)h->Cp.p));
-        BHS_TRY(timed_end(h, ep));
-        h->stats[ep->stat].launches++;
-        h->stats[ep->stat].rows += numCount[kHubBin];
-        numStat[kHubBin] = ep->stat;
-    }
-    if (numCount[kLaneBin]) {
-        bin_stream(h, kLaneBin);
-        BHS_TRY(timed_begin(h, "numeric_lane", &ep));
-        BHS_TRY(launch_row_lane<true>(h, laneK, numQueue ? numQueue + numStart[kLaneBin] : nullptr, numCount[kLaneBin], (int*)h->Cp.p));
-        BHS_TRY(timed_end(h, ep));
-        h->stats[ep->stat].launches++;
-        h->stats[ep->stat].rows += numCount[kLaneBin];
-        numStat[kLaneBin] = ep->stat;
-    }
-    for (int i = 1; i < kNumNumBins; ++i) {
-        const int b = kNumNumBins - i;
-        if (!numCount[b]) continue;
-        // Neighbouring bins that all run the LDS-bitmap kernel (one workgroup per CU: two such kernels side by side
-        // only take CUs from each other, and the shorter bins' launch would trail behind) go as ONE queue, taken
-        // from its end so that the longest rows start first.
-        int lo = b, rows = numCount[b];
-        auto kernel_of = [&](int bb) { return !bin_takes_lds_bitmap<true>(h, kNumCfg[bb]) ? 0 : bin_takes_wave_window<true>(h, kNumCfg[bb]) ? (kNumCfg[bb].win ? 3 : 2) : 1; };
-        if (numQueue && h->mergeBitmapBins && kernel_of(b))
-            while (lo - 1 >= 2 && kernel_of(lo - 1) == kernel_of(b)) { --lo; rows += numCount[lo]; }
-        bin_stream(h, b);
-        BHS_TRY(timed_begin(h, kNumNames[b], &ep));
-        BHS_TRY(dispatch_bin<true>(h, kNumCfg[b], numQueue ? numQueue + numStart[lo] : nullptr, rows, (int*)h->Cp.p, lo < b));
-        BHS_TRY(timed_end(h, ep));
-        h->stats[ep->stat].launches++;
-        h->stats[ep->stat].rows += rows;
-        for (int bb = lo; bb <= b; ++bb) { if (numCount[bb]) numStat[bb] = ep->stat; numCount[bb] = 0; }
-    }
-    BHS_TRY(join_bins(h));
-    return BHS_SUCCESS;
+    return run_bins<true>(h, numCount, numStart, numQueue, true, laneK);
 }
 
 // End of a multiply: everything launched has run, errors raised on the device are collected, timers are read.

@@ -197,12 +197,10 @@ int finish_set_data(bhs_handle* h)
     // timed region; this pass only yields the pair count)
     // (round 4: the pair count is also taken for rows of 256 to 1536 products: where B's entries come in long runs -- banded
     // matrices, dense diagonal blocks: a tenth as many pairs as entries -- the compressed pass pays from there on)
-    // A data set that will try the row classes first (pipeline_symbolic's test) and has rows below the old gate leaves the
+    // A data set that will try the row classes first (class_path_first) and has rows below the old gate leaves the
     // count to its first multiply on the general pipeline, if it ever gets there (cmpState 0: that multiply measures the
     // ratio, the ones after it use the verdict) -- poisson27pt's hand-over does not pay a pass over B for nothing.
-    const bool classFirst = h->classPath && h->forcePath == 0 && h->maxTableLog2 >= 15 && cls_row_a(h) <= kClassMaxRowBig &&
-                            cls_row_b(h) <= kClassMaxRowBig &&
-                            (h->classPath == 2 || (avgA * avgB >= (double)h->classMinProducts && (double)h->m * avgA * avgB >= 6e7));
+    const bool classFirst = class_path_first(h, 6e7);
     if (h->compressB == 1 && (avgA * avgB < 256.0 || !h->bSorted)) h->cmpState = -1;
     else if (h->compressB == 1 && classFirst && avgA * avgB <= 1536.0) h->cmpState = 0;
     else if (h->compressB == 1 && h->nnzB > 0 && h->k > 0) {

@@ -474,6 +474,26 @@ int timed_end(bhs_handle* h, EventPair* p)
     return BHS_SUCCESS;
 }
 
+// One timed launch of a kernel record: `enqueue` puts the work on h->ls and returns how many kernels it launched, or an
+// error code (< 0); the record books them and `rows`.  *stat (if given): the record's index, for callers that book more.
+template <typename F>
+int timed(bhs_handle* h, const char* name, int64_t rows, F&& enqueue, int* stat = nullptr)
+{
+    EventPair* ep;
+    BHS_TRY(timed_begin(h, name, &ep));
+    const int launches = enqueue();
+    if (launches < 0) return launches;
+    BHS_HIP(hipGetLastError());
+    BHS_TRY(timed_end(h, ep));
+    h->stats[ep->stat].launches += launches;
+    h->stats[ep->stat].rows += rows;
+    if (stat) *stat = ep->stat;
+    return BHS_SUCCESS;
+}
+
+// an `enqueue` of timed() around a launch helper: its error code, or the one kernel it launched
+inline int one_launch(int rc) { return rc != BHS_SUCCESS ? rc : 1; }
+
 #include "bhs_host_launch.inc.h"
 #include "bhs_host_pipeline.inc.h"
 #include "bhs_host_setdata.inc.h"
