@@ -59,6 +59,13 @@ SYMBOLS = {
     "bhs_expand_class_columns_device": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp]),
     "bhs_spgemm_masked_device": (_i, [_vp, _vp, _vp, _i, _vp, C.POINTER(_i64), C.POINTER(C.c_double)]),
     "bhs_spgemm_masked": (_i, [_vp, _vp, _vp, _i, _vp, C.POINTER(_i64), C.POINTER(C.c_double)]),
+    "bhs_csr_add_symbolic_device": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, C.POINTER(_i), C.POINTER(_i)]),
+    "bhs_csr_add_numeric_device": (_i, [_vp, _i, _i, C.c_double, _i, _vp, _vp, _vp, C.c_double, _i, _vp, _vp, _vp, _vp, _vp, _vp,
+                                        C.POINTER(C.c_double)]),
+    "bhs_spgemm_add_device": (_i, [_vp, C.c_double, C.c_double, _i, _vp, _vp, _vp, _vp, C.POINTER(_i64), C.POINTER(_i),
+                                   C.POINTER(C.c_double)]),
+    "bhs_spgemm_add": (_i, [_vp, C.c_double, C.c_double, _i, _vp, _vp, _vp, _vp, C.POINTER(_i64), C.POINTER(_i),
+                            C.POINTER(C.c_double)]),
     "bhs_strerror": (C.c_char_p, [_i]),
     "bhs_version": (C.c_char_p, []),
 }
@@ -69,7 +76,7 @@ _lib = None
 _libs = {}
 
 
-SOURCES = ("bhsparse_hip.hip", "bhs_host_launch.inc.h", "bhs_host_pipeline.inc.h", "bhs_host_setdata.inc.h", "bhs_host_cabi.inc.h", "bhs_kernels.hip.h", "bhs_row_wg.hip.h", "bhs_row_window.hip.h", "bhs_row_wave.hip.h", "bhs_row_quad.hip.h", "bhs_compress.hip.h", "bhs_row_lane.hip.h", "bhs_sort.hip.h", "bhs_hub.hip.h", "bhs_class.hip.h", "bhs_class_mix.hip.h", "bhs_class_wg.hip.h", "bhs_class_ring.hip.h", "bhs_class_fused.hip.h", "bhs_class_tile.hip.h", "bhs_class_big.hip.h", "bhs_wave.hip.h", "bhs_lab.hip.h", "bhs_masked.hip.h", "bhs_host_masked.inc.h")
+SOURCES = ("bhsparse_hip.hip", "bhs_host_launch.inc.h", "bhs_host_pipeline.inc.h", "bhs_host_setdata.inc.h", "bhs_host_cabi.inc.h", "bhs_kernels.hip.h", "bhs_row_wg.hip.h", "bhs_row_window.hip.h", "bhs_row_wave.hip.h", "bhs_row_quad.hip.h", "bhs_compress.hip.h", "bhs_row_lane.hip.h", "bhs_sort.hip.h", "bhs_hub.hip.h", "bhs_class.hip.h", "bhs_class_mix.hip.h", "bhs_class_wg.hip.h", "bhs_class_ring.hip.h", "bhs_class_fused.hip.h", "bhs_class_tile.hip.h", "bhs_class_big.hip.h", "bhs_wave.hip.h", "bhs_lab.hip.h", "bhs_masked.hip.h", "bhs_host_masked.inc.h", "bhs_add.hip.h", "bhs_host_add.inc.h")
 
 
 def source_digest():

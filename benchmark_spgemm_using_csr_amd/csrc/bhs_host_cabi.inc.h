@@ -73,7 +73,10 @@ static int free_data(bhs_handle* h, bool keepOutput)
     if (!keepOutput) {
         release(h->Cj);
         release(h->Cx);
+        release(h->sumCj);
+        release(h->sumCx);
     }
+    h->sumActive = false;
     h->dAp = h->dAj = h->dBp = h->dBj = nullptr;
     h->dAx = h->dBx = nullptr;
     h->hasData = h->hasC = h->ownAB = false;
@@ -112,6 +115,10 @@ int bhs_destroy(bhs_handle* h)
     release(h->spaBits);
     release(h->maskCtl); release(h->maskQueue);
     for (int i = 0; i < 3; ++i) release(h->maskM[i]);
+    release(h->addCtl); release(h->addQueue); release(h->addCnt); release(h->addTiles); release(h->addPos); release(h->sumCp);
+    for (int i = 0; i < 3; ++i) release(h->addD[i]);
+    if (h->addHost) (void)hipHostFree(h->addHost);
+    for (int i = 0; i < 2; ++i) if (h->addEv[i]) (void)hipEventDestroy(h->addEv[i]);
     if (h->maskHost) (void)hipHostFree(h->maskHost);
     for (int i = 0; i < 2; ++i) if (h->maskEv[i]) (void)hipEventDestroy(h->maskEv[i]);
     if (h->hostSmall) (void)hipHostFree(h->hostSmall);
@@ -298,7 +305,7 @@ int bhs_get_nnzC(bhs_handle* h, int* nnzC_out)
 {
     if (!h || !nnzC_out) return BHS_ERR_INVALID_ARG;
     if (!h->hasC) return BHS_ERR_NOT_READY;
-    *nnzC_out = (int)h->nnzC;
+    *nnzC_out = (int)(h->sumActive ? h->sumNnz : h->nnzC);             // (sumActive: the last bhs_spgemm_add's sum, bhs_host_add.inc.h)
     return BHS_SUCCESS;
 }
 
@@ -306,6 +313,16 @@ int bhs_get_C(bhs_handle* h, int* csrColIndC, bhs_value_t* csrValC)
 {
     if (!h) return BHS_ERR_INVALID_ARG;
     if (!h->hasC) return BHS_ERR_NOT_READY;
+    if (h->sumActive) {
+        if (h->sumNnz && (!csrColIndC || !csrValC)) return BHS_ERR_INVALID_ARG;
+        BHS_HIP(hipSetDevice(h->device));
+        if (h->sumNnz) {
+            BHS_HIP(hipMemcpyAsync(csrColIndC, h->sumCj.p, sizeof(int) * (size_t)h->sumNnz, hipMemcpyDeviceToHost, h->stream));
+            BHS_HIP(hipMemcpyAsync(csrValC, h->sumCx.p, sizeof(value_t) * (size_t)h->sumNnz, hipMemcpyDeviceToHost, h->stream));
+        }
+        BHS_HIP(hipStreamSynchronize(h->stream));
+        return BHS_SUCCESS;
+    }
     if (h->nnzC && out_cj(h) != h->resCj) return BHS_ERR_NOT_READY;   // (the result went to arrays that were unbound since: it lives there)
     if (h->nnzC && (!csrColIndC || !csrValC)) return BHS_ERR_INVALID_ARG;
     BHS_HIP(hipSetDevice(h->device));
@@ -322,7 +339,7 @@ int bhs_get_rowptrC(bhs_handle* h, int* csrRowPtrC)
     if (!h || !csrRowPtrC) return BHS_ERR_INVALID_ARG;
     if (!h->hasC && !h->ps.open) return BHS_ERR_NOT_READY;         // (between the halves rowPtrC is already final)
     BHS_HIP(hipSetDevice(h->device));
-    BHS_HIP(hipMemcpyAsync(csrRowPtrC, h->Cp.p, sizeof(int) * ((size_t)h->m + 1), hipMemcpyDeviceToHost, h->stream));
+    BHS_HIP(hipMemcpyAsync(csrRowPtrC, h->sumActive ? h->sumCp.p : h->Cp.p, sizeof(int) * ((size_t)h->m + 1), hipMemcpyDeviceToHost, h->stream));
     BHS_HIP(hipStreamSynchronize(h->stream));
     return BHS_SUCCESS;
 }
@@ -331,6 +348,12 @@ int bhs_get_C_device(bhs_handle* h, const int** d_rowPtrC, const int** d_colIndC
 {
     if (!h) return BHS_ERR_INVALID_ARG;
     if (!h->hasC && !h->ps.open) return BHS_ERR_NOT_READY;        // (between the halves rowPtrC is already final)
+    if (h->sumActive) {
+        if (d_rowPtrC) *d_rowPtrC = (const int*)h->sumCp.p;
+        if (d_colIndC) *d_colIndC = (const int*)h->sumCj.p;
+        if (d_valC) *d_valC = (const bhs_value_t*)h->sumCx.p;
+        return BHS_SUCCESS;
+    }
     if (h->hasC && h->nnzC && out_cj(h) != h->resCj && (d_colIndC || d_valC)) return BHS_ERR_NOT_READY;   // (see bhs_get_C)
     if (d_rowPtrC) *d_rowPtrC = (const int*)h->Cp.p;
     if (d_colIndC) *d_colIndC = (const int*)out_cj(h);
@@ -379,6 +402,7 @@ int bhs_set_option(bhs_handle* h, const char* key, int64_t value)
         return BHS_SUCCESS;
     }
     if (!strcmp(key, "masked_hub_min_products")) { h->maskHubMin = std::max<int64_t>(0, value); return BHS_SUCCESS; }
+    if (!strcmp(key, "add_inplace")) { h->addInplace = value ? 1 : 0; return BHS_SUCCESS; }   // (the add's key likewise)
     h->classSpec.valid = false;                                     // (any other option may change what a multiply decides)
     h->laneSpec.valid = false;
     if (!strcmp(key, "spec_numeric")) { h->specNumeric = value ? 1 : 0; return BHS_SUCCESS; }
@@ -467,6 +491,7 @@ int bhs_get_info(bhs_handle* h, const char* key, int64_t* value_out)
     if (!strcmp(key, "max_row_b")) { *value_out = h->maxRowB; return BHS_SUCCESS; }
     if (!strcmp(key, "local_a")) { *value_out = h->localA; return BHS_SUCCESS; }
     if (!strcmp(key, "line_a")) { *value_out = h->lineA; return BHS_SUCCESS; }
+    if (!strcmp(key, "add_inplace_used")) { *value_out = h->addInplaceUsed; return BHS_SUCCESS; }   // the last bhs_spgemm_add added into valC in place (1) or wrote the sum to arrays of its own (0)
     if (!strcmp(key, "compress_b_used")) { *value_out = h->cmpState > 0 ? 1 : 0; return BHS_SUCCESS; }
     return BHS_ERR_INVALID_ARG;
 }

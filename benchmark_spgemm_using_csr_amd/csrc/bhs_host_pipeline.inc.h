@@ -779,6 +779,7 @@ int symbolic_attempt(bhs_handle* h, bool restart)
     h->nnzC = 0;
     h->nnzCt = 0;
     h->hasC = false;
+    h->sumActive = false;             // (a sum of the last bhs_spgemm_add goes with the product it was made from)
     h->rowPtrStaged = false;          // (an empty product returns early: the previous multiply's staging must not be read)
     h->ps = bhs_handle::PipeState();
 

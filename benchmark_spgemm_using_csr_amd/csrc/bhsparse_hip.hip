@@ -1,5 +1,6 @@
 // bhsparse_hip.hip — libbhsparse_hip.so (see include/bhsparse_hip.h): the handle and its helpers here; the launch helpers,
-// the pipeline, the hand-over of a data set and the C-ABI in bhs_host_{launch,pipeline,setdata,cabi}.inc.h (one translation unit).
+// the pipeline, the hand-over of a data set and the C-ABI in bhs_host_{launch,pipeline,setdata,cabi}.inc.h, the masked multiply
+// and the sparse add in bhs_host_{masked,add}.inc.h (one translation unit).
 //
 // Pipeline of one bhs_spgemm() (replaces bhsparse::spgemm_cuda, bhsparse.h:297-339):
 //   stage 1  k_upper_bound (ub per row, nnzCt, symbolic-bin histogram)          <- compute_nnzCt + statistics()
@@ -41,6 +42,7 @@
 #include "bhs_class_tile.hip.h"
 #include "bhs_class_big.hip.h"
 #include "bhs_masked.hip.h"
+#include "bhs_add.hip.h"
 
 #include <algorithm>
 #include <chrono>
@@ -350,6 +352,20 @@ struct bhs_handle {
     hipEvent_t maskEv[2] = {nullptr, nullptr};
     int maskTableLog2 = 11;              // option "masked_max_table_log2": mask rows beyond 2^v entries take k_masked_long
     long long maskHubMin = 1 << 17;      // option "masked_hub_min_products": rows of this many products go to k_masked_hub
+    // the sparse add (bhs_host_add.inc.h): buffers of its own as well
+    DevBuf addCtl, addQueue, addCnt;     // counters; per-bin queues of rows; the rows' counts, scanned in place
+    DevBuf addTiles, addPos;             // tile words of its scan (epoch addEpoch); where in C every entry of D sits (in-place path)
+    DevBuf addD[3];                      // bhs_spgemm_add: device copies of rowPtrD, colIndD and valD
+    int* addHost = nullptr;              // pinned mirror of addCtl
+    hipEvent_t addEv[2] = {nullptr, nullptr};
+    unsigned addEpoch = 0;
+    int addInplace = 1;                  // option "add_inplace": 0 the sum always goes to the second set of arrays
+    int addInplaceUsed = 0;              // bhs_get_info "add_inplace_used": the last bhs_spgemm_add added into valC in place
+    // C = alpha A·B + beta D where D reaches outside A·B: the sum, served by the getters until the next multiply drops it
+    // (the pipeline's own Cp / Cj / Cx stay where they are)
+    DevBuf sumCp, sumCj, sumCx;
+    bool sumActive = false;
+    long long sumNnz = 0;
 };
 
 namespace {
@@ -502,3 +518,4 @@ inline int one_launch(int rc) { return rc != BHS_SUCCESS ? rc : 1; }
 
 #include "bhs_host_cabi.inc.h"
 #include "bhs_host_masked.inc.h"
+#include "bhs_host_add.inc.h"

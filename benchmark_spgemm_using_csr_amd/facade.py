@@ -59,6 +59,7 @@ class bhsparse(object):
         self.stage_ms = [0.0] * 4
         self.time_ms = 0.0
         self.masked_ms = 0.0
+        self.add_ms = 0.0
         self.quiet = True
 
     # -- bhsparse.h:91-125 -------------------------------------------------
@@ -184,6 +185,84 @@ class bhsparse(object):
         if err == BHSPARSE_SUCCESS:
             self.nnzCt, self.masked_ms = int(nnzCt.value), float(ms.value)
         return err
+
+    # -- extension (not in the reference): C = alpha A·B + beta D and the sparse add (include/bhsparse_hip.h, "sparse add")
+    def spgemm_add(self, alpha, beta, rowPtrD, colIndD, valD):
+        """C = alpha A·B + beta D on the data of initData; D: host numpy CSR, m x n, rows strictly ascending.  Returns the
+        status code like spgemm() (an invalid D: BHS_ERR_INVALID_ARG, the last C untouched); fills the csrRowPtrC given to
+        initData and sets nnzCt (products of A·B), nnzC (entries of the sum), time_ms and add_ms (device time of the add).
+        get_nnzC / get_C / get_rowptrC / get_C_device then return this C."""
+        if self._h is None:
+            return _lib.BHS_ERR_NOT_READY
+        import time
+        rowPtrD = np.ascontiguousarray(rowPtrD, np.int32)
+        colIndD = np.ascontiguousarray(colIndD, np.int32)
+        valD = np.ascontiguousarray(valD, self._vdt)
+        if rowPtrD.size < self._m + 1 or valD.size != colIndD.size:
+            return _lib.BHS_ERR_INVALID_ARG
+        nnzD = colIndD.size
+        nnzCt, nnzC = C.c_int64(0), C.c_int(0)
+        ms = (C.c_double * 2)()
+        t0 = time.perf_counter()
+        err = self._lib.bhs_spgemm_add(self._h, float(alpha), float(beta), nnzD, _ptr(valD) if nnzD else None, _ptr(rowPtrD),
+                                       _ptr(colIndD) if nnzD else None, _ptr(self._rowptrC), C.byref(nnzCt), C.byref(nnzC), ms)
+        self.time_ms = (time.perf_counter() - t0) * 1e3
+        if err == BHSPARSE_SUCCESS:
+            self.nnzCt, self.nnzC, self.add_ms = int(nnzCt.value), int(nnzC.value), float(ms[1])
+        return err
+
+    def spgemm_add_device(self, alpha, beta, nnzD, d_valD, d_rowPtrD, d_colIndD):
+        """The same with D on the device (torch tensors on this handle's GPU, or raw device addresses)."""
+        if self._h is None:
+            return _lib.BHS_ERR_NOT_READY
+        if any(hasattr(t, "is_cuda") and t.is_cuda for t in (d_valD, d_rowPtrD, d_colIndD)):
+            import torch
+            torch.cuda.synchronize()                       # the library works on its own stream (see initData_device)
+        nnzCt, nnzC = C.c_int64(0), C.c_int(0)
+        ms = (C.c_double * 2)()
+        err = self._lib.bhs_spgemm_add_device(self._h, float(alpha), float(beta), int(nnzD), _ptr(d_valD), _ptr(d_rowPtrD),
+                                              _ptr(d_colIndD), _ptr(self._rowptrC), C.byref(nnzCt), C.byref(nnzC), ms)
+        if err == BHSPARSE_SUCCESS:
+            self.nnzCt, self.nnzC, self.add_ms = int(nnzCt.value), int(nnzC.value), float(ms[1])
+        return err
+
+    def csr_add_symbolic_device(self, m, n, nnzX, d_rowPtrX, d_colIndX, nnzY, d_rowPtrY, d_colIndY, d_rowPtrZ):
+        """bhs_csr_add_symbolic_device: (status, nnz(Z), y_inside_x); d_rowPtrZ (m+1 ints on the device) is written."""
+        nnzZ, inside = C.c_int(0), C.c_int(0)
+        err = self._lib.bhs_csr_add_symbolic_device(self._h, int(m), int(n), int(nnzX), _ptr(d_rowPtrX), _ptr(d_colIndX),
+                                                    int(nnzY), _ptr(d_rowPtrY), _ptr(d_colIndY), _ptr(d_rowPtrZ),
+                                                    C.byref(nnzZ), C.byref(inside))
+        return err, int(nnzZ.value), int(inside.value)
+
+    def csr_add_numeric_device(self, m, n, alpha, nnzX, d_valX, d_rowPtrX, d_colIndX, beta, nnzY, d_valY, d_rowPtrY, d_colIndY,
+                               d_rowPtrZ, d_colIndZ, d_valZ):
+        """bhs_csr_add_numeric_device: the status code; sets add_ms."""
+        ms = C.c_double(0)
+        err = self._lib.bhs_csr_add_numeric_device(self._h, int(m), int(n), float(alpha), int(nnzX), _ptr(d_valX), _ptr(d_rowPtrX),
+                                                   _ptr(d_colIndX), float(beta), int(nnzY), _ptr(d_valY), _ptr(d_rowPtrY),
+                                                   _ptr(d_colIndY), _ptr(d_rowPtrZ), _ptr(d_colIndZ), _ptr(d_valZ), C.byref(ms))
+        if err == BHSPARSE_SUCCESS:
+            self.add_ms = float(ms.value)
+        return err
+
+    def csr_add_device(self, m, n, alpha, X, beta, Y):
+        """Z = alpha X + beta Y on device arrays: X, Y = (rowPtr, colInd, val) torch tensors on this handle's GPU.  Returns
+        (rowPtrZ, colIndZ, valZ, y_inside_x) as torch tensors; raises BhsparseError on failure."""
+        import torch
+        torch.cuda.synchronize()                           # the library works on its own stream (see initData_device)
+        Xp, Xj, Xx = X
+        Yp, Yj, Yx = Y
+        Zp = torch.empty(m + 1, dtype=torch.int32, device=Xp.device)
+        err, nnzZ, inside = self.csr_add_symbolic_device(m, n, Xj.numel(), Xp, Xj, Yj.numel(), Yp, Yj, Zp)
+        if err != BHSPARSE_SUCCESS:
+            raise BhsparseError("bhs_csr_add_symbolic_device", err)
+        Zj = torch.empty(max(nnzZ, 1), dtype=torch.int32, device=Xp.device)
+        Zx = torch.empty(max(nnzZ, 1), dtype=Xx.dtype, device=Xp.device)
+        torch.cuda.synchronize()
+        err = self.csr_add_numeric_device(m, n, alpha, Xj.numel(), Xx, Xp, Xj, beta, Yj.numel(), Yx, Yp, Yj, Zp, Zj, Zx)
+        if err != BHSPARSE_SUCCESS:
+            raise BhsparseError("bhs_csr_add_numeric_device", err)
+        return Zp, Zj[:nnzZ], Zx[:nnzZ], inside
 
     def get_nnzC(self):
         if self._h is None:
@@ -389,3 +468,73 @@ def spgemm_masked_csr(m, k, n, Ap, Aj, Ax, Bp, Bj, Bx, Mp, Mj, options=None, val
     finally:
         bh.freePlatform()
     return valC, info
+
+
+def _new_handle(value_dtype, device, options):
+    plats = [False] * NUM_PLATFORMS
+    plats[BHSPARSE_HIP] = True
+    bh = bhsparse(value_dtype=value_dtype)
+    err = bh.initPlatform(plats, device=device)
+    if err:
+        raise BhsparseError("initPlatform", err)
+    for key, val in (options or {}).items():
+        err = bh.set_option(key, val)
+        if err:
+            bh.freePlatform()
+            raise BhsparseError("set_option(%s)" % key, err)
+    return bh
+
+
+def csr_add(m, n, alpha, Xp, Xj, Xx, beta, Yp, Yj, Yx, value_dtype=np.float64, device=0):
+    """Convenience: Z = alpha X + beta Y once on host CSR arrays (m x n, rows strictly ascending), staged as torch tensors
+    on the handle's device -- the stand-alone add takes device arrays only.  Returns (Zp int32[m+1], Zj int32[nnzZ],
+    Zx value_dtype[nnzZ], info) with info["kernels"], info["y_inside_x"], info["ms"].  Needs no multiply data."""
+    import torch
+    dev = torch.device("cuda", device)
+    tdt = torch.float32 if np.dtype(value_dtype) == np.dtype(np.float32) else torch.float64
+
+    def up(a, dt):
+        return torch.from_numpy(np.ascontiguousarray(a, dt).copy()).to(dev)
+    X = (up(Xp, np.int32), up(Xj, np.int32), up(Xx, value_dtype))
+    Y = (up(Yp, np.int32), up(Yj, np.int32), up(Yx, value_dtype))
+    assert X[2].dtype == tdt
+    bh = _new_handle(value_dtype, device, None)
+    try:
+        Zp, Zj, Zx, inside = bh.csr_add_device(m, n, alpha, X, beta, Y)
+        info = {"kernels": bh.kernel_stats(), "y_inside_x": inside, "ms": bh.add_ms}
+        out = (Zp.cpu().numpy(), Zj.cpu().numpy(), Zx.cpu().numpy(), info)
+    finally:
+        bh.freePlatform()
+    return out
+
+
+def spgemm_add_csr(m, k, n, Ap, Aj, Ax, Bp, Bj, Bx, Dp, Dj, Dx, alpha=1.0, beta=1.0, options=None, value_dtype=np.float64,
+                   device=0):
+    """Convenience: C = alpha A·B + beta D once on host CSR arrays.  Returns (rowPtrC, colIndC, valC, info)."""
+    bh = _new_handle(value_dtype, device, options)
+    try:
+        Ap, Aj, Ax = (np.ascontiguousarray(Ap, np.int32), np.ascontiguousarray(Aj, np.int32),
+                      np.ascontiguousarray(Ax, value_dtype))
+        Bp, Bj, Bx = (np.ascontiguousarray(Bp, np.int32), np.ascontiguousarray(Bj, np.int32),
+                      np.ascontiguousarray(Bx, value_dtype))
+        Cp = np.zeros(m + 1, np.int32)
+        err = bh.initData(m, k, n, len(Aj), Ax, Ap, Aj, len(Bj), Bx, Bp, Bj, Cp)
+        if err:
+            raise BhsparseError("initData", err)
+        err = bh.spgemm_add(alpha, beta, Dp, Dj, Dx)
+        if err:
+            raise BhsparseError("bhs_spgemm_add", err)
+        nnzC = bh.get_nnzC()
+        Cj = np.empty(nnzC, np.int32)
+        Cx = np.empty(nnzC, value_dtype)
+        err = bh.get_C(Cj, Cx)
+        if err:
+            raise BhsparseError("get_C", err)
+        info = {"nnzCt": bh.nnzCt, "nnzC": nnzC, "add_ms": bh.add_ms, "time_ms": bh.time_ms, "kernels": bh.kernel_stats(),
+                "add_inplace_used": bh.get_info("add_inplace_used"), "class_state": bh.get_info("class_state")}
+        err = bh.free_mem()
+        if err:
+            raise BhsparseError("free_mem", err)
+    finally:
+        bh.freePlatform()
+    return Cp, Cj, Cx, info

@@ -45,6 +45,11 @@ public:
     // (m x n, rows strictly ascending; 0 where no product lands).  Host arrays; does not disturb get_C's result.
     int spgemm_masked(int *csrRowPtrM, int *csrColIndM, int nnzM, value_type *csrValC);
 
+    // EXTENSION, not part of the reference's API: C = alpha A·B + beta D (bhs_spgemm_add, include/bhsparse_hip.h) on the
+    // data of initData; D is m x n CSR with strictly ascending rows, host arrays.  Fills the csrRowPtrC of initData;
+    // get_nnzC / get_C then return the sum.
+    int spgemm_add(value_type alpha, value_type beta, int nnzD, value_type *csrValD, int *csrRowPtrD, int *csrColIndD);
+
 private:
     bool       *_spgemm_platform;
     bhs_handle *_h;
@@ -108,6 +113,15 @@ inline int bhsparse::spgemm_masked(int *csrRowPtrM, int *csrColIndM, int nnzM, v
 {
     if (!_h) return BHS_ERR_NOT_READY;
     return bhs_spgemm_masked(_h, csrRowPtrM, csrColIndM, nnzM, csrValC, 0, 0);
+}
+
+inline int bhsparse::spgemm_add(value_type alpha, value_type beta, int nnzD, value_type *csrValD, int *csrRowPtrD, int *csrColIndD)
+{
+    if (!_h) return BHS_ERR_NOT_READY;
+    int64_t nnzCt = 0;
+    int err = bhs_spgemm_add(_h, alpha, beta, nnzD, csrValD, csrRowPtrD, csrColIndD, _h_csrRowPtrC, &nnzCt, &_nnzC, 0);
+    if (err == BHSPARSE_SUCCESS) _nnzCt_full = nnzCt;
+    return err;
 }
 
 inline int bhsparse::get_nnzC()

@@ -171,6 +171,56 @@ BHS_API int bhs_spgemm_masked_device(bhs_handle *h, const int *d_rowPtrM, const 
 BHS_API int bhs_spgemm_masked(bhs_handle *h, const int *rowPtrM, const int *colIndM, int nnzM,
                               bhs_value_t *valC, int64_t *nnzCt_out, double *ms_out);   /* host arrays, copied */
 
+/* ---- sparse add -----------------------------------------------------------
+ * Z = alpha X + beta Y on CSR with the UNION of the patterns (rocSPARSE csrgeam; no reference counterpart), and the
+ * multiply with an addend, C = alpha A·B + beta D (bhs_add.hip.h).  X, Y, D: 0-based int32 CSR with STRICTLY ascending
+ * rows; so is the result.  The pattern never depends on values: an entry of both operands reads alpha x + beta y even
+ * where that sum is 0, and alpha == 0 / beta == 0 keep their operand's entries as explicit zeros (bhs_spgemm's contract:
+ * "explicit zeros kept").  Arithmetic in double, one rounding to bhs_value_t per entry; no atomics: the result does not
+ * depend on scheduling.
+ *
+ * bhs_csr_add_symbolic_device: the pattern's row pointer.  X and Y are m x n.  Writes d_rowPtrZ (m+1 ints, caller-owned,
+ *   device) and returns nnz(Z) in *nnzZ_out.  *y_inside_x_out (may be NULL) = 1 when every entry of Y is an entry of X
+ *   (then rowPtrZ == rowPtrX).  Validated on the device before anything is written, as bhs_spgemm_masked validates M:
+ *   rowPtr[0] != 0, a decreasing rowPtr, rowPtr[m] != nnz, a column outside [0, n) or a row not strictly ascending
+ *   returns BHS_ERR_INVALID_ARG; nnz(Z) > INT32_MAX returns BHS_ERR_NNZ_OVERFLOW.  Needs no bound data (works on a handle
+ *   straight after bhs_create); BHS_ERR_INVALID_ARG between bhs_spgemm_symbolic and bhs_spgemm_finish.  Synchronous.
+ * bhs_csr_add_numeric_device: Z = alpha X + beta Y on the rowPtrZ of the call above: writes d_colIndZ / d_valZ
+ *   (caller-owned, nnz(Z) entries, must not overlap X or Y), rows strictly ascending.  ms_out (may be NULL): device time.
+ *   Synchronous.  Z may be the X of a later add.
+ * bhs_spgemm_add[_device]: C = alpha A·B + beta D on the data bound by bhs_set_data[_device]; D is m x n (device arrays /
+ *   host arrays, copied).  Runs the ordinary multiply (every option, path and precondition of bhs_spgemm applies), then
+ *   the add.  Afterwards bhs_get_nnzC / bhs_get_C / bhs_get_rowptrC / bhs_get_C_device return THIS C (library-owned,
+ *   valid until the next multiply / bhs_free_data / bhs_destroy); rowPtrC_out / nnzCt_out / nnzC_out as in bhs_spgemm
+ *   (nnzCt: products of A·B; nnzC: entries of the sum).  ms_out[2] (may be NULL): device time of the multiply, of the
+ *   add.  An invalid D returns BHS_ERR_INVALID_ARG before the multiply is started and leaves the handle's last C as it
+ *   was.  BHS_ERR_INVALID_ARG while output arrays are bound with bhs_set_output_device (the sum's size is not known
+ *   when they are bound) and between bhs_spgemm_symbolic and bhs_spgemm_finish; BHS_ERR_NOT_READY without data.
+ *   Where every entry of D is an entry of A·B (A·A + A with a full diagonal, a smoothed prolongator, J·S + K with K
+ *   inside the product) the add runs IN PLACE: no second C, no column rewritten; with alpha == 1 only the values D names
+ *   are touched.  Otherwise the sum goes to a second set of arrays and the getters serve those; the multiply's own
+ *   arrays stay where they are.  The next bhs_spgemm, bhs_spgemm_symbolic, bhs_warmup or bhs_free_data drops the sum;
+ *   bhs_spgemm_masked leaves it alone.  "class_state", the speculative-launch figures and every option are what the
+ *   inner bhs_spgemm leaves.
+ * bhs_get_kernel_stats after any of these reports the add's kernel families (add_count, add_scan, add_bin, add_short,
+ * add_wave, add_long, add_inplace) -- after bhs_spgemm_add beside the multiply's families.
+ * Tunables: "add_inplace" (default 1; 0: the sum always goes to the second set of arrays).  bhs_get_info
+ * "add_inplace_used": 1 / 0 for the last bhs_spgemm_add.                                                          */
+BHS_API int bhs_csr_add_symbolic_device(bhs_handle *h, int m, int n,
+                                        int nnzX, const int *d_rowPtrX, const int *d_colIndX,
+                                        int nnzY, const int *d_rowPtrY, const int *d_colIndY,
+                                        int *d_rowPtrZ, int *nnzZ_out, int *y_inside_x_out);
+BHS_API int bhs_csr_add_numeric_device(bhs_handle *h, int m, int n,
+                                       double alpha, int nnzX, const bhs_value_t *d_valX, const int *d_rowPtrX, const int *d_colIndX,
+                                       double beta, int nnzY, const bhs_value_t *d_valY, const int *d_rowPtrY, const int *d_colIndY,
+                                       const int *d_rowPtrZ, int *d_colIndZ, bhs_value_t *d_valZ, double *ms_out);
+BHS_API int bhs_spgemm_add_device(bhs_handle *h, double alpha, double beta,
+                                  int nnzD, const bhs_value_t *d_valD, const int *d_rowPtrD, const int *d_colIndD,
+                                  int *rowPtrC_out, int64_t *nnzCt_out, int *nnzC_out, double ms_out[2]);
+BHS_API int bhs_spgemm_add(bhs_handle *h, double alpha, double beta,
+                           int nnzD, const bhs_value_t *valD, const int *rowPtrD, const int *colIndD,
+                           int *rowPtrC_out, int64_t *nnzCt_out, int *nnzC_out, double ms_out[2]);   /* host arrays, copied */
+
 /* replaces bhsparse::get_nnzC (bhsparse.h: get_nnzC -> bhsparse_cuda::get_nnzC). */
 BHS_API int bhs_get_nnzC(bhs_handle *h, int *nnzC_out);
 
@@ -306,6 +356,8 @@ BHS_API int bhs_get_kernel_stats(bhs_handle *h, bhs_kernel_stat *out, int cap);
  *                     (bhs_hub.hip.h: items of "hub_item_products" products handed out to the whole device, one shared
  *                     bitmap slot per row); default 131072, 0 never.  "hub_item_products" (default 8192, >= 64),
  *                     "hub_slots" (rows per batch; default: as many as fit 1/16 of the device memory)
+ *   "add_inplace"     1 (default): bhs_spgemm_add adds into valC in place where every entry of D is an entry of A·B; 0: the
+ *                     sum always goes to a second set of arrays (tests reach both paths on the same data)
  *   "wg_per_cu"       persistent workgroups per CU of the wave kernels (default: occupancy API)
  *   "verbose"         same as bhs_set_verbose
  * Returns BHS_ERR_INVALID_ARG for unknown keys.                               */
@@ -322,6 +374,7 @@ BHS_API int bhs_set_option(bhs_handle *h, const char *key, int64_t value);
  *                mask) pairs for this data set
  *   "class_state"  which pipeline this data set's multiplies take: 1 row classes, 2 row classes with irregular rows on the
  *                general pipeline's kernels (mixed mode), -1 the general pipeline (for good: until the next bhs_set_data)
+ *   "add_inplace_used"  1 when the last bhs_spgemm_add added into valC in place, 0 when it wrote the sum to arrays of its own
  *   "mixed_rows"   rows of the last multiply that had no class and went through the general pipeline's kernels (0: none)
  * Returns BHS_ERR_INVALID_ARG for unknown keys, BHS_ERR_NOT_READY without data.  */
 BHS_API int bhs_get_info(bhs_handle *h, const char *key, int64_t *value_out);
