@@ -31,6 +31,15 @@ class KernelStat(C.Structure):
                 ("nnzA_rows", C.c_int64)]
 
 
+class Select(C.Structure):
+    """bhs_select (include/bhsparse_hip.h, "entry selection")"""
+    _fields_ = [("flags", C.c_uint32), ("top_k", C.c_int32), ("band_lo", C.c_int64), ("band_hi", C.c_int64),
+                ("abs_tol", C.c_double), ("rel_tol", C.c_double)]
+
+
+BHS_SEL_BAND, BHS_SEL_DROP_DIAG, BHS_SEL_KEEP_DIAG, BHS_SEL_ABS, BHS_SEL_REL, BHS_SEL_TOPK = 1, 2, 4, 8, 16, 32
+
+
 # every symbol include/bhsparse_hip.h declares: (restype, argtypes)
 _vp, _i, _i64 = C.c_void_p, C.c_int, C.c_int64
 SYMBOLS = {
@@ -66,6 +75,10 @@ SYMBOLS = {
                                    C.POINTER(C.c_double)]),
     "bhs_spgemm_add": (_i, [_vp, C.c_double, C.c_double, _i, _vp, _vp, _vp, _vp, C.POINTER(_i64), C.POINTER(_i),
                             C.POINTER(C.c_double)]),
+    "bhs_csr_select_symbolic_device": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, C.POINTER(Select), _vp, C.POINTER(_i)]),
+    "bhs_csr_select_numeric_device": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, C.POINTER(Select), _vp, _vp, _vp, C.POINTER(C.c_double)]),
+    "bhs_spgemm_select_device": (_i, [_vp, C.POINTER(Select), _vp, C.POINTER(_i64), C.POINTER(_i), C.POINTER(C.c_double)]),
+    "bhs_spgemm_select": (_i, [_vp, C.POINTER(Select), _vp, C.POINTER(_i64), C.POINTER(_i), C.POINTER(C.c_double)]),
     "bhs_strerror": (C.c_char_p, [_i]),
     "bhs_version": (C.c_char_p, []),
 }
@@ -76,7 +89,7 @@ _lib = None
 _libs = {}
 
 
-SOURCES = ("bhsparse_hip.hip", "bhs_host_launch.inc.h", "bhs_host_pipeline.inc.h", "bhs_host_setdata.inc.h", "bhs_host_cabi.inc.h", "bhs_kernels.hip.h", "bhs_row_wg.hip.h", "bhs_row_window.hip.h", "bhs_row_wave.hip.h", "bhs_row_quad.hip.h", "bhs_compress.hip.h", "bhs_row_lane.hip.h", "bhs_sort.hip.h", "bhs_hub.hip.h", "bhs_class.hip.h", "bhs_class_mix.hip.h", "bhs_class_wg.hip.h", "bhs_class_ring.hip.h", "bhs_class_fused.hip.h", "bhs_class_tile.hip.h", "bhs_class_big.hip.h", "bhs_wave.hip.h", "bhs_lab.hip.h", "bhs_masked.hip.h", "bhs_host_masked.inc.h", "bhs_add.hip.h", "bhs_host_add.inc.h")
+SOURCES = ("bhsparse_hip.hip", "bhs_host_launch.inc.h", "bhs_host_pipeline.inc.h", "bhs_host_setdata.inc.h", "bhs_host_cabi.inc.h", "bhs_kernels.hip.h", "bhs_row_wg.hip.h", "bhs_row_window.hip.h", "bhs_row_wave.hip.h", "bhs_row_quad.hip.h", "bhs_compress.hip.h", "bhs_row_lane.hip.h", "bhs_sort.hip.h", "bhs_hub.hip.h", "bhs_class.hip.h", "bhs_class_mix.hip.h", "bhs_class_wg.hip.h", "bhs_class_ring.hip.h", "bhs_class_fused.hip.h", "bhs_class_tile.hip.h", "bhs_class_big.hip.h", "bhs_wave.hip.h", "bhs_lab.hip.h", "bhs_masked.hip.h", "bhs_host_masked.inc.h", "bhs_add.hip.h", "bhs_host_add.inc.h", "bhs_select.hip.h", "bhs_host_select.inc.h")
 
 
 def source_digest():

@@ -117,6 +117,9 @@ int bhs_destroy(bhs_handle* h)
     for (int i = 0; i < 3; ++i) release(h->maskM[i]);
     release(h->addCtl); release(h->addQueue); release(h->addCnt); release(h->addTiles); release(h->addPos); release(h->sumCp);
     for (int i = 0; i < 3; ++i) release(h->addD[i]);
+    release(h->selCtl); release(h->selQueue); release(h->selCnt); release(h->selTiles);
+    if (h->selHost) (void)hipHostFree(h->selHost);
+    for (int i = 0; i < 2; ++i) if (h->selEv[i]) (void)hipEventDestroy(h->selEv[i]);
     if (h->addHost) (void)hipHostFree(h->addHost);
     for (int i = 0; i < 2; ++i) if (h->addEv[i]) (void)hipEventDestroy(h->addEv[i]);
     if (h->maskHost) (void)hipHostFree(h->maskHost);
@@ -492,6 +495,7 @@ int bhs_get_info(bhs_handle* h, const char* key, int64_t* value_out)
     if (!strcmp(key, "local_a")) { *value_out = h->localA; return BHS_SUCCESS; }
     if (!strcmp(key, "line_a")) { *value_out = h->lineA; return BHS_SUCCESS; }
     if (!strcmp(key, "add_inplace_used")) { *value_out = h->addInplaceUsed; return BHS_SUCCESS; }   // the last bhs_spgemm_add added into valC in place (1) or wrote the sum to arrays of its own (0)
+    if (!strcmp(key, "select_dropped")) { *value_out = h->selDropped; return BHS_SUCCESS; }   // entries the last bhs_spgemm_select removed from A·B
     if (!strcmp(key, "compress_b_used")) { *value_out = h->cmpState > 0 ? 1 : 0; return BHS_SUCCESS; }
     return BHS_ERR_INVALID_ARG;
 }

@@ -1,6 +1,6 @@
 // bhsparse_hip.hip — libbhsparse_hip.so (see include/bhsparse_hip.h): the handle and its helpers here; the launch helpers,
 // the pipeline, the hand-over of a data set and the C-ABI in bhs_host_{launch,pipeline,setdata,cabi}.inc.h, the masked multiply
-// and the sparse add in bhs_host_{masked,add}.inc.h (one translation unit).
+// the sparse add and the entry selection in bhs_host_{masked,add,select}.inc.h (one translation unit).
 //
 // Pipeline of one bhs_spgemm() (replaces bhsparse::spgemm_cuda, bhsparse.h:297-339):
 //   stage 1  k_upper_bound (ub per row, nnzCt, symbolic-bin histogram)          <- compute_nnzCt + statistics()
@@ -43,6 +43,7 @@
 #include "bhs_class_big.hip.h"
 #include "bhs_masked.hip.h"
 #include "bhs_add.hip.h"
+#include "bhs_select.hip.h"
 
 #include <algorithm>
 #include <chrono>
@@ -363,9 +364,16 @@ struct bhs_handle {
     int addInplaceUsed = 0;              // bhs_get_info "add_inplace_used": the last bhs_spgemm_add added into valC in place
     // C = alpha A·B + beta D where D reaches outside A·B: the sum, served by the getters until the next multiply drops it
     // (the pipeline's own Cp / Cj / Cx stay where they are)
+    // (bhs_spgemm_select's selected C where entries were dropped lives there in the same way)
     DevBuf sumCp, sumCj, sumCx;
     bool sumActive = false;
     long long sumNnz = 0;
+    // the entry selection (bhs_host_select.inc.h): buffers of its own as well
+    DevBuf selCtl, selQueue, selCnt, selTiles;   // counters; per-bin queues of rows; the rows' counts, scanned in place; its scan's tile words (epoch selEpoch)
+    int* selHost = nullptr;              // pinned mirror of selCtl
+    hipEvent_t selEv[2] = {nullptr, nullptr};
+    unsigned selEpoch = 0;
+    long long selDropped = 0;            // bhs_get_info "select_dropped": entries the last bhs_spgemm_select removed
 };
 
 namespace {
@@ -519,3 +527,4 @@ inline int one_launch(int rc) { return rc != BHS_SUCCESS ? rc : 1; }
 #include "bhs_host_cabi.inc.h"
 #include "bhs_host_masked.inc.h"
 #include "bhs_host_add.inc.h"
+#include "bhs_host_select.inc.h"

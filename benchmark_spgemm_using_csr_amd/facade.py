@@ -60,6 +60,7 @@ class bhsparse(object):
         self.time_ms = 0.0
         self.masked_ms = 0.0
         self.add_ms = 0.0
+        self.select_ms = 0.0
         self.quiet = True
 
     # -- bhsparse.h:91-125 -------------------------------------------------
@@ -263,6 +264,71 @@ class bhsparse(object):
         if err != BHSPARSE_SUCCESS:
             raise BhsparseError("bhs_csr_add_numeric_device", err)
         return Zp, Zj[:nnzZ], Zx[:nnzZ], inside
+
+    # -- extension (not in the reference): entry selection and the pruned multiply (include/bhsparse_hip.h, "entry selection")
+    def spgemm_select(self, spec):
+        """C = select(A·B) on the data of initData; spec: a select_spec(...) / _lib.Select.  Returns the status code like
+        spgemm(); fills the csrRowPtrC given to initData and sets nnzCt (products of A·B), nnzC (entries after the
+        selection), time_ms and select_ms (device time of the selection).  get_nnzC / get_C / get_rowptrC / get_C_device
+        then return the selected C."""
+        if self._h is None:
+            return _lib.BHS_ERR_NOT_READY
+        import time
+        nnzCt, nnzC = C.c_int64(0), C.c_int(0)
+        ms = (C.c_double * 2)()
+        t0 = time.perf_counter()
+        err = self._lib.bhs_spgemm_select(self._h, C.byref(spec), _ptr(self._rowptrC), C.byref(nnzCt), C.byref(nnzC), ms)
+        self.time_ms = (time.perf_counter() - t0) * 1e3
+        if err == BHSPARSE_SUCCESS:
+            self.nnzCt, self.nnzC, self.select_ms = int(nnzCt.value), int(nnzC.value), float(ms[1])
+        return err
+
+    def spgemm_select_device(self, spec, d_rowPtrC=None):
+        """The same; d_rowPtrC (may be None): m+1 ints on the device that receive the selected C's row pointer."""
+        if self._h is None:
+            return _lib.BHS_ERR_NOT_READY
+        nnzCt, nnzC = C.c_int64(0), C.c_int(0)
+        ms = (C.c_double * 2)()
+        err = self._lib.bhs_spgemm_select_device(self._h, C.byref(spec), _ptr(d_rowPtrC), C.byref(nnzCt), C.byref(nnzC), ms)
+        if err == BHSPARSE_SUCCESS:
+            self.nnzCt, self.nnzC, self.select_ms = int(nnzCt.value), int(nnzC.value), float(ms[1])
+        return err
+
+    def csr_select_symbolic_device(self, m, n, nnzX, d_valX, d_rowPtrX, d_colIndX, spec, d_rowPtrZ):
+        """bhs_csr_select_symbolic_device: (status, nnz(Z)); d_rowPtrZ (m+1 ints on the device) is written."""
+        nnzZ = C.c_int(0)
+        err = self._lib.bhs_csr_select_symbolic_device(self._h, int(m), int(n), int(nnzX), _ptr(d_valX), _ptr(d_rowPtrX),
+                                                       _ptr(d_colIndX), C.byref(spec), _ptr(d_rowPtrZ), C.byref(nnzZ))
+        return err, int(nnzZ.value)
+
+    def csr_select_numeric_device(self, m, n, nnzX, d_valX, d_rowPtrX, d_colIndX, spec, d_rowPtrZ, d_colIndZ, d_valZ):
+        """bhs_csr_select_numeric_device: the status code; sets select_ms."""
+        ms = C.c_double(0)
+        err = self._lib.bhs_csr_select_numeric_device(self._h, int(m), int(n), int(nnzX), _ptr(d_valX), _ptr(d_rowPtrX),
+                                                      _ptr(d_colIndX), C.byref(spec), _ptr(d_rowPtrZ), _ptr(d_colIndZ),
+                                                      _ptr(d_valZ), C.byref(ms))
+        if err == BHSPARSE_SUCCESS:
+            self.select_ms = float(ms.value)
+        return err
+
+    def csr_select_device(self, m, n, X, spec, values=True):
+        """Z = select(X) on device arrays: X = (rowPtr, colInd, val) torch tensors on this handle's GPU (val may be None for
+        a rule without value flags).  Returns (rowPtrZ, colIndZ, valZ) as torch tensors (valZ None when values is false or
+        X has none); raises BhsparseError on failure."""
+        import torch
+        torch.cuda.synchronize()                           # the library works on its own stream (see initData_device)
+        Xp, Xj, Xx = X
+        Zp = torch.empty(m + 1, dtype=torch.int32, device=Xp.device)
+        err, nnzZ = self.csr_select_symbolic_device(m, n, Xj.numel(), Xx, Xp, Xj, spec, Zp)
+        if err != BHSPARSE_SUCCESS:
+            raise BhsparseError("bhs_csr_select_symbolic_device", err)
+        Zj = torch.empty(max(nnzZ, 1), dtype=torch.int32, device=Xp.device)
+        Zx = torch.empty(max(nnzZ, 1), dtype=Xx.dtype, device=Xp.device) if (values and Xx is not None) else None
+        torch.cuda.synchronize()
+        err = self.csr_select_numeric_device(m, n, Xj.numel(), Xx, Xp, Xj, spec, Zp, Zj, Zx)
+        if err != BHSPARSE_SUCCESS:
+            raise BhsparseError("bhs_csr_select_numeric_device", err)
+        return Zp, Zj[:nnzZ], (Zx[:nnzZ] if Zx is not None else None)
 
     def get_nnzC(self):
         if self._h is None:
@@ -470,6 +536,32 @@ def spgemm_masked_csr(m, k, n, Ap, Aj, Ax, Bp, Bj, Bx, Mp, Mj, options=None, val
     return valC, info
 
 
+def select_spec(band=None, drop_diag=False, keep_diag=False, abs_tol=None, rel_tol=None, top_k=None):
+    """A bhs_select rule: band = (lo, hi) on col - row (None ends: unbounded), abs_tol / rel_tol / top_k set their flag when
+    given."""
+    s = _lib.Select()
+    s.flags = 0
+    s.band_lo, s.band_hi = -2 ** 63, 2 ** 63 - 1
+    if band is not None:
+        s.flags |= _lib.BHS_SEL_BAND
+        s.band_lo = -2 ** 63 if band[0] is None else int(band[0])
+        s.band_hi = 2 ** 63 - 1 if band[1] is None else int(band[1])
+    if drop_diag:
+        s.flags |= _lib.BHS_SEL_DROP_DIAG
+    if keep_diag:
+        s.flags |= _lib.BHS_SEL_KEEP_DIAG
+    if abs_tol is not None:
+        s.flags |= _lib.BHS_SEL_ABS
+        s.abs_tol = float(abs_tol)
+    if rel_tol is not None:
+        s.flags |= _lib.BHS_SEL_REL
+        s.rel_tol = float(rel_tol)
+    if top_k is not None:
+        s.flags |= _lib.BHS_SEL_TOPK
+        s.top_k = int(top_k)
+    return s
+
+
 def _new_handle(value_dtype, device, options):
     plats = [False] * NUM_PLATFORMS
     plats[BHSPARSE_HIP] = True
@@ -532,6 +624,57 @@ def spgemm_add_csr(m, k, n, Ap, Aj, Ax, Bp, Bj, Bx, Dp, Dj, Dx, alpha=1.0, beta=
             raise BhsparseError("get_C", err)
         info = {"nnzCt": bh.nnzCt, "nnzC": nnzC, "add_ms": bh.add_ms, "time_ms": bh.time_ms, "kernels": bh.kernel_stats(),
                 "add_inplace_used": bh.get_info("add_inplace_used"), "class_state": bh.get_info("class_state")}
+        err = bh.free_mem()
+        if err:
+            raise BhsparseError("free_mem", err)
+    finally:
+        bh.freePlatform()
+    return Cp, Cj, Cx, info
+
+
+def csr_select(m, n, Xp, Xj, Xx, spec, value_dtype=np.float64, device=0):
+    """Convenience: Z = select(X) once on host CSR arrays (m x n), staged as torch tensors on the handle's device -- the
+    stand-alone selection takes device arrays only.  Returns (Zp int32[m+1], Zj int32[nnzZ], Zx value_dtype[nnzZ], info)
+    with info["kernels"], info["ms"].  Needs no multiply data."""
+    import torch
+    dev = torch.device("cuda", device)
+
+    def up(a, dt):
+        return torch.from_numpy(np.ascontiguousarray(a, dt).copy()).to(dev)
+    X = (up(Xp, np.int32), up(Xj, np.int32), up(Xx, value_dtype))
+    bh = _new_handle(value_dtype, device, None)
+    try:
+        Zp, Zj, Zx = bh.csr_select_device(m, n, X, spec)
+        info = {"kernels": bh.kernel_stats(), "ms": bh.select_ms}
+        out = (Zp.cpu().numpy(), Zj.cpu().numpy(), Zx.cpu().numpy(), info)
+    finally:
+        bh.freePlatform()
+    return out
+
+
+def spgemm_select_csr(m, k, n, Ap, Aj, Ax, Bp, Bj, Bx, spec, options=None, value_dtype=np.float64, device=0):
+    """Convenience: C = select(A·B) once on host CSR arrays.  Returns (rowPtrC, colIndC, valC, info)."""
+    bh = _new_handle(value_dtype, device, options)
+    try:
+        Ap, Aj, Ax = (np.ascontiguousarray(Ap, np.int32), np.ascontiguousarray(Aj, np.int32),
+                      np.ascontiguousarray(Ax, value_dtype))
+        Bp, Bj, Bx = (np.ascontiguousarray(Bp, np.int32), np.ascontiguousarray(Bj, np.int32),
+                      np.ascontiguousarray(Bx, value_dtype))
+        Cp = np.zeros(m + 1, np.int32)
+        err = bh.initData(m, k, n, len(Aj), Ax, Ap, Aj, len(Bj), Bx, Bp, Bj, Cp)
+        if err:
+            raise BhsparseError("initData", err)
+        err = bh.spgemm_select(spec)
+        if err:
+            raise BhsparseError("bhs_spgemm_select", err)
+        nnzC = bh.get_nnzC()
+        Cj = np.empty(nnzC, np.int32)
+        Cx = np.empty(nnzC, value_dtype)
+        err = bh.get_C(Cj, Cx)
+        if err:
+            raise BhsparseError("get_C", err)
+        info = {"nnzCt": bh.nnzCt, "nnzC": nnzC, "select_ms": bh.select_ms, "time_ms": bh.time_ms, "kernels": bh.kernel_stats(),
+                "select_dropped": bh.get_info("select_dropped"), "class_state": bh.get_info("class_state")}
         err = bh.free_mem()
         if err:
             raise BhsparseError("free_mem", err)

@@ -50,6 +50,11 @@ public:
     // get_nnzC / get_C then return the sum.
     int spgemm_add(value_type alpha, value_type beta, int nnzD, value_type *csrValD, int *csrRowPtrD, int *csrColIndD);
 
+    // EXTENSION, not part of the reference's API: C = select(A·B) (bhs_spgemm_select, include/bhsparse_hip.h, "entry
+    // selection") on the data of initData: the multiply, then the rule `sel` applied to its result.  Fills the csrRowPtrC of
+    // initData; get_nnzC / get_C then return the selected C.
+    int spgemm_select(const bhs_select &sel);
+
 private:
     bool       *_spgemm_platform;
     bhs_handle *_h;
@@ -120,6 +125,15 @@ inline int bhsparse::spgemm_add(value_type alpha, value_type beta, int nnzD, val
     if (!_h) return BHS_ERR_NOT_READY;
     int64_t nnzCt = 0;
     int err = bhs_spgemm_add(_h, alpha, beta, nnzD, csrValD, csrRowPtrD, csrColIndD, _h_csrRowPtrC, &nnzCt, &_nnzC, 0);
+    if (err == BHSPARSE_SUCCESS) _nnzCt_full = nnzCt;
+    return err;
+}
+
+inline int bhsparse::spgemm_select(const bhs_select &sel)
+{
+    if (!_h) return BHS_ERR_NOT_READY;
+    int64_t nnzCt = 0;
+    int err = bhs_spgemm_select(_h, &sel, _h_csrRowPtrC, &nnzCt, &_nnzC, 0);
     if (err == BHSPARSE_SUCCESS) _nnzCt_full = nnzCt;
     return err;
 }

@@ -221,6 +221,79 @@ BHS_API int bhs_spgemm_add(bhs_handle *h, double alpha, double beta,
                            int nnzD, const bhs_value_t *valD, const int *rowPtrD, const int *colIndD,
                            int *rowPtrC_out, int64_t *nnzCt_out, int *nnzC_out, double ms_out[2]);   /* host arrays, copied */
 
+/* ---- entry selection ------------------------------------------------------
+ * Z = the entries of X that a rule keeps (no reference counterpart): by position, by magnitude and by rank within the
+ * row -- tril / triu / a band, dropping explicit zeros, AMG truncation and strength of connection, threshold + top-k
+ * pruning of iterated products -- and the multiply that applies the rule to its own result (bhs_select.hip.h).
+ * X: m x n, 0-based int32 CSR; rows need NOT be ascending.
+ *
+ * The rule.  Stages apply in this order, each to what the stage before left:
+ *   1. position   BHS_SEL_BAND keeps band_lo <= col - row <= band_hi (the difference in int64 arithmetic: INT64_MIN /
+ *                 INT64_MAX ends are legal); BHS_SEL_DROP_DIAG drops col == row.
+ *   2. ABS        keep unless |v| <= abs_tol   (abs_tol = 0 drops +0 and -0 and nothing else)
+ *   3. REL        keep unless |v| <  rel_tol * rowmax
+ *   4. TOPK       of what is left, the top_k entries of largest |v|
+ * BHS_SEL_KEEP_DIAG: an entry with col == row that passed stage 1 passes ABS, REL and TOPK unconditionally, is not
+ *   counted in top_k and does not enter the row maximum.
+ * rowmax is taken over the entries stage 1 left (without the diagonal under KEEP_DIAG; 0 when there are none): it is the
+ *   entry that ranks highest in the order below, so a row holding a NaN has rowmax = NaN and REL drops nothing there.
+ * Magnitudes are compared as fabs((double)v) -- exact for the float build.  rel_tol * rowmax is one double product.
+ * Rank order is the order of that double's bit pattern read as an unsigned 64-bit integer: NaN ranks above Inf.  The ABS
+ *   and REL tests are written "keep unless", so a NaN is kept: a selection never hides a NaN.  Ties in rank go to the
+ *   entry that comes first in the row.
+ * The output keeps the input order of the survivors and their bits (a stable compaction): ascending rows stay
+ *   ascending.  Nothing is computed on values but these comparisons; no atomics on values: the result does not depend
+ *   on scheduling.
+ * An invalid rule returns BHS_ERR_INVALID_ARG: DROP_DIAG together with KEEP_DIAG, top_k < 0, abs_tol or rel_tol
+ *   negative, NaN or Inf, band_lo > band_hi, unknown flag bits.  Fields whose flag is not set are ignored, except that
+ *   they must still be valid.
+ *
+ * bhs_csr_select_symbolic_device: the selection's row pointer.  Writes d_rowPtrZ (m+1 ints, caller-owned, device) and
+ *   returns nnz(Z) in *nnzZ_out.  X is validated on the device before anything caller-owned is written: rowPtrX[0] != 0,
+ *   a decreasing rowPtrX, rowPtrX[m] != nnzX or a column outside [0, n) returns BHS_ERR_INVALID_ARG.  d_valX may be
+ *   NULL when no value flag (ABS, REL, TOPK) is set.  Needs no bound data; BHS_ERR_INVALID_ARG between
+ *   bhs_spgemm_symbolic and bhs_spgemm_finish.  Synchronous.
+ * bhs_csr_select_numeric_device: writes the survivors to d_colIndZ / d_valZ (caller-owned, nnz(Z) entries, must not
+ *   overlap X) on the d_rowPtrZ of the call above.  d_valZ may be NULL: the pattern alone.  The rule is evaluated again:
+ *   a row whose survivors are not what d_rowPtrZ says (X or the rule changed between the calls) returns
+ *   BHS_ERR_INVALID_ARG; nothing is ever written outside [0, rowPtrZ[m]).  ms_out (may be NULL): device time.  Synchronous.
+ * bhs_spgemm_select / bhs_spgemm_select_device: C = select(A·B) on the data bound by bhs_set_data[_device].  The rule is
+ *   checked first; then the ordinary multiply runs (every option, path and precondition of bhs_spgemm applies), then the
+ *   selection of its C.  Afterwards bhs_get_nnzC / bhs_get_C / bhs_get_rowptrC / bhs_get_C_device return the SELECTED C
+ *   (library-owned, the second set of arrays bhs_spgemm_add uses, with the same lifetime: the next bhs_spgemm,
+ *   bhs_spgemm_symbolic, bhs_warmup or bhs_free_data drops it; the multiply's own arrays never move).  Where the rule
+ *   drops nothing no second set is made and the getters return what bhs_spgemm alone returns.  rowPtrC_out (may be NULL):
+ *   m+1 ints, HOST memory for bhs_spgemm_select, DEVICE memory for bhs_spgemm_select_device; nnzCt_out: products of A·B;
+ *   nnzC_out: entries after the selection; ms_out[2] (may be NULL): device time of the multiply, of the selection.
+ *   BHS_ERR_INVALID_ARG while output arrays are bound with bhs_set_output_device and between bhs_spgemm_symbolic and
+ *   bhs_spgemm_finish; BHS_ERR_NOT_READY without data.  bhs_get_info "select_dropped": entries the last call removed.
+ * bhs_get_kernel_stats after any of these reports the selection's kernel families: select_count (the count pass; for
+ *   the numeric call the binning), select_scan, select_short (rows of up to 32 entries), select_wave (up to 1024),
+ *   select_long -- after bhs_spgemm_select beside the multiply's families.                                        */
+enum {
+  BHS_SEL_BAND      = 1,   /* keep band_lo <= col - row <= band_hi (int64 arithmetic) */
+  BHS_SEL_DROP_DIAG = 2,   /* drop col == row */
+  BHS_SEL_KEEP_DIAG = 4,   /* col == row passes ABS / REL / TOPK unconditionally, is not
+                              counted in top_k and does not enter the row maximum */
+  BHS_SEL_ABS       = 8,   /* keep unless |v| <= abs_tol          (abs_tol = 0 drops +-0) */
+  BHS_SEL_REL       = 16,  /* keep unless |v| <  rel_tol * rowmax                          */
+  BHS_SEL_TOPK      = 32   /* of what is left, the top_k entries of largest |v| */
+};
+typedef struct bhs_select {
+  uint32_t flags; int32_t top_k; int64_t band_lo, band_hi; double abs_tol, rel_tol;
+} bhs_select;
+BHS_API int bhs_csr_select_symbolic_device(bhs_handle *h, int m, int n,
+                                           int nnzX, const bhs_value_t *d_valX, const int *d_rowPtrX, const int *d_colIndX,
+                                           const bhs_select *sel, int *d_rowPtrZ, int *nnzZ_out);
+BHS_API int bhs_csr_select_numeric_device(bhs_handle *h, int m, int n,
+                                          int nnzX, const bhs_value_t *d_valX, const int *d_rowPtrX, const int *d_colIndX,
+                                          const bhs_select *sel, const int *d_rowPtrZ, int *d_colIndZ, bhs_value_t *d_valZ,
+                                          double *ms_out);
+BHS_API int bhs_spgemm_select_device(bhs_handle *h, const bhs_select *sel,
+                                     int *d_rowPtrC_out, int64_t *nnzCt_out, int *nnzC_out, double ms_out[2]);
+BHS_API int bhs_spgemm_select(bhs_handle *h, const bhs_select *sel,
+                              int *rowPtrC_out, int64_t *nnzCt_out, int *nnzC_out, double ms_out[2]);
+
 /* replaces bhsparse::get_nnzC (bhsparse.h: get_nnzC -> bhsparse_cuda::get_nnzC). */
 BHS_API int bhs_get_nnzC(bhs_handle *h, int *nnzC_out);
 
@@ -374,6 +447,7 @@ BHS_API int bhs_set_option(bhs_handle *h, const char *key, int64_t value);
  *                mask) pairs for this data set
  *   "class_state"  which pipeline this data set's multiplies take: 1 row classes, 2 row classes with irregular rows on the
  *                general pipeline's kernels (mixed mode), -1 the general pipeline (for good: until the next bhs_set_data)
+ *   "select_dropped"  entries the last bhs_spgemm_select removed from A·B (0: no second set of arrays was made)
  *   "add_inplace_used"  1 when the last bhs_spgemm_add added into valC in place, 0 when it wrote the sum to arrays of its own
  *   "mixed_rows"   rows of the last multiply that had no class and went through the general pipeline's kernels (0: none)
  * Returns BHS_ERR_INVALID_ARG for unknown keys, BHS_ERR_NOT_READY without data.  */
