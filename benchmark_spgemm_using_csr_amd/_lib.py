@@ -79,6 +79,8 @@ SYMBOLS = {
     "bhs_csr_select_numeric_device": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, C.POINTER(Select), _vp, _vp, _vp, C.POINTER(C.c_double)]),
     "bhs_spgemm_select_device": (_i, [_vp, C.POINTER(Select), _vp, C.POINTER(_i64), C.POINTER(_i), C.POINTER(C.c_double)]),
     "bhs_spgemm_select": (_i, [_vp, C.POINTER(Select), _vp, C.POINTER(_i64), C.POINTER(_i), C.POINTER(C.c_double)]),
+    "bhs_csr_transpose_device": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_double)]),
+    "bhs_csr_transpose_values_device": (_i, [_vp, _i, _vp, _vp, _vp, C.POINTER(C.c_double)]),
     "bhs_strerror": (C.c_char_p, [_i]),
     "bhs_version": (C.c_char_p, []),
 }
@@ -89,7 +91,7 @@ _lib = None
 _libs = {}
 
 
-SOURCES = ("bhsparse_hip.hip", "bhs_host_launch.inc.h", "bhs_host_pipeline.inc.h", "bhs_host_setdata.inc.h", "bhs_host_cabi.inc.h", "bhs_kernels.hip.h", "bhs_row_wg.hip.h", "bhs_row_window.hip.h", "bhs_row_wave.hip.h", "bhs_row_quad.hip.h", "bhs_compress.hip.h", "bhs_row_lane.hip.h", "bhs_sort.hip.h", "bhs_hub.hip.h", "bhs_class.hip.h", "bhs_class_mix.hip.h", "bhs_class_wg.hip.h", "bhs_class_ring.hip.h", "bhs_class_fused.hip.h", "bhs_class_tile.hip.h", "bhs_class_big.hip.h", "bhs_wave.hip.h", "bhs_lab.hip.h", "bhs_masked.hip.h", "bhs_host_masked.inc.h", "bhs_add.hip.h", "bhs_host_add.inc.h", "bhs_select.hip.h", "bhs_host_select.inc.h")
+SOURCES = ("bhsparse_hip.hip", "bhs_host_launch.inc.h", "bhs_host_pipeline.inc.h", "bhs_host_setdata.inc.h", "bhs_host_cabi.inc.h", "bhs_kernels.hip.h", "bhs_row_wg.hip.h", "bhs_row_window.hip.h", "bhs_row_wave.hip.h", "bhs_row_quad.hip.h", "bhs_compress.hip.h", "bhs_row_lane.hip.h", "bhs_sort.hip.h", "bhs_hub.hip.h", "bhs_class.hip.h", "bhs_class_mix.hip.h", "bhs_class_wg.hip.h", "bhs_class_ring.hip.h", "bhs_class_fused.hip.h", "bhs_class_tile.hip.h", "bhs_class_big.hip.h", "bhs_wave.hip.h", "bhs_lab.hip.h", "bhs_masked.hip.h", "bhs_host_masked.inc.h", "bhs_add.hip.h", "bhs_host_add.inc.h", "bhs_select.hip.h", "bhs_host_select.inc.h", "bhs_transpose.hip.h", "bhs_host_transpose.inc.h")
 
 
 def source_digest():

@@ -120,6 +120,9 @@ int bhs_destroy(bhs_handle* h)
     release(h->selCtl); release(h->selQueue); release(h->selCnt); release(h->selTiles);
     if (h->selHost) (void)hipHostFree(h->selHost);
     for (int i = 0; i < 2; ++i) if (h->selEv[i]) (void)hipEventDestroy(h->selEv[i]);
+    release(h->trCtl); release(h->trCnt); release(h->trCur); release(h->trQueue); release(h->trWin); release(h->trKeys); release(h->trTiles);
+    if (h->trHost) (void)hipHostFree(h->trHost);
+    for (int i = 0; i < 2; ++i) if (h->trEv[i]) (void)hipEventDestroy(h->trEv[i]);
     if (h->addHost) (void)hipHostFree(h->addHost);
     for (int i = 0; i < 2; ++i) if (h->addEv[i]) (void)hipEventDestroy(h->addEv[i]);
     if (h->maskHost) (void)hipHostFree(h->maskHost);

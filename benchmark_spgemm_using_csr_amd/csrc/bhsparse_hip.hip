@@ -1,6 +1,6 @@
 // bhsparse_hip.hip — libbhsparse_hip.so (see include/bhsparse_hip.h): the handle and its helpers here; the launch helpers,
 // the pipeline, the hand-over of a data set and the C-ABI in bhs_host_{launch,pipeline,setdata,cabi}.inc.h, the masked multiply
-// the sparse add and the entry selection in bhs_host_{masked,add,select}.inc.h (one translation unit).
+// the sparse add, the entry selection and the transpose in bhs_host_{masked,add,select,transpose}.inc.h (one translation unit).
 //
 // Pipeline of one bhs_spgemm() (replaces bhsparse::spgemm_cuda, bhsparse.h:297-339):
 //   stage 1  k_upper_bound (ub per row, nnzCt, symbolic-bin histogram)          <- compute_nnzCt + statistics()
@@ -44,6 +44,7 @@
 #include "bhs_masked.hip.h"
 #include "bhs_add.hip.h"
 #include "bhs_select.hip.h"
+#include "bhs_transpose.hip.h"
 
 #include <algorithm>
 #include <chrono>
@@ -374,6 +375,12 @@ struct bhs_handle {
     hipEvent_t selEv[2] = {nullptr, nullptr};
     unsigned selEpoch = 0;
     long long selDropped = 0;            // bhs_get_info "select_dropped": entries the last bhs_spgemm_select removed
+    // the transpose (bhs_host_transpose.inc.h): buffers of its own as well
+    DevBuf trCtl, trCnt, trCur, trQueue;  // counters; the columns' counts, scanned in place (rowPtrT); the T rows' next free places; per-bin queues of T rows
+    DevBuf trWin, trKeys, trTiles;       // the column window of every workgroup of k_tr_count; the keys (row << 32 | position in X), 8 bytes an entry; its scan's tile words (epoch trEpoch)
+    int* trHost = nullptr;               // pinned mirror of trCtl
+    hipEvent_t trEv[2] = {nullptr, nullptr};
+    unsigned trEpoch = 0;
 };
 
 namespace {
@@ -528,3 +535,4 @@ inline int one_launch(int rc) { return rc != BHS_SUCCESS ? rc : 1; }
 #include "bhs_host_masked.inc.h"
 #include "bhs_host_add.inc.h"
 #include "bhs_host_select.inc.h"
+#include "bhs_host_transpose.inc.h"

@@ -61,6 +61,7 @@ class bhsparse(object):
         self.masked_ms = 0.0
         self.add_ms = 0.0
         self.select_ms = 0.0
+        self.transpose_ms = 0.0
         self.quiet = True
 
     # -- bhsparse.h:91-125 -------------------------------------------------
@@ -329,6 +330,51 @@ class bhsparse(object):
         if err != BHSPARSE_SUCCESS:
             raise BhsparseError("bhs_csr_select_numeric_device", err)
         return Zp, Zj[:nnzZ], (Zx[:nnzZ] if Zx is not None else None)
+
+    # -- extension (not in the reference): the stable transpose and its pattern reuse (include/bhsparse_hip.h, "transpose")
+    def csr_transpose_raw_device(self, m, n, nnzX, d_valX, d_rowPtrX, d_colIndX, d_rowPtrT, d_colIndT, d_valT, d_perm):
+        """bhs_csr_transpose_device: the status code; sets transpose_ms."""
+        if self._h is None:
+            return _lib.BHS_ERR_NOT_READY
+        ms = C.c_double(0)
+        err = self._lib.bhs_csr_transpose_device(self._h, int(m), int(n), int(nnzX), _ptr(d_valX), _ptr(d_rowPtrX), _ptr(d_colIndX),
+                                                 _ptr(d_rowPtrT), _ptr(d_colIndT), _ptr(d_valT), _ptr(d_perm), C.byref(ms))
+        if err == BHSPARSE_SUCCESS:
+            self.transpose_ms = float(ms.value)
+        return err
+
+    def csr_transpose_device(self, m, n, X, values=True, perm=False):
+        """T = X^T on device arrays: X = (rowPtr, colInd, val) torch tensors on this handle's GPU (val may be None: the
+        pattern alone).  Returns (rowPtrT, colIndT, valT, perm) as torch tensors (valT None when values is false or X has
+        none, perm None unless asked for); raises BhsparseError on failure."""
+        import torch
+        torch.cuda.synchronize()                           # the library works on its own stream (see initData_device)
+        Xp, Xj, Xx = X
+        nnz = Xj.numel()
+        Tp = torch.empty(n + 1, dtype=torch.int32, device=Xp.device)
+        Tj = torch.empty(max(nnz, 1), dtype=torch.int32, device=Xp.device)
+        Tx = torch.empty(max(nnz, 1), dtype=Xx.dtype, device=Xp.device) if (values and Xx is not None) else None
+        pm = torch.empty(max(nnz, 1), dtype=torch.int32, device=Xp.device) if perm else None
+        torch.cuda.synchronize()
+        err = self.csr_transpose_raw_device(m, n, nnz, Xx, Xp, Xj, Tp, Tj, Tx, pm)
+        if err != BHSPARSE_SUCCESS:
+            raise BhsparseError("bhs_csr_transpose_device", err)
+        return Tp, Tj[:nnz], (Tx[:nnz] if Tx is not None else None), (pm[:nnz] if pm is not None else None)
+
+    def csr_transpose_values_device(self, d_valX, d_perm, d_valT=None):
+        """valT[q] = valX[perm[q]] on torch tensors of this handle's GPU (bhs_csr_transpose_values_device): the values of a
+        transpose whose pattern is known.  d_valT (made when None) is returned; sets transpose_ms; raises BhsparseError."""
+        import torch
+        nnz = d_perm.numel()
+        if d_valT is None:
+            d_valT = torch.empty(max(nnz, 1), dtype=d_valX.dtype, device=d_valX.device)[:nnz]
+        torch.cuda.synchronize()
+        ms = C.c_double(0)
+        err = self._lib.bhs_csr_transpose_values_device(self._h, int(nnz), _ptr(d_valX), _ptr(d_perm), _ptr(d_valT), C.byref(ms))
+        if err != BHSPARSE_SUCCESS:
+            raise BhsparseError("bhs_csr_transpose_values_device", err)
+        self.transpose_ms = float(ms.value)
+        return d_valT
 
     def get_nnzC(self):
         if self._h is None:
@@ -680,4 +726,79 @@ def spgemm_select_csr(m, k, n, Ap, Aj, Ax, Bp, Bj, Bx, spec, options=None, value
             raise BhsparseError("free_mem", err)
     finally:
         bh.freePlatform()
+    return Cp, Cj, Cx, info
+
+
+def csr_transpose(m, n, Xp, Xj, Xx, value_dtype=np.float64, device=0):
+    """Convenience: T = X^T once on host CSR arrays (X is m x n; rows in any order, duplicates allowed), staged as torch
+    tensors on the handle's device -- the transpose takes device arrays only.  Returns (Tp int32[n+1], Tj int32[nnz],
+    Tx value_dtype[nnz], info) with info["kernels"], info["ms"], info["perm"] (int32[nnz]: the position in X of every entry
+    of T).  Needs no multiply data."""
+    import torch
+    dev = torch.device("cuda", device)
+
+    def up(a, dt):
+        return torch.from_numpy(np.ascontiguousarray(a, dt).copy()).to(dev)
+    X = (up(Xp, np.int32), up(Xj, np.int32), up(Xx, value_dtype))
+    bh = _new_handle(value_dtype, device, None)
+    try:
+        Tp, Tj, Tx, pm = bh.csr_transpose_device(m, n, X, values=True, perm=True)
+        info = {"kernels": bh.kernel_stats(), "ms": bh.transpose_ms, "perm": pm.cpu().numpy()}
+        out = (Tp.cpu().numpy(), Tj.cpu().numpy(), Tx.cpu().numpy(), info)
+    finally:
+        bh.freePlatform()
+    return out
+
+
+def galerkin_csr(m, nc, Pp, Pj, Px, Ap, Aj, Ax, options=None, value_dtype=np.float64, device=0):
+    """Convenience: the Galerkin product C = P^T·(A·P) of an m x m matrix A and an m x nc prolongator P on host CSR
+    arrays, kept on the device between the upload and one get_C: P is transposed there, one handle multiplies A·P, a
+    second one multiplies P^T with the first one's device-resident result (bhs_get_C_device).  Public calls only.
+    Returns (Cp int32[nc+1], Cj, Cx, info); info: "nnzCt_AP", "nnzCt" (products of the two multiplies), "nnzC_AP", "nnzC",
+    "transpose_ms", "ap_ms", "ptap_ms" (device times), "class_state_AP", "class_state", "kernels_AP", "kernels"."""
+    import torch
+    dev = torch.device("cuda", device)
+
+    def up(a, dt):
+        return torch.from_numpy(np.ascontiguousarray(a, dt).copy()).to(dev)
+    P = (up(Pp, np.int32), up(Pj, np.int32), up(Px, value_dtype))
+    A = (up(Ap, np.int32), up(Aj, np.int32), up(Ax, value_dtype))
+    nnzP, nnzA = P[1].numel(), A[1].numel()
+    h1 = _new_handle(value_dtype, device, options)
+    h2 = None
+    try:
+        h2 = _new_handle(value_dtype, device, options)
+        Tp, Tj, Tx, _ = h2.csr_transpose_device(m, nc, P)
+        info = {"transpose_ms": h2.transpose_ms}
+        err = h1.initData_device(m, m, nc, nnzA, A[2], A[0], A[1], nnzP, P[2], P[0], P[1])
+        if err:
+            raise BhsparseError("initData_device(A, P)", err)
+        err = h1.spgemm()
+        if err:
+            raise BhsparseError("spgemm(A·P)", err)
+        nnzAP = h1.get_nnzC()
+        dAPp, dAPj, dAPx = h1.get_C_device()
+        info.update({"nnzCt_AP": h1.nnzCt, "nnzC_AP": nnzAP, "ap_ms": float(sum(h1.stage_ms)), "kernels_AP": h1.kernel_stats(),
+                     "class_state_AP": h1.get_info("class_state")})
+        err = h2.initData_device(nc, m, nc, nnzP, Tx, Tp, Tj, nnzAP, dAPx, dAPp, dAPj)
+        if err:
+            raise BhsparseError("initData_device(P^T, A·P)", err)
+        err = h2.spgemm()
+        if err:
+            raise BhsparseError("spgemm(P^T·AP)", err)
+        nnzC = h2.get_nnzC()
+        Cp = h2.get_rowptrC()
+        Cj = np.empty(nnzC, np.int32)
+        Cx = np.empty(nnzC, value_dtype)
+        err = h2.get_C(Cj, Cx)
+        if err:
+            raise BhsparseError("get_C", err)
+        info.update({"nnzCt": h2.nnzCt, "nnzC": nnzC, "ptap_ms": float(sum(h2.stage_ms)), "kernels": h2.kernel_stats(),
+                     "class_state": h2.get_info("class_state")})
+        h2.free_mem()
+        h1.free_mem()
+    finally:
+        if h2 is not None:
+            h2.freePlatform()
+        h1.freePlatform()
     return Cp, Cj, Cx, info

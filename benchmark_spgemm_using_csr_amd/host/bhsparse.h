@@ -55,6 +55,13 @@ public:
     // initData; get_nnzC / get_C then return the selected C.
     int spgemm_select(const bhs_select &sel);
 
+    // EXTENSION, not part of the reference's API: T = X^T (bhs_csr_transpose_device, include/bhsparse_hip.h, "transpose") on
+    // DEVICE arrays; X is m x n, T's arrays are the caller's (n + 1, nnzX, nnzX entries; d_valX / d_valT / d_perm may be 0).
+    // Needs initPlatform only; does not disturb the data of initData or get_C's result.
+    int csr_transpose_device(int m, int n, int nnzX, const value_type *d_valX, const index_type *d_rowPtrX,
+                             const index_type *d_colIndX, index_type *d_rowPtrT, index_type *d_colIndT, value_type *d_valT,
+                             index_type *d_perm);
+
 private:
     bool       *_spgemm_platform;
     bhs_handle *_h;
@@ -136,6 +143,14 @@ inline int bhsparse::spgemm_select(const bhs_select &sel)
     int err = bhs_spgemm_select(_h, &sel, _h_csrRowPtrC, &nnzCt, &_nnzC, 0);
     if (err == BHSPARSE_SUCCESS) _nnzCt_full = nnzCt;
     return err;
+}
+
+inline int bhsparse::csr_transpose_device(int m, int n, int nnzX, const value_type *d_valX, const index_type *d_rowPtrX,
+                                          const index_type *d_colIndX, index_type *d_rowPtrT, index_type *d_colIndT,
+                                          value_type *d_valT, index_type *d_perm)
+{
+    if (!_h) return BHS_ERR_NOT_READY;
+    return bhs_csr_transpose_device(_h, m, n, nnzX, d_valX, d_rowPtrX, d_colIndX, d_rowPtrT, d_colIndT, d_valT, d_perm, 0);
 }
 
 inline int bhsparse::get_nnzC()

@@ -294,6 +294,49 @@ BHS_API int bhs_spgemm_select_device(bhs_handle *h, const bhs_select *sel,
 BHS_API int bhs_spgemm_select(bhs_handle *h, const bhs_select *sel,
                               int *rowPtrC_out, int64_t *nnzCt_out, int *nnzC_out, double ms_out[2]);
 
+/* ---- transpose ------------------------------------------------------------
+ * T = X^T on CSR (rocSPARSE csr2csc; no reference counterpart), with the permutation that re-values a known pattern
+ * (bhs_transpose.hip.h).  What it is for: the Galerkin product P^T·A·P that ends an AMG setup, A^T·A, symmetrising a
+ * graph (A + A^T: bhs_csr_add_* finishes it), handing a result to a CSC consumer -- T's arrays ARE X in CSC.
+ * X: m x n, 0-based int32 CSR; rows need NOT be ascending, duplicate (row, column) pairs are legal.  T is n x m and
+ * nnz(T) = nnz(X).
+ *
+ * T is the STABLE transpose: the entries of row j of T are the entries of X with column j, in the order of their
+ * position in X's arrays.  The columns of a T row are therefore ascending -- strictly ascending when X has no duplicate
+ * pair, and T is then a legal operand of bhs_csr_add_* and bhs_spgemm_masked.  Values are copied bit for bit (NaN
+ * payloads and -0 included); nothing is computed on them.  The result does not depend on scheduling; in numpy it is
+ *   order = argsort(colIndX, kind="stable"); colIndT = row_of_entry[order]; valT = valX[order]; perm = order;
+ *   rowPtrT = cumsum of bincount(colIndX, minlength=n) with a leading 0.
+ *
+ * bhs_csr_transpose_device
+ *   d_valX     nnzX values, or NULL: the pattern alone (d_valT must then be NULL too)
+ *   d_rowPtrT  n+1 ints, d_colIndT nnzX ints, d_valT nnzX values or NULL, d_perm nnzX ints or NULL: caller-owned device
+ *              arrays that must not overlap X or one another.  d_perm[q] is the position in X of entry q of T.
+ *   ms_out     device time of the whole call, validation included; may be NULL
+ *   X is validated on the device BEFORE anything caller-owned is written: rowPtrX[0] != 0, a decreasing rowPtrX,
+ *   rowPtrX[m] != nnzX or a column outside [0, n) returns BHS_ERR_INVALID_ARG with every output untouched.
+ *   m, n or nnzX may be 0; d_rowPtrT is still written (n+1 zeros when nnzX is 0).  Needs no bound data (works on a handle
+ *   straight after bhs_create); BHS_ERR_INVALID_ARG between bhs_spgemm_symbolic and bhs_spgemm_finish.  Synchronous.
+ * bhs_csr_transpose_values_device: valT[q] = valX[perm[q]] -- the pattern-reuse half.  Where the values of X change and
+ *   its pattern does not (time steps, Newton loops, AMG with fixed coarsening: the reuse workflow of bhs_spgemm_masked)
+ *   transpose once with d_perm, keep rowPtrT / colIndT, and re-value T with this call: 4 bytes of perm and the gathered
+ *   value read, one value written, an entry.  A perm entry outside [0, nnzX) returns BHS_ERR_INVALID_ARG; it is not
+ *   followed: nothing is read out of range (valT may have been written in part).  d_valT must not be d_valX.  Synchronous.
+ * Both calls leave the handle as it was: they use counters, tile words, epoch, events and scratch of their own from the
+ *   grow-only pool (8 bytes an entry of X for the keys, 8 bytes a column); C of the last multiply (every getter,
+ *   bhs_get_C_device's pointers), a sum or selection the getters serve, "class_state", the speculative-launch figures
+ *   and every option stay.  Only bhs_get_kernel_stats now reports the transpose's kernel families: transpose_count
+ *   (validation, the columns' histogram, the T rows' bins), transpose_scan, transpose_scatter, transpose_short (T rows of
+ *   up to 32 entries), transpose_wave (up to 1024), transpose_long; transpose_values after the values call.
+ * Known limit: one T row is put in order by one workgroup.  A column of X with millions of entries (n = 1, a hub column)
+ *   goes through a bitonic network in HBM and is slow; it is correct.                                               */
+BHS_API int bhs_csr_transpose_device(bhs_handle *h, int m, int n, int nnzX,
+                                     const bhs_value_t *d_valX /* may be NULL */, const int *d_rowPtrX, const int *d_colIndX,
+                                     int *d_rowPtrT /* n+1 */, int *d_colIndT /* nnzX */, bhs_value_t *d_valT /* may be NULL */,
+                                     int *d_perm /* may be NULL, nnzX */, double *ms_out /* may be NULL */);
+BHS_API int bhs_csr_transpose_values_device(bhs_handle *h, int nnzX, const bhs_value_t *d_valX,
+                                            const int *d_perm, bhs_value_t *d_valT, double *ms_out);
+
 /* replaces bhsparse::get_nnzC (bhsparse.h: get_nnzC -> bhsparse_cuda::get_nnzC). */
 BHS_API int bhs_get_nnzC(bhs_handle *h, int *nnzC_out);
 
