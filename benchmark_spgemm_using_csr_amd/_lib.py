@@ -39,6 +39,13 @@ class Select(C.Structure):
 
 BHS_SEL_BAND, BHS_SEL_DROP_DIAG, BHS_SEL_KEEP_DIAG, BHS_SEL_ABS, BHS_SEL_REL, BHS_SEL_TOPK = 1, 2, 4, 8, 16, 32
 
+# the semirings of bhs_spgemm_semiring* (include/bhsparse_hip.h, "semiring multiply")
+(BHS_SR_PLUS_TIMES, BHS_SR_MIN_PLUS, BHS_SR_MAX_PLUS, BHS_SR_MAX_TIMES, BHS_SR_MIN_MAX, BHS_SR_MAX_MIN, BHS_SR_OR_AND,
+ BHS_SR_PLUS_PAIR) = range(8)
+SEMIRINGS = {"plus_times": BHS_SR_PLUS_TIMES, "min_plus": BHS_SR_MIN_PLUS, "max_plus": BHS_SR_MAX_PLUS,
+             "max_times": BHS_SR_MAX_TIMES, "min_max": BHS_SR_MIN_MAX, "max_min": BHS_SR_MAX_MIN, "or_and": BHS_SR_OR_AND,
+             "plus_pair": BHS_SR_PLUS_PAIR}
+
 
 # every symbol include/bhsparse_hip.h declares: (restype, argtypes)
 _vp, _i, _i64 = C.c_void_p, C.c_int, C.c_int64
@@ -81,6 +88,9 @@ SYMBOLS = {
     "bhs_spgemm_select": (_i, [_vp, C.POINTER(Select), _vp, C.POINTER(_i64), C.POINTER(_i), C.POINTER(C.c_double)]),
     "bhs_csr_transpose_device": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_double)]),
     "bhs_csr_transpose_values_device": (_i, [_vp, _i, _vp, _vp, _vp, C.POINTER(C.c_double)]),
+    "bhs_spgemm_semiring_masked_device": (_i, [_vp, _i, _vp, _vp, _i, _vp, C.POINTER(_i64), C.POINTER(C.c_double)]),
+    "bhs_spgemm_semiring_masked": (_i, [_vp, _i, _vp, _vp, _i, _vp, C.POINTER(_i64), C.POINTER(C.c_double)]),
+    "bhs_spgemm_semiring": (_i, [_vp, _i, _vp, C.POINTER(_i64), C.POINTER(_i), C.POINTER(C.c_double)]),
     "bhs_strerror": (C.c_char_p, [_i]),
     "bhs_version": (C.c_char_p, []),
 }
@@ -91,7 +101,7 @@ _lib = None
 _libs = {}
 
 
-SOURCES = ("bhsparse_hip.hip", "bhs_host_launch.inc.h", "bhs_host_pipeline.inc.h", "bhs_host_setdata.inc.h", "bhs_host_cabi.inc.h", "bhs_kernels.hip.h", "bhs_row_wg.hip.h", "bhs_row_window.hip.h", "bhs_row_wave.hip.h", "bhs_row_quad.hip.h", "bhs_compress.hip.h", "bhs_row_lane.hip.h", "bhs_sort.hip.h", "bhs_hub.hip.h", "bhs_class.hip.h", "bhs_class_mix.hip.h", "bhs_class_wg.hip.h", "bhs_class_ring.hip.h", "bhs_class_fused.hip.h", "bhs_class_tile.hip.h", "bhs_class_big.hip.h", "bhs_wave.hip.h", "bhs_lab.hip.h", "bhs_masked.hip.h", "bhs_host_masked.inc.h", "bhs_add.hip.h", "bhs_host_add.inc.h", "bhs_select.hip.h", "bhs_host_select.inc.h", "bhs_transpose.hip.h", "bhs_host_transpose.inc.h")
+SOURCES = ("bhsparse_hip.hip", "bhs_host_launch.inc.h", "bhs_host_pipeline.inc.h", "bhs_host_setdata.inc.h", "bhs_host_cabi.inc.h", "bhs_kernels.hip.h", "bhs_row_wg.hip.h", "bhs_row_window.hip.h", "bhs_row_wave.hip.h", "bhs_row_quad.hip.h", "bhs_compress.hip.h", "bhs_row_lane.hip.h", "bhs_sort.hip.h", "bhs_hub.hip.h", "bhs_class.hip.h", "bhs_class_mix.hip.h", "bhs_class_wg.hip.h", "bhs_class_ring.hip.h", "bhs_class_fused.hip.h", "bhs_class_tile.hip.h", "bhs_class_big.hip.h", "bhs_wave.hip.h", "bhs_lab.hip.h", "bhs_masked.hip.h", "bhs_host_masked.inc.h", "bhs_add.hip.h", "bhs_host_add.inc.h", "bhs_select.hip.h", "bhs_host_select.inc.h", "bhs_transpose.hip.h", "bhs_host_transpose.inc.h", "bhs_semiring.hip.h", "bhs_host_semiring.inc.h")
 
 
 def source_digest():

@@ -11,12 +11,62 @@ namespace {
 constexpr int kMaskHubItem = 8192;       // products per part of a hub row (k_masked_hub)
 constexpr int kMaskHubMaxParts = 1024;
 
-int masked_run(bhs_handle* h, const int* dMp, const int* dMj, int nnzM, value_t* dValC, int64_t* nnzCt_out, double* ms_out)
+// What one bin's launch needs: its queue and the operands
+struct MaskLaunch {
+    int nq;
+    const int2* q;
+    const int *Mp, *Mj, *Ap, *Aj;
+    const value_t* Ax;
+    const int *Bp, *Bj;
+    const value_t* Bx;
+    int bSorted;
+    value_t* valC;
+    hipStream_t st;
+};
+
+enum { kMaskFamScan = 0, kMaskFamShort, kMaskFamWave, kMaskFamLong, kMaskFamHub };
+
+// The kernel set of the plus-times masked multiply: the families' names and the launches of the bins.  (The semiring multiply
+// brings a set of its own, bhs_host_semiring.inc.h; mask_drive below is the one driver of both.)
+struct MaskedKernels {
+    static const char* family(int f)
+    {
+        static const char* const names[] = {"masked_scan", "masked_short", "masked_wave", "masked_long", "masked_hub"};
+        return names[f];
+    }
+    template <int G, int CAP, int BLOCK>
+    static void lds(const MaskLaunch& a, unsigned grid)
+    {
+        hipLaunchKernelGGL((k_masked_lds<G, CAP, BLOCK>), dim3(grid), dim3(BLOCK), 0, a.st, a.nq, a.q, a.Mp, a.Mj, a.Ap, a.Aj, a.Ax,
+                           a.Bp, a.Bj, a.Bx, a.bSorted, a.valC);
+    }
+    static void long_rows(const MaskLaunch& a)
+    {
+        hipLaunchKernelGGL(k_masked_long, dim3((unsigned)a.nq), dim3(256), 0, a.st, a.nq, a.q, a.Mp, a.Mj, a.Ap, a.Aj, a.Ax, a.Bp,
+                           a.Bj, a.Bx, a.bSorted, a.valC);
+    }
+    static int hub(const MaskLaunch& a, int parts, unsigned gy, int ldsCap)    // returns the kernels launched
+    {
+        hipLaunchKernelGGL(k_masked_zero, dim3(gy), dim3(256), 0, a.st, a.nq, a.q, a.Mp, a.valC);
+        hipLaunchKernelGGL(k_masked_hub, dim3((unsigned)parts, gy), dim3(256), 0, a.st, a.nq, a.q, a.Mp, a.Mj, a.Ap, a.Aj, a.Ax,
+                           a.Bp, a.Bj, a.Bx, a.bSorted, ldsCap, a.valC);
+        return 2;
+    }
+};
+
+// The driver of a masked multiply with the kernel set K: validation and binning (k_masked_scan), the read-back, one launch
+// block per non-empty bin, the timers.  keepStats: the call follows a multiply whose kernel records (and read-out events) stay.
+template <typename K>
+int mask_drive(bhs_handle* h, const int* dMp, const int* dMj, int nnzM, value_t* dValC, bool keepStats, int64_t* nnzCt_out,
+               double* ms_out)
 {
     const int m = h->m;
     h->ls = h->stream;
-    h->evUsed = 0;
-    for (auto& s : h->stats) { s.launches = 0; s.ms = 0; s.rows = s.products = s.nnz_out = s.nnzA_rows = 0; }
+    if (!keepStats) {
+        h->evUsed = 0;
+        for (auto& s : h->stats) { s.launches = 0; s.ms = 0; s.rows = s.products = s.nnz_out = s.nnzA_rows = 0; }
+    }
+    const size_t evFirst = h->evUsed;
     if (!h->maskEv[0]) {
         BHS_HIP(hipEventCreate(&h->maskEv[0]));
         BHS_HIP(hipEventCreate(&h->maskEv[1]));
@@ -33,12 +83,11 @@ int masked_run(bhs_handle* h, const int* dMp, const int* dMj, int nnzM, value_t*
     spec.waveS = std::min(kMaskWaveTab, cap);
     spec.waveL = cap;
     spec.hubMin = h->maskHubMin;
-    const int bSorted = h->bSorted ? 1 : 0;
 
     BHS_HIP(hipEventRecord(h->maskEv[0], h->stream));
     BHS_HIP(hipMemsetAsync(ctl, 0, sizeof(int) * MS_INTS, h->stream));
     int scanStat = 0;
-    BHS_TRY(timed(h, "masked_scan", m, [&] {
+    BHS_TRY(timed(h, K::family(kMaskFamScan), m, [&] {
         const long long gs = std::max<long long>(1, ((long long)m + kMaskScanRows - 1) / kMaskScanRows);
         hipLaunchKernelGGL(k_masked_scan, dim3((unsigned)gs), dim3(256), 0, h->stream, m, h->n, nnzM, dMp, dMj, h->dAp, h->dAj,
                            h->dBp, spec, ctl, (int2*)h->maskQueue.p);
@@ -56,50 +105,42 @@ int masked_run(bhs_handle* h, const int* dMp, const int* dMj, int nnzM, value_t*
     int count[kMaskBins];
     memcpy(count, hs + MS_COUNT, sizeof(count));
 
-    const int* Mp = dMp;
+    auto bin = [&](int b) {
+        MaskLaunch a = {count[b], queue + (size_t)b * m, dMp, dMj, h->dAp, h->dAj, h->dAx, h->dBp, h->dBj, h->dBx,
+                        h->bSorted ? 1 : 0, dValC, h->stream};
+        return a;
+    };
     int stat = 0;
     if (count[kMaskShort]) {
-        const int nq = count[kMaskShort];
-        BHS_TRY(timed(h, "masked_short", nq, [&] {
-            hipLaunchKernelGGL((k_masked_lds<16, kMaskShortLM, 256>), dim3((unsigned)((nq + 15) / 16)), dim3(256), 0, h->stream, nq,
-                               queue + (size_t)kMaskShort * m, Mp, dMj, h->dAp, h->dAj, h->dAx, h->dBp, h->dBj, h->dBx, bSorted, dValC);
+        const MaskLaunch a = bin(kMaskShort);
+        BHS_TRY(timed(h, K::family(kMaskFamShort), a.nq, [&] {
+            K::template lds<16, kMaskShortLM, 256>(a, (unsigned)((a.nq + 15) / 16));
             return 1;
         }, &stat));
         h->stats[stat].products += (int64_t)sums[kMaskShort];
     }
     if (count[kMaskWaveS] || count[kMaskWaveL]) {
-        const int nS = count[kMaskWaveS], nL = count[kMaskWaveL];
-        BHS_TRY(timed(h, "masked_wave", nS + nL, [&] {
-            if (nS)
-                hipLaunchKernelGGL((k_masked_lds<64, kMaskWaveTab, 256>), dim3((unsigned)((nS + 3) / 4)), dim3(256), 0, h->stream, nS,
-                                   queue + (size_t)kMaskWaveS * m, Mp, dMj, h->dAp, h->dAj, h->dAx, h->dBp, h->dBj, h->dBx, bSorted, dValC);
-            if (nL)
-                hipLaunchKernelGGL((k_masked_lds<64, kMaskHubLds, 64>), dim3((unsigned)nL), dim3(64), 0, h->stream, nL,
-                                   queue + (size_t)kMaskWaveL * m, Mp, dMj, h->dAp, h->dAj, h->dAx, h->dBp, h->dBj, h->dBx, bSorted, dValC);
-            return (nS ? 1 : 0) + (nL ? 1 : 0);
+        const MaskLaunch aS = bin(kMaskWaveS), aL = bin(kMaskWaveL);
+        BHS_TRY(timed(h, K::family(kMaskFamWave), aS.nq + aL.nq, [&] {
+            if (aS.nq) K::template lds<64, kMaskWaveTab, 256>(aS, (unsigned)((aS.nq + 3) / 4));
+            if (aL.nq) K::template lds<64, kMaskHubLds, 64>(aL, (unsigned)aL.nq);
+            return (aS.nq ? 1 : 0) + (aL.nq ? 1 : 0);
         }, &stat));
         h->stats[stat].products += (int64_t)(sums[kMaskWaveS] + sums[kMaskWaveL]);
     }
     if (count[kMaskLong]) {
-        const int nq = count[kMaskLong];
-        BHS_TRY(timed(h, "masked_long", nq, [&] {
-            hipLaunchKernelGGL(k_masked_long, dim3((unsigned)nq), dim3(256), 0, h->stream, nq, queue + (size_t)kMaskLong * m, Mp,
-                               dMj, h->dAp, h->dAj, h->dAx, h->dBp, h->dBj, h->dBx, bSorted, dValC);
+        const MaskLaunch a = bin(kMaskLong);
+        BHS_TRY(timed(h, K::family(kMaskFamLong), a.nq, [&] {
+            K::long_rows(a);
             return 1;
         }, &stat));
         h->stats[stat].products += (int64_t)sums[kMaskLong];
     }
     if (count[kMaskHub]) {
-        const int nq = count[kMaskHub];
+        const MaskLaunch a = bin(kMaskHub);
         const int parts = (int)std::max<unsigned long long>(1, std::min<unsigned long long>(kMaskHubMaxParts, (hubMax + kMaskHubItem - 1) / kMaskHubItem));
-        const unsigned gy = (unsigned)std::min(nq, 65535);
-        BHS_TRY(timed(h, "masked_hub", nq, [&] {
-            const int2* q = queue + (size_t)kMaskHub * m;
-            hipLaunchKernelGGL(k_masked_zero, dim3(gy), dim3(256), 0, h->stream, nq, q, Mp, dValC);
-            hipLaunchKernelGGL(k_masked_hub, dim3((unsigned)parts, gy), dim3(256), 0, h->stream, nq, q, Mp, dMj, h->dAp, h->dAj,
-                               h->dAx, h->dBp, h->dBj, h->dBx, bSorted, std::min(kMaskHubLds, cap), dValC);
-            return 2;
-        }, &stat));
+        const unsigned gy = (unsigned)std::min(a.nq, 65535);
+        BHS_TRY(timed(h, K::family(kMaskFamHub), a.nq, [&] { return K::hub(a, parts, gy, std::min(kMaskHubLds, cap)); }, &stat));
         h->stats[stat].products += (int64_t)sums[kMaskHub];
     }
     BHS_HIP(hipEventRecord(h->maskEv[1], h->stream));
@@ -110,12 +151,17 @@ int masked_run(bhs_handle* h, const int* dMp, const int* dMj, int nnzM, value_t*
         BHS_HIP(hipEventElapsedTime(&ms, h->maskEv[0], h->maskEv[1]));
         *ms_out = ms;
     }
-    for (size_t i = 0; i < h->evUsed; ++i) {
+    for (size_t i = evFirst; i < h->evUsed; ++i) {
         float ms = 0;
         BHS_HIP(hipEventElapsedTime(&ms, h->evPool[i].a, h->evPool[i].b));
         h->stats[h->evPool[i].stat].ms += ms;
     }
     return BHS_SUCCESS;
+}
+
+int masked_run(bhs_handle* h, const int* dMp, const int* dMj, int nnzM, value_t* dValC, int64_t* nnzCt_out, double* ms_out)
+{
+    return mask_drive<MaskedKernels>(h, dMp, dMj, nnzM, dValC, false, nnzCt_out, ms_out);
 }
 
 // after a failed call: nothing of it stays queued (the pipeline's own state is not touched)

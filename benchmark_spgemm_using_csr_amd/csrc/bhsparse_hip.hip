@@ -1,6 +1,7 @@
 // bhsparse_hip.hip — libbhsparse_hip.so (see include/bhsparse_hip.h): the handle and its helpers here; the launch helpers,
 // the pipeline, the hand-over of a data set and the C-ABI in bhs_host_{launch,pipeline,setdata,cabi}.inc.h, the masked multiply
-// the sparse add, the entry selection and the transpose in bhs_host_{masked,add,select,transpose}.inc.h (one translation unit).
+// the sparse add, the entry selection, the transpose and the semiring multiply in
+// bhs_host_{masked,add,select,transpose,semiring}.inc.h (one translation unit).
 //
 // Pipeline of one bhs_spgemm() (replaces bhsparse::spgemm_cuda, bhsparse.h:297-339):
 //   stage 1  k_upper_bound (ub per row, nnzCt, symbolic-bin histogram)          <- compute_nnzCt + statistics()
@@ -536,3 +537,4 @@ inline int one_launch(int rc) { return rc != BHS_SUCCESS ? rc : 1; }
 #include "bhs_host_add.inc.h"
 #include "bhs_host_select.inc.h"
 #include "bhs_host_transpose.inc.h"
+#include "bhs_host_semiring.inc.h"

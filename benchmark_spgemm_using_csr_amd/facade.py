@@ -62,6 +62,8 @@ class bhsparse(object):
         self.add_ms = 0.0
         self.select_ms = 0.0
         self.transpose_ms = 0.0
+        self.semiring_ms = 0.0
+        self.multiply_ms = 0.0
         self.quiet = True
 
     # -- bhsparse.h:91-125 -------------------------------------------------
@@ -376,6 +378,63 @@ class bhsparse(object):
         self.transpose_ms = float(ms.value)
         return d_valT
 
+    # -- extension (not in the reference): the multiply over a semiring (include/bhsparse_hip.h, "semiring multiply")
+    def spgemm_semiring(self, semiring):
+        """C = A (+).(x) B on the data of initData; semiring: a _lib.BHS_SR_* constant.  The ordinary multiply, then its C
+        re-valued in place.  Returns the status code like spgemm(); fills the csrRowPtrC given to initData and sets nnzCt,
+        nnzC, time_ms, multiply_ms (device time of the multiply) and semiring_ms (device time of the re-valuation).
+        get_nnzC / get_C / get_rowptrC / get_C_device then return the semiring's values."""
+        if self._h is None:
+            return _lib.BHS_ERR_NOT_READY
+        import time
+        nnzCt, nnzC = C.c_int64(0), C.c_int(0)
+        ms = (C.c_double * 2)()
+        t0 = time.perf_counter()
+        err = self._lib.bhs_spgemm_semiring(self._h, int(semiring), _ptr(self._rowptrC), C.byref(nnzCt), C.byref(nnzC), ms)
+        self.time_ms = (time.perf_counter() - t0) * 1e3
+        if err == BHSPARSE_SUCCESS:
+            self.nnzCt, self.nnzC, self.semiring_ms = int(nnzCt.value), int(nnzC.value), float(ms[1])
+            self.multiply_ms = float(ms[0])
+        return err
+
+    def spgemm_semiring_masked(self, semiring, rowPtrM, colIndM, valC=None):
+        """spgemm_masked over a semiring: valC[p] = the (+)-reduction of A(i,k) (x) B(k, colIndM[p]) for every entry p of row i
+        of the pattern M, the (+)-identity where no product lands.  Returns valC (allocated when None); raises BhsparseError
+        (an invalid M or an unknown semiring: code BHS_ERR_INVALID_ARG, valC untouched).  Sets nnzCt and semiring_ms."""
+        if self._h is None:
+            raise BhsparseError("bhs_spgemm_semiring_masked", _lib.BHS_ERR_NOT_READY)
+        rowPtrM = np.ascontiguousarray(rowPtrM, np.int32)
+        colIndM = np.ascontiguousarray(colIndM, np.int32)
+        if rowPtrM.size < self._m + 1:
+            raise BhsparseError("bhs_spgemm_semiring_masked", _lib.BHS_ERR_INVALID_ARG)
+        nnzM = colIndM.size
+        if valC is None:
+            valC = np.empty(nnzM, self._vdt)
+        elif not (isinstance(valC, np.ndarray) and valC.dtype == self._vdt and valC.size >= nnzM and valC.flags.c_contiguous):
+            raise BhsparseError("bhs_spgemm_semiring_masked", _lib.BHS_ERR_INVALID_ARG)
+        nnzCt, ms = C.c_int64(0), C.c_double(0)
+        err = self._lib.bhs_spgemm_semiring_masked(self._h, int(semiring), _ptr(rowPtrM), _ptr(colIndM) if nnzM else None, nnzM,
+                                                   _ptr(valC) if nnzM else None, C.byref(nnzCt), C.byref(ms))
+        if err != BHSPARSE_SUCCESS:
+            raise BhsparseError("bhs_spgemm_semiring_masked", err)
+        self.nnzCt, self.semiring_ms = int(nnzCt.value), float(ms.value)
+        return valC
+
+    def spgemm_semiring_masked_device(self, semiring, d_rowPtrM, d_colIndM, nnzM, d_valC):
+        """The same on device arrays (torch tensors on this handle's GPU, or raw device addresses); valC is written in
+        place.  Returns the status code (0 on success) and sets nnzCt / semiring_ms."""
+        if self._h is None:
+            return _lib.BHS_ERR_NOT_READY
+        if any(hasattr(t, "is_cuda") and t.is_cuda for t in (d_rowPtrM, d_colIndM, d_valC)):
+            import torch
+            torch.cuda.synchronize()                       # the library works on its own stream (see initData_device)
+        nnzCt, ms = C.c_int64(0), C.c_double(0)
+        err = self._lib.bhs_spgemm_semiring_masked_device(self._h, int(semiring), _ptr(d_rowPtrM), _ptr(d_colIndM), int(nnzM),
+                                                          _ptr(d_valC), C.byref(nnzCt), C.byref(ms))
+        if err == BHSPARSE_SUCCESS:
+            self.nnzCt, self.semiring_ms = int(nnzCt.value), float(ms.value)
+        return err
+
     def get_nnzC(self):
         if self._h is None:
             return 0
@@ -574,6 +633,60 @@ def spgemm_masked_csr(m, k, n, Ap, Aj, Ax, Bp, Bj, Bx, Mp, Mj, options=None, val
             raise BhsparseError("initData", err)
         valC = bh.spgemm_masked(Mp, Mj)
         info = {"nnzCt": bh.nnzCt, "ms": bh.masked_ms, "kernels": bh.kernel_stats()}
+        err = bh.free_mem()
+        if err:
+            raise BhsparseError("free_mem", err)
+    finally:
+        bh.freePlatform()
+    return valC, info
+
+
+def spgemm_semiring_csr(m, k, n, Ap, Aj, Ax, Bp, Bj, Bx, semiring, options=None, value_dtype=np.float64, device=0):
+    """Convenience: C = A (+).(x) B once on host CSR arrays.  Returns (rowPtrC, colIndC, valC, info)."""
+    bh = _new_handle(value_dtype, device, options)
+    try:
+        Ap, Aj, Ax = (np.ascontiguousarray(Ap, np.int32), np.ascontiguousarray(Aj, np.int32),
+                      np.ascontiguousarray(Ax, value_dtype))
+        Bp, Bj, Bx = (np.ascontiguousarray(Bp, np.int32), np.ascontiguousarray(Bj, np.int32),
+                      np.ascontiguousarray(Bx, value_dtype))
+        Cp = np.zeros(m + 1, np.int32)
+        err = bh.initData(m, k, n, len(Aj), Ax, Ap, Aj, len(Bj), Bx, Bp, Bj, Cp)
+        if err:
+            raise BhsparseError("initData", err)
+        err = bh.spgemm_semiring(semiring)
+        if err:
+            raise BhsparseError("bhs_spgemm_semiring", err)
+        nnzC = bh.get_nnzC()
+        Cj = np.empty(nnzC, np.int32)
+        Cx = np.empty(nnzC, value_dtype)
+        err = bh.get_C(Cj, Cx)
+        if err:
+            raise BhsparseError("get_C", err)
+        info = {"nnzCt": bh.nnzCt, "nnzC": nnzC, "semiring_ms": bh.semiring_ms, "multiply_ms": bh.multiply_ms,
+                "time_ms": bh.time_ms, "kernels": bh.kernel_stats(), "class_state": bh.get_info("class_state")}
+        err = bh.free_mem()
+        if err:
+            raise BhsparseError("free_mem", err)
+    finally:
+        bh.freePlatform()
+    return Cp, Cj, Cx, info
+
+
+def spgemm_semiring_masked_csr(m, k, n, Ap, Aj, Ax, Bp, Bj, Bx, Mp, Mj, semiring, options=None, value_dtype=np.float64,
+                               device=0):
+    """Convenience: the masked multiply over a semiring once on host CSR arrays.  Returns (valC value_dtype[nnzM], info);
+    the result's pattern is the caller's (Mp, Mj)."""
+    bh = _new_handle(value_dtype, device, options)
+    try:
+        Ap, Aj, Ax = (np.ascontiguousarray(Ap, np.int32), np.ascontiguousarray(Aj, np.int32),
+                      np.ascontiguousarray(Ax, value_dtype))
+        Bp, Bj, Bx = (np.ascontiguousarray(Bp, np.int32), np.ascontiguousarray(Bj, np.int32),
+                      np.ascontiguousarray(Bx, value_dtype))
+        err = bh.initData(m, k, n, len(Aj), Ax, Ap, Aj, len(Bj), Bx, Bp, Bj, None)
+        if err:
+            raise BhsparseError("initData", err)
+        valC = bh.spgemm_semiring_masked(semiring, Mp, Mj)
+        info = {"nnzCt": bh.nnzCt, "ms": bh.semiring_ms, "kernels": bh.kernel_stats()}
         err = bh.free_mem()
         if err:
             raise BhsparseError("free_mem", err)

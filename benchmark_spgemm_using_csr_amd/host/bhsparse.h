@@ -62,6 +62,13 @@ public:
                              const index_type *d_colIndX, index_type *d_rowPtrT, index_type *d_colIndT, value_type *d_valT,
                              index_type *d_perm);
 
+    // EXTENSION, not part of the reference's API: the multiply over a semiring (bhs_spgemm_semiring*, include/bhsparse_hip.h,
+    // "semiring multiply"; semiring: a BHS_SR_* constant) on the data of initData.  spgemm_semiring is the full product: it
+    // fills the csrRowPtrC of initData, and get_nnzC / get_C then return A (+).(x) B on the pattern of A·B.
+    // spgemm_semiring_masked is spgemm_masked over the semiring: an entry of M no product lands on reads the (+)-identity.
+    int spgemm_semiring(int semiring);
+    int spgemm_semiring_masked(int semiring, int *csrRowPtrM, int *csrColIndM, int nnzM, value_type *csrValC);
+
 private:
     bool       *_spgemm_platform;
     bhs_handle *_h;
@@ -143,6 +150,21 @@ inline int bhsparse::spgemm_select(const bhs_select &sel)
     int err = bhs_spgemm_select(_h, &sel, _h_csrRowPtrC, &nnzCt, &_nnzC, 0);
     if (err == BHSPARSE_SUCCESS) _nnzCt_full = nnzCt;
     return err;
+}
+
+inline int bhsparse::spgemm_semiring(int semiring)
+{
+    if (!_h) return BHS_ERR_NOT_READY;
+    int64_t nnzCt = 0;
+    int err = bhs_spgemm_semiring(_h, semiring, _h_csrRowPtrC, &nnzCt, &_nnzC, 0);
+    if (err == BHSPARSE_SUCCESS) _nnzCt_full = nnzCt;
+    return err;
+}
+
+inline int bhsparse::spgemm_semiring_masked(int semiring, int *csrRowPtrM, int *csrColIndM, int nnzM, value_type *csrValC)
+{
+    if (!_h) return BHS_ERR_NOT_READY;
+    return bhs_spgemm_semiring_masked(_h, semiring, csrRowPtrM, csrColIndM, nnzM, csrValC, 0, 0);
 }
 
 inline int bhsparse::csr_transpose_device(int m, int n, int nnzX, const value_type *d_valX, const index_type *d_rowPtrX,

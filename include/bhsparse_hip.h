@@ -337,6 +337,73 @@ BHS_API int bhs_csr_transpose_device(bhs_handle *h, int m, int n, int nnzX,
 BHS_API int bhs_csr_transpose_values_device(bhs_handle *h, int nnzX, const bhs_value_t *d_valX,
                                             const int *d_perm, bhs_value_t *d_valT, double *ms_out);
 
+/* ---- semiring multiply ----------------------------------------------------
+ * C<M> = A (+).(x) B and C = A (+).(x) B over a semiring other than plus-times (GraphBLAS mxm; no reference counterpart):
+ * one relaxation step of all-pairs shortest paths (MIN_PLUS), widest / bottleneck paths (MAX_MIN, MIN_MAX), most
+ * reliable paths (MAX_TIMES), reachability and BFS frontiers (OR_AND), structural triangle counting that never reads a
+ * value (PLUS_PAIR).  Kernels: bhs_semiring.hip.h -- the masked multiply's, with the product and the reduction made
+ * parameters.
+ *
+ * The rule.  For an entry (i, j) of the result, with a = A(i,k) and b = B(k,j), both converted to double, over every k
+ * for which both are entries:
+ *     semiring            product (x)                      reduction (+)   (+)-identity
+ *     BHS_SR_PLUS_TIMES   a * b                            +               0
+ *     BHS_SR_MIN_PLUS     a + b                            min             +Inf
+ *     BHS_SR_MAX_PLUS     a + b                            max             -Inf
+ *     BHS_SR_MAX_TIMES    a * b                            max             -Inf
+ *     BHS_SR_MIN_MAX      max(a, b)                        min             +Inf
+ *     BHS_SR_MAX_MIN      min(a, b)                        max             -Inf
+ *     BHS_SR_OR_AND       (a != 0 and b != 0) ? 1 : 0      or              0
+ *     BHS_SR_PLUS_PAIR    1 (values not read)              +               0
+ *   Order of min and max, as (+) and as (x): the order of the values as numbers, with -0 below +0.
+ *   NaN: a product that is NaN makes its entry NaN -- NaN propagates, it is not skipped.  That covers a NaN operand (of
+ *     max(a, b) / min(a, b) too), Inf - Inf in the *_PLUS semirings and 0 * Inf in MAX_TIMES.  Which NaN comes out is not
+ *     specified.
+ *   OR_AND treats NaN as non-zero (NaN != 0); -0 is zero.
+ *   Arithmetic: products and the reduction in double, ONE rounding to bhs_value_t per entry.  Rounding is monotone, so
+ *     reducing rounded products gives the same bits: the float build's long and hub bins reduce floats in valC.
+ *   PLUS_PAIR counts in integers and converts once: exact up to 2^53 in the double build, 2^24 in the float build.
+ *   min, max and or do not depend on the order of their operands: unlike the plus-times kernels, results are bit for bit
+ *     the same from run to run on any input, in every bin.
+ *   PLUS_TIMES is accepted everywhere and forwards to the existing call (bhs_spgemm_masked[_device] / bhs_spgemm); it runs no
+ *     new kernel.  A caller can hold the semiring in a variable.
+ *
+ * bhs_spgemm_semiring_masked[_device]: C<M> = A (+).(x) B.  The contract of bhs_spgemm_masked[_device], word for word: the
+ *   preconditions on M and its validation on the device (an invalid M returns BHS_ERR_INVALID_ARG with valC untouched), the
+ *   refusals (BHS_ERR_NOT_READY without data, BHS_ERR_INVALID_ARG between bhs_spgemm_symbolic and bhs_spgemm_finish), the
+ *   handle left as it was, the "b_sorted" rejections, the tunables "masked_max_table_log2" and "masked_hub_min_products".
+ *   Two differences: an entry of M that no product lands on reads the (+)-identity of the table above (+Inf for MIN_PLUS),
+ *   and an unknown semiring returns BHS_ERR_INVALID_ARG.  bhs_get_kernel_stats then reports the families sr_scan,
+ *   sr_short, sr_wave, sr_long and sr_hub.
+ * bhs_spgemm_semiring: the full product.  The pattern of A (+).(x) B is the structural pattern of A·B for every semiring,
+ *   and bhs_spgemm keeps computed zeros, so its C already has that pattern.  The call (1) checks the semiring before
+ *   anything is started -- an unknown one returns BHS_ERR_INVALID_ARG and leaves the last C as it was --, (2) runs the
+ *   ordinary bhs_spgemm (every option, path, precondition and speculative launch as ever), (3) re-values that C IN PLACE
+ *   with the masked semiring kernels, M = C's own device arrays: no second set of arrays, no column rewritten, the
+ *   pipeline's arrays not moved.  The plus-times values of step 2 are computed and then thrown away: a pattern-only pass
+ *   through the pipeline does not exist yet.  Afterwards bhs_get_nnzC / bhs_get_C / bhs_get_rowptrC / bhs_get_C_device
+ *   serve the semiring's values; rowPtrC_out / nnzCt_out / nnzC_out as in bhs_spgemm; ms_out[2] (may be NULL): device time
+ *   of the multiply, of the re-valuation (the Python mirror keeps them as multiply_ms and semiring_ms).
+ *   bhs_get_kernel_stats reports the sr_ families beside the multiply's.
+ *   BHS_ERR_INVALID_ARG while output arrays are bound with bhs_set_output_device and between bhs_spgemm_symbolic and
+ *   bhs_spgemm_finish (as bhs_spgemm_add); BHS_ERR_NOT_READY without data.                                            */
+enum {
+  BHS_SR_PLUS_TIMES = 0,
+  BHS_SR_MIN_PLUS   = 1,
+  BHS_SR_MAX_PLUS   = 2,
+  BHS_SR_MAX_TIMES  = 3,
+  BHS_SR_MIN_MAX    = 4,
+  BHS_SR_MAX_MIN    = 5,
+  BHS_SR_OR_AND     = 6,
+  BHS_SR_PLUS_PAIR  = 7
+};
+BHS_API int bhs_spgemm_semiring_masked_device(bhs_handle *h, int semiring, const int *d_rowPtrM, const int *d_colIndM, int nnzM,
+                                              bhs_value_t *d_valC, int64_t *nnzCt_out, double *ms_out);
+BHS_API int bhs_spgemm_semiring_masked(bhs_handle *h, int semiring, const int *rowPtrM, const int *colIndM, int nnzM,
+                                       bhs_value_t *valC, int64_t *nnzCt_out, double *ms_out);   /* host arrays, copied */
+BHS_API int bhs_spgemm_semiring(bhs_handle *h, int semiring, int *rowPtrC_out, int64_t *nnzCt_out, int *nnzC_out,
+                                double ms_out[2]);
+
 /* replaces bhsparse::get_nnzC (bhsparse.h: get_nnzC -> bhsparse_cuda::get_nnzC). */
 BHS_API int bhs_get_nnzC(bhs_handle *h, int *nnzC_out);
 
