@@ -91,6 +91,9 @@ SYMBOLS = {
     "bhs_spgemm_semiring_masked_device": (_i, [_vp, _i, _vp, _vp, _i, _vp, C.POINTER(_i64), C.POINTER(C.c_double)]),
     "bhs_spgemm_semiring_masked": (_i, [_vp, _i, _vp, _vp, _i, _vp, C.POINTER(_i64), C.POINTER(C.c_double)]),
     "bhs_spgemm_semiring": (_i, [_vp, _i, _vp, C.POINTER(_i64), C.POINTER(_i), C.POINTER(C.c_double)]),
+    "bhs_csr_extract_symbolic_device": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, C.POINTER(_i)]),
+    "bhs_csr_extract_numeric_device": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp,
+                                            C.POINTER(C.c_double)]),
     "bhs_strerror": (C.c_char_p, [_i]),
     "bhs_version": (C.c_char_p, []),
 }
@@ -101,7 +104,7 @@ _lib = None
 _libs = {}
 
 
-SOURCES = ("bhsparse_hip.hip", "bhs_host_launch.inc.h", "bhs_host_pipeline.inc.h", "bhs_host_setdata.inc.h", "bhs_host_cabi.inc.h", "bhs_kernels.hip.h", "bhs_row_wg.hip.h", "bhs_row_window.hip.h", "bhs_row_wave.hip.h", "bhs_row_quad.hip.h", "bhs_compress.hip.h", "bhs_row_lane.hip.h", "bhs_sort.hip.h", "bhs_hub.hip.h", "bhs_class.hip.h", "bhs_class_mix.hip.h", "bhs_class_wg.hip.h", "bhs_class_ring.hip.h", "bhs_class_fused.hip.h", "bhs_class_tile.hip.h", "bhs_class_big.hip.h", "bhs_wave.hip.h", "bhs_lab.hip.h", "bhs_masked.hip.h", "bhs_host_masked.inc.h", "bhs_add.hip.h", "bhs_host_add.inc.h", "bhs_select.hip.h", "bhs_host_select.inc.h", "bhs_transpose.hip.h", "bhs_host_transpose.inc.h", "bhs_semiring.hip.h", "bhs_host_semiring.inc.h")
+SOURCES = ("bhsparse_hip.hip", "bhs_host_launch.inc.h", "bhs_host_pipeline.inc.h", "bhs_host_setdata.inc.h", "bhs_host_cabi.inc.h", "bhs_kernels.hip.h", "bhs_row_wg.hip.h", "bhs_row_window.hip.h", "bhs_row_wave.hip.h", "bhs_row_quad.hip.h", "bhs_compress.hip.h", "bhs_row_lane.hip.h", "bhs_sort.hip.h", "bhs_hub.hip.h", "bhs_class.hip.h", "bhs_class_mix.hip.h", "bhs_class_wg.hip.h", "bhs_class_ring.hip.h", "bhs_class_fused.hip.h", "bhs_class_tile.hip.h", "bhs_class_big.hip.h", "bhs_wave.hip.h", "bhs_lab.hip.h", "bhs_masked.hip.h", "bhs_host_masked.inc.h", "bhs_add.hip.h", "bhs_host_add.inc.h", "bhs_select.hip.h", "bhs_host_select.inc.h", "bhs_transpose.hip.h", "bhs_host_transpose.inc.h", "bhs_semiring.hip.h", "bhs_host_semiring.inc.h", "bhs_extract.hip.h", "bhs_host_extract.inc.h")
 
 
 def source_digest():

@@ -123,6 +123,9 @@ int bhs_destroy(bhs_handle* h)
     release(h->trCtl); release(h->trCnt); release(h->trCur); release(h->trQueue); release(h->trWin); release(h->trKeys); release(h->trTiles);
     if (h->trHost) (void)hipHostFree(h->trHost);
     for (int i = 0; i < 2; ++i) if (h->trEv[i]) (void)hipEventDestroy(h->trEv[i]);
+    release(h->exCtl); release(h->exCnt); release(h->exQueue); release(h->exInv); release(h->exKeys); release(h->exTiles);
+    if (h->exHost) (void)hipHostFree(h->exHost);
+    for (int i = 0; i < 2; ++i) if (h->exEv[i]) (void)hipEventDestroy(h->exEv[i]);
     if (h->addHost) (void)hipHostFree(h->addHost);
     for (int i = 0; i < 2; ++i) if (h->addEv[i]) (void)hipEventDestroy(h->addEv[i]);
     if (h->maskHost) (void)hipHostFree(h->maskHost);
@@ -486,6 +489,7 @@ int bhs_set_option(bhs_handle* h, const char* key, int64_t value)
 int bhs_get_info(bhs_handle* h, const char* key, int64_t* value_out)
 {
     if (!h || !key || !value_out) return BHS_ERR_INVALID_ARG;
+    if (!strcmp(key, "extract_reordered_rows")) { *value_out = h->exReordered; return BHS_SUCCESS; }   // Z rows the last bhs_csr_extract_numeric_device had to put in order (needs no bound data, as the call itself)
     if (!h->hasData) return BHS_ERR_NOT_READY;
     if (!strcmp(key, "b_sorted")) { *value_out = h->bSorted; return BHS_SUCCESS; }
     if (!strcmp(key, "span_words")) { *value_out = h->ps.spanWPL; return BHS_SUCCESS; }   // bitmap words per lane of the last multiply's span kernels (0: hash kernels)

@@ -1,7 +1,7 @@
 // bhsparse_hip.hip — libbhsparse_hip.so (see include/bhsparse_hip.h): the handle and its helpers here; the launch helpers,
 // the pipeline, the hand-over of a data set and the C-ABI in bhs_host_{launch,pipeline,setdata,cabi}.inc.h, the masked multiply
-// the sparse add, the entry selection, the transpose and the semiring multiply in
-// bhs_host_{masked,add,select,transpose,semiring}.inc.h (one translation unit).
+// the sparse add, the entry selection, the transpose, the semiring multiply and the extraction in
+// bhs_host_{masked,add,select,transpose,semiring,extract}.inc.h (one translation unit).
 //
 // Pipeline of one bhs_spgemm() (replaces bhsparse::spgemm_cuda, bhsparse.h:297-339):
 //   stage 1  k_upper_bound (ub per row, nnzCt, symbolic-bin histogram)          <- compute_nnzCt + statistics()
@@ -382,6 +382,13 @@ struct bhs_handle {
     int* trHost = nullptr;               // pinned mirror of trCtl
     hipEvent_t trEv[2] = {nullptr, nullptr};
     unsigned trEpoch = 0;
+    // the extraction (bhs_host_extract.inc.h): buffers of its own as well
+    DevBuf exCtl, exCnt, exQueue, exInv;  // counters; the Z rows' counts, scanned in place (rowPtrZ); per-bin queues of Z rows; the inverse column map, n ints
+    DevBuf exKeys, exTiles;              // the keys (place << 32 | position in X) of Z rows beyond the LDS, 8 bytes an entry of Z, only where such rows exist; its scan's tile words (epoch exEpoch)
+    int* exHost = nullptr;               // pinned mirror of exCtl
+    hipEvent_t exEv[2] = {nullptr, nullptr};
+    unsigned exEpoch = 0;
+    long long exReordered = 0;           // bhs_get_info "extract_reordered_rows": Z rows the last numeric call had to put in order
 };
 
 namespace {
@@ -538,3 +545,4 @@ inline int one_launch(int rc) { return rc != BHS_SUCCESS ? rc : 1; }
 #include "bhs_host_select.inc.h"
 #include "bhs_host_transpose.inc.h"
 #include "bhs_host_semiring.inc.h"
+#include "bhs_host_extract.inc.h"

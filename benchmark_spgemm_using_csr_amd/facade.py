@@ -62,6 +62,7 @@ class bhsparse(object):
         self.add_ms = 0.0
         self.select_ms = 0.0
         self.transpose_ms = 0.0
+        self.extract_ms = 0.0
         self.semiring_ms = 0.0
         self.multiply_ms = 0.0
         self.quiet = True
@@ -377,6 +378,74 @@ class bhsparse(object):
             raise BhsparseError("bhs_csr_transpose_values_device", err)
         self.transpose_ms = float(ms.value)
         return d_valT
+
+    # -- extension (not in the reference): Z = X(rows, cols) (include/bhsparse_hip.h, "extract")
+    @staticmethod
+    def _index_list(a):
+        """An index list for the C-ABI, where NULL means "all": an EMPTY torch tensor (whose data pointer is null) is stood in
+        for by a one-element tensor, so that the call sees an empty list."""
+        if a is not None and hasattr(a, "numel") and a.numel() == 0:
+            return a.new_empty(1)
+        return a
+
+    def csr_extract_symbolic_device(self, m, n, nnzX, d_rowPtrX, d_colIndX, mI, d_rows, nJ, d_cols, d_rowPtrZ):
+        """bhs_csr_extract_symbolic_device: (status, nnz(Z)); d_rowPtrZ (mI+1 ints on the device) is written."""
+        if self._h is None:
+            return _lib.BHS_ERR_NOT_READY, 0
+        d_rows, d_cols = self._index_list(d_rows), self._index_list(d_cols)
+        nnzZ = C.c_int(0)
+        err = self._lib.bhs_csr_extract_symbolic_device(self._h, int(m), int(n), int(nnzX), _ptr(d_rowPtrX), _ptr(d_colIndX),
+                                                        int(mI), _ptr(d_rows), int(nJ), _ptr(d_cols), _ptr(d_rowPtrZ),
+                                                        C.byref(nnzZ))
+        return err, int(nnzZ.value)
+
+    def csr_extract_numeric_device(self, m, n, nnzX, d_valX, d_rowPtrX, d_colIndX, mI, d_rows, nJ, d_cols, nnzZ, d_rowPtrZ,
+                                   d_colIndZ, d_valZ, d_perm):
+        """bhs_csr_extract_numeric_device: the status code; sets extract_ms."""
+        if self._h is None:
+            return _lib.BHS_ERR_NOT_READY
+        d_rows, d_cols = self._index_list(d_rows), self._index_list(d_cols)
+        ms = C.c_double(0)
+        err = self._lib.bhs_csr_extract_numeric_device(self._h, int(m), int(n), int(nnzX), _ptr(d_valX), _ptr(d_rowPtrX),
+                                                       _ptr(d_colIndX), int(mI), _ptr(d_rows), int(nJ), _ptr(d_cols), int(nnzZ),
+                                                       _ptr(d_rowPtrZ), _ptr(d_colIndZ), _ptr(d_valZ), _ptr(d_perm), C.byref(ms))
+        if err == BHSPARSE_SUCCESS:
+            self.extract_ms = float(ms.value)
+        return err
+
+    def csr_extract_raw_device(self, m, n, nnzX, d_valX, d_rowPtrX, d_colIndX, mI, d_rows, nJ, d_cols, d_rowPtrZ, d_colIndZ,
+                               d_valZ, d_perm):
+        """Both calls on caller-given arrays: (status, nnz(Z)); the numeric call runs only where the symbolic one succeeds."""
+        err, nnzZ = self.csr_extract_symbolic_device(m, n, nnzX, d_rowPtrX, d_colIndX, mI, d_rows, nJ, d_cols, d_rowPtrZ)
+        if err != BHSPARSE_SUCCESS:
+            return err, 0
+        err = self.csr_extract_numeric_device(m, n, nnzX, d_valX, d_rowPtrX, d_colIndX, mI, d_rows, nJ, d_cols, nnzZ, d_rowPtrZ,
+                                              d_colIndZ, d_valZ, d_perm)
+        return err, nnzZ
+
+    def csr_extract_device(self, m, n, X, rows=None, cols=None, values=True, perm=False):
+        """Z = X(rows, cols) on device arrays: X = (rowPtr, colInd, val) torch tensors on this handle's GPU (val may be None:
+        the pattern alone); rows / cols: int32 torch tensors there, or None for all of them in order.  Returns (rowPtrZ,
+        colIndZ, valZ, perm) as torch tensors (valZ None when values is false or X has none, perm None unless asked for);
+        raises BhsparseError on failure."""
+        import torch
+        torch.cuda.synchronize()                           # the library works on its own stream (see initData_device)
+        Xp, Xj, Xx = X
+        nnzX = Xj.numel()
+        mI = m if rows is None else rows.numel()
+        nJ = n if cols is None else cols.numel()
+        Zp = torch.empty(mI + 1, dtype=torch.int32, device=Xp.device)
+        err, nnzZ = self.csr_extract_symbolic_device(m, n, nnzX, Xp, Xj, mI, rows, nJ, cols, Zp)
+        if err != BHSPARSE_SUCCESS:
+            raise BhsparseError("bhs_csr_extract_symbolic_device", err)
+        Zj = torch.empty(max(nnzZ, 1), dtype=torch.int32, device=Xp.device)
+        Zx = torch.empty(max(nnzZ, 1), dtype=Xx.dtype, device=Xp.device) if (values and Xx is not None) else None
+        pm = torch.empty(max(nnzZ, 1), dtype=torch.int32, device=Xp.device) if perm else None
+        torch.cuda.synchronize()
+        err = self.csr_extract_numeric_device(m, n, nnzX, Xx, Xp, Xj, mI, rows, nJ, cols, nnzZ, Zp, Zj, Zx, pm)
+        if err != BHSPARSE_SUCCESS:
+            raise BhsparseError("bhs_csr_extract_numeric_device", err)
+        return Zp, Zj[:nnzZ], (Zx[:nnzZ] if Zx is not None else None), (pm[:nnzZ] if pm is not None else None)
 
     # -- extension (not in the reference): the multiply over a semiring (include/bhsparse_hip.h, "semiring multiply")
     def spgemm_semiring(self, semiring):
@@ -861,6 +930,36 @@ def csr_transpose(m, n, Xp, Xj, Xx, value_dtype=np.float64, device=0):
     finally:
         bh.freePlatform()
     return out
+
+
+def extract_csr(m, n, Xp, Xj, Xx, rows=None, cols=None, value_dtype=np.float64, device=0):
+    """Convenience: Z = X(rows, cols) once on host CSR arrays (X is m x n; rows in any order, duplicates allowed; rows /
+    cols: index arrays or None for all in order), staged as torch tensors on the handle's device -- the extraction takes
+    device arrays only.  Returns (Zp int32[mI+1], Zj int32[nnzZ], Zx value_dtype[nnzZ], info) with info["kernels"],
+    info["ms"], info["reordered_rows"], info["perm"] (int32[nnzZ]: the position in X of every entry of Z).  Needs no
+    multiply data."""
+    import torch
+    dev = torch.device("cuda", device)
+
+    def up(a, dt):
+        return torch.from_numpy(np.ascontiguousarray(a, dt).copy()).to(dev)
+    X = (up(Xp, np.int32), up(Xj, np.int32), up(Xx, value_dtype))
+    r = None if rows is None else up(rows, np.int32)
+    c = None if cols is None else up(cols, np.int32)
+    bh = _new_handle(value_dtype, device, None)
+    try:
+        Zp, Zj, Zx, pm = bh.csr_extract_device(m, n, X, rows=r, cols=c, values=True, perm=True)
+        info = {"kernels": bh.kernel_stats(), "ms": bh.extract_ms, "reordered_rows": bh.get_info("extract_reordered_rows"),
+                "perm": pm.cpu().numpy()}
+        out = (Zp.cpu().numpy(), Zj.cpu().numpy(), Zx.cpu().numpy(), info)
+    finally:
+        bh.freePlatform()
+    return out
+
+
+def permute_csr(n, Xp, Xj, Xx, p, value_dtype=np.float64, device=0):
+    """Convenience: the symmetric reordering X(p, p) of an n x n matrix: extract_csr with rows = cols = p."""
+    return extract_csr(n, n, Xp, Xj, Xx, rows=p, cols=p, value_dtype=value_dtype, device=device)
 
 
 def galerkin_csr(m, nc, Pp, Pj, Px, Ap, Aj, Ax, options=None, value_dtype=np.float64, device=0):

@@ -62,6 +62,18 @@ public:
                              const index_type *d_colIndX, index_type *d_rowPtrT, index_type *d_colIndT, value_type *d_valT,
                              index_type *d_perm);
 
+    // EXTENSION, not part of the reference's API: Z = X(rows, cols) (bhs_csr_extract_{symbolic,numeric}_device,
+    // include/bhsparse_hip.h, "extract") on DEVICE arrays; X is m x n, d_rows / d_cols may be 0 (all, in order), Z's arrays are
+    // the caller's (mI + 1 ints, then nnzZ entries each; d_valX / d_valZ / d_perm may be 0).  Needs initPlatform only; does
+    // not disturb the data of initData or get_C's result.
+    int csr_extract_symbolic_device(int m, int n, int nnzX, const index_type *d_rowPtrX, const index_type *d_colIndX, int mI,
+                                    const index_type *d_rows, int nJ, const index_type *d_cols, index_type *d_rowPtrZ,
+                                    int *nnzZ_out);
+    int csr_extract_numeric_device(int m, int n, int nnzX, const value_type *d_valX, const index_type *d_rowPtrX,
+                                   const index_type *d_colIndX, int mI, const index_type *d_rows, int nJ,
+                                   const index_type *d_cols, int nnzZ, const index_type *d_rowPtrZ, index_type *d_colIndZ,
+                                   value_type *d_valZ, index_type *d_perm);
+
     // EXTENSION, not part of the reference's API: the multiply over a semiring (bhs_spgemm_semiring*, include/bhsparse_hip.h,
     // "semiring multiply"; semiring: a BHS_SR_* constant) on the data of initData.  spgemm_semiring is the full product: it
     // fills the csrRowPtrC of initData, and get_nnzC / get_C then return A (+).(x) B on the pattern of A·B.
@@ -173,6 +185,24 @@ inline int bhsparse::csr_transpose_device(int m, int n, int nnzX, const value_ty
 {
     if (!_h) return BHS_ERR_NOT_READY;
     return bhs_csr_transpose_device(_h, m, n, nnzX, d_valX, d_rowPtrX, d_colIndX, d_rowPtrT, d_colIndT, d_valT, d_perm, 0);
+}
+
+inline int bhsparse::csr_extract_symbolic_device(int m, int n, int nnzX, const index_type *d_rowPtrX, const index_type *d_colIndX,
+                                                 int mI, const index_type *d_rows, int nJ, const index_type *d_cols,
+                                                 index_type *d_rowPtrZ, int *nnzZ_out)
+{
+    if (!_h) return BHS_ERR_NOT_READY;
+    return bhs_csr_extract_symbolic_device(_h, m, n, nnzX, d_rowPtrX, d_colIndX, mI, d_rows, nJ, d_cols, d_rowPtrZ, nnzZ_out);
+}
+
+inline int bhsparse::csr_extract_numeric_device(int m, int n, int nnzX, const value_type *d_valX, const index_type *d_rowPtrX,
+                                                const index_type *d_colIndX, int mI, const index_type *d_rows, int nJ,
+                                                const index_type *d_cols, int nnzZ, const index_type *d_rowPtrZ,
+                                                index_type *d_colIndZ, value_type *d_valZ, index_type *d_perm)
+{
+    if (!_h) return BHS_ERR_NOT_READY;
+    return bhs_csr_extract_numeric_device(_h, m, n, nnzX, d_valX, d_rowPtrX, d_colIndX, mI, d_rows, nJ, d_cols, nnzZ, d_rowPtrZ,
+                                          d_colIndZ, d_valZ, d_perm, 0);
 }
 
 inline int bhsparse::get_nnzC()

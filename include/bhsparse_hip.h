@@ -404,6 +404,70 @@ BHS_API int bhs_spgemm_semiring_masked(bhs_handle *h, int semiring, const int *r
 BHS_API int bhs_spgemm_semiring(bhs_handle *h, int semiring, int *rowPtrC_out, int64_t *nnzCt_out, int *nnzC_out,
                                 double ms_out[2]);
 
+/* ---- extract --------------------------------------------------------------
+ * Z = X(rows, cols) on CSR: submatrix extraction and permutation (GraphBLAS extract, MATLAB's A(I, J); no reference
+ * counterpart; bhs_extract.hip.h).  What it is for: the blocks A_FF, A_FC, A_CF, A_CC of a C/F splitting, an induced
+ * subgraph, the column block one rank's rows reach, a symmetric reordering X(p, p) before a multiply.
+ * X: m x n, 0-based int32 CSR; rows need NOT be ascending, duplicate (row, column) pairs are legal (as for the
+ * transpose).  Z is mI x nJ with Z(i, j) = X(rows[i], cols[j]).
+ *   rows   mI ints, each in [0, m), in any order, repeats allowed (a row may be taken twice).  NULL: all rows in order;
+ *          mI must then equal m.
+ *   cols   nJ ints, each in [0, n), in any order, NO repeats (a repeated column would duplicate entries: another
+ *          operation, refused).  NULL: all columns in order; nJ must then equal n, no column map is built and the call
+ *          is a row gather.
+ * Order inside a Z row: row i of Z holds the entries q of X's row rows[i] whose column c = colIndX[q] is named by cols,
+ * each relabelled to the j with cols[j] == c, in ASCENDING j; ties (duplicate pairs of X) in the order of their position
+ * q in X.  Z's rows are therefore always ascending -- strictly ascending when X has no duplicate pair, and Z is then a
+ * legal operand of bhs_csr_add_*, bhs_spgemm_masked and bhs_set_data_device with "b_sorted".  Values are copied bit for
+ * bit (NaN payloads and -0 included); nothing is computed on them.  The result does not depend on scheduling; in numpy,
+ * per Z row i with r = rows[i]:
+ *   q = arange(Xp[r], Xp[r+1]); j = inv[Xj[q]] (inv[cols[t]] = t, -1 elsewhere); keep j >= 0;
+ *   order = argsort(j[keep], kind="stable"); colIndZ = j[keep][order]; perm = q[keep][order]; valZ = valX[perm].
+ * perm[p] is the position in X's arrays of entry p of Z: valZ = valX[perm].  Where the values of X change and its pattern
+ * does not, extract once with d_perm, keep rowPtrZ / colIndZ and re-value Z with
+ *   bhs_csr_transpose_values_device(h, nnzZ, d_valX, d_perm, d_valZ, ms_out)
+ * -- there is no values call of its own.  That call refuses a perm entry outside [0, count) for the count it is given:
+ * with count = nnzZ it serves every extraction with nnz(Z) >= nnz(X) (a permutation X(p, p), a row gather by a
+ * permutation, a column permutation, rows taken more than once).  For a true sub-matrix perm may reach beyond nnzZ and
+ * the values call then refuses it; re-value such a Z with the numeric call on the kept d_rowPtrZ.
+ *
+ * bhs_csr_extract_symbolic_device: validates, counts, writes d_rowPtrZ (mI+1 ints) and *nnzZ_out.
+ * bhs_csr_extract_numeric_device: fills d_colIndZ, d_valZ (may be NULL: the pattern alone; must be NULL when d_valX is),
+ *   d_perm (may be NULL), nnzZ entries each, for the d_rowPtrZ of the symbolic call (d_valX may be NULL with nnzX == 0).  ms_out (may be NULL): device time
+ *   of the call, validation included.
+ * Validation: on the device, BEFORE anything caller-owned is written, in both calls.  rowPtrX[0] != 0, a decreasing
+ *   rowPtrX (anywhere in X), rowPtrX[m] != nnzX, a row index outside [0, m), a column index outside [0, n), a repeated
+ *   column index, or a column of X outside [0, n) return BHS_ERR_INVALID_ARG with every output untouched.  Rows of X that
+ *   `rows` never names are never read: X's COLUMNS are checked in the rows that are read, its row pointer everywhere.
+ *   On the host: d_rows == NULL with mI != m, d_cols == NULL with nJ != n, d_valZ without d_valX, outputs that overlap
+ *   inputs or one another return BHS_ERR_INVALID_ARG as well.
+ *   The numeric call evaluates the rule again before it writes: if a row's survivors are not what d_rowPtrZ says, or
+ *   d_rowPtrZ[mI] != nnzZ, it returns BHS_ERR_INVALID_ARG with the outputs untouched; nothing is ever written outside
+ *   [0, nnzZ).
+ * Sizes: nnz(Z) > INT32_MAX is possible with repeated rows and returns BHS_ERR_NNZ_OVERFLOW from the symbolic call
+ *   (d_rowPtrZ untouched).  m, n, mI, nJ and nnzX may be 0; d_rowPtrZ is still written.
+ * Both calls are synchronous, need no bound data (they work on a handle straight after bhs_create), return
+ *   BHS_ERR_INVALID_ARG between bhs_spgemm_symbolic and bhs_spgemm_finish, and leave the handle as it was: counters,
+ *   queues, tile words, epoch, events, the column map (n ints) and the keys of rows beyond the LDS (8 bytes an entry of
+ *   Z, only where an X row has more than 1024 entries) are buffers of their own from the grow-only pool; C of the last
+ *   multiply, a served sum or selection, "class_state", the speculative-launch figures and every option stay.  Only
+ *   bhs_get_kernel_stats now reports the extraction's families: extract_map (validation of rows and cols, rowPtrX's
+ *   monotonicity, the inverse column map; absent when both d_rows and d_cols are NULL), extract_count (the touched rows
+ *   of X: validation, survivors, bins), extract_scan (symbolic call), extract_short (X rows of up to 32 entries),
+ *   extract_wave (up to 1024), extract_long (numeric call).  bhs_get_info "extract_reordered_rows" (needs no bound data):
+ *   the Z rows of the last successful numeric call whose relabelled entries were not already ascending and had to be put
+ *   in order -- 0 for ascending cols on ascending X rows, a C/F split with sorted F, the row gather.
+ * Known limit: one Z row is compacted and put in order by one workgroup; a single row of millions of entries is slow.  */
+BHS_API int bhs_csr_extract_symbolic_device(bhs_handle *h, int m, int n,
+        int nnzX, const int *d_rowPtrX, const int *d_colIndX,
+        int mI, const int *d_rows /* may be NULL */, int nJ, const int *d_cols /* may be NULL */,
+        int *d_rowPtrZ /* mI+1 */, int *nnzZ_out);
+BHS_API int bhs_csr_extract_numeric_device(bhs_handle *h, int m, int n,
+        int nnzX, const bhs_value_t *d_valX /* may be NULL */, const int *d_rowPtrX, const int *d_colIndX,
+        int mI, const int *d_rows, int nJ, const int *d_cols,
+        int nnzZ, const int *d_rowPtrZ, int *d_colIndZ, bhs_value_t *d_valZ /* may be NULL */,
+        int *d_perm /* may be NULL */, double *ms_out /* may be NULL */);
+
 /* replaces bhsparse::get_nnzC (bhsparse.h: get_nnzC -> bhsparse_cuda::get_nnzC). */
 BHS_API int bhs_get_nnzC(bhs_handle *h, int *nnzC_out);
 
