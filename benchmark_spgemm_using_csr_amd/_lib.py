@@ -46,6 +46,12 @@ SEMIRINGS = {"plus_times": BHS_SR_PLUS_TIMES, "min_plus": BHS_SR_MIN_PLUS, "max_
              "max_times": BHS_SR_MAX_TIMES, "min_max": BHS_SR_MIN_MAX, "max_min": BHS_SR_MAX_MIN, "or_and": BHS_SR_OR_AND,
              "plus_pair": BHS_SR_PLUS_PAIR}
 
+# bhs_csr_reduce_device / bhs_csr_scale_device (include/bhsparse_hip.h, "reduce / scale")
+BHS_AXIS_ROWS, BHS_AXIS_COLS, BHS_AXIS_ALL, BHS_AXIS_DIAG = range(4)
+(BHS_RED_PLUS, BHS_RED_MIN, BHS_RED_MAX, BHS_RED_ABS_PLUS, BHS_RED_ABS_MAX, BHS_RED_SQ_PLUS, BHS_RED_COUNT) = range(7)
+BHS_RED_OFFDIAG = 1
+BHS_SCALE_LEFT_DIV, BHS_SCALE_RIGHT_DIV = 1, 2
+
 
 # every symbol include/bhsparse_hip.h declares: (restype, argtypes)
 _vp, _i, _i64 = C.c_void_p, C.c_int, C.c_int64
@@ -94,6 +100,8 @@ SYMBOLS = {
     "bhs_csr_extract_symbolic_device": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, C.POINTER(_i)]),
     "bhs_csr_extract_numeric_device": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp,
                                             C.POINTER(C.c_double)]),
+    "bhs_csr_reduce_device": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _vp, C.POINTER(C.c_double)]),
+    "bhs_csr_scale_device": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, C.c_double, _vp, _vp, _i, _vp, C.POINTER(C.c_double)]),
     "bhs_strerror": (C.c_char_p, [_i]),
     "bhs_version": (C.c_char_p, []),
 }
@@ -104,7 +112,7 @@ _lib = None
 _libs = {}
 
 
-SOURCES = ("bhsparse_hip.hip", "bhs_host_launch.inc.h", "bhs_host_pipeline.inc.h", "bhs_host_setdata.inc.h", "bhs_host_cabi.inc.h", "bhs_kernels.hip.h", "bhs_row_wg.hip.h", "bhs_row_window.hip.h", "bhs_row_wave.hip.h", "bhs_row_quad.hip.h", "bhs_compress.hip.h", "bhs_row_lane.hip.h", "bhs_sort.hip.h", "bhs_hub.hip.h", "bhs_class.hip.h", "bhs_class_mix.hip.h", "bhs_class_wg.hip.h", "bhs_class_ring.hip.h", "bhs_class_fused.hip.h", "bhs_class_tile.hip.h", "bhs_class_big.hip.h", "bhs_wave.hip.h", "bhs_lab.hip.h", "bhs_masked.hip.h", "bhs_host_masked.inc.h", "bhs_add.hip.h", "bhs_host_add.inc.h", "bhs_select.hip.h", "bhs_host_select.inc.h", "bhs_transpose.hip.h", "bhs_host_transpose.inc.h", "bhs_semiring.hip.h", "bhs_host_semiring.inc.h", "bhs_extract.hip.h", "bhs_host_extract.inc.h")
+SOURCES = ("bhsparse_hip.hip", "bhs_host_launch.inc.h", "bhs_host_pipeline.inc.h", "bhs_host_setdata.inc.h", "bhs_host_cabi.inc.h", "bhs_kernels.hip.h", "bhs_row_wg.hip.h", "bhs_row_window.hip.h", "bhs_row_wave.hip.h", "bhs_row_quad.hip.h", "bhs_compress.hip.h", "bhs_row_lane.hip.h", "bhs_sort.hip.h", "bhs_hub.hip.h", "bhs_class.hip.h", "bhs_class_mix.hip.h", "bhs_class_wg.hip.h", "bhs_class_ring.hip.h", "bhs_class_fused.hip.h", "bhs_class_tile.hip.h", "bhs_class_big.hip.h", "bhs_wave.hip.h", "bhs_lab.hip.h", "bhs_masked.hip.h", "bhs_host_masked.inc.h", "bhs_add.hip.h", "bhs_host_add.inc.h", "bhs_select.hip.h", "bhs_host_select.inc.h", "bhs_transpose.hip.h", "bhs_host_transpose.inc.h", "bhs_semiring.hip.h", "bhs_host_semiring.inc.h", "bhs_extract.hip.h", "bhs_host_extract.inc.h", "bhs_reduce.hip.h", "bhs_host_reduce.inc.h")
 
 
 def source_digest():

@@ -126,6 +126,9 @@ int bhs_destroy(bhs_handle* h)
     release(h->exCtl); release(h->exCnt); release(h->exQueue); release(h->exInv); release(h->exKeys); release(h->exTiles);
     if (h->exHost) (void)hipHostFree(h->exHost);
     for (int i = 0; i < 2; ++i) if (h->exEv[i]) (void)hipEventDestroy(h->exEv[i]);
+    release(h->rdCtl); release(h->rdQueue); release(h->rdAcc); release(h->rdPart);
+    if (h->rdHost) (void)hipHostFree(h->rdHost);
+    for (int i = 0; i < 2; ++i) if (h->rdEv[i]) (void)hipEventDestroy(h->rdEv[i]);
     if (h->addHost) (void)hipHostFree(h->addHost);
     for (int i = 0; i < 2; ++i) if (h->addEv[i]) (void)hipEventDestroy(h->addEv[i]);
     if (h->maskHost) (void)hipHostFree(h->maskHost);

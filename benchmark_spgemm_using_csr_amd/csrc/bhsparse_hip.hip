@@ -1,7 +1,7 @@
 // bhsparse_hip.hip — libbhsparse_hip.so (see include/bhsparse_hip.h): the handle and its helpers here; the launch helpers,
 // the pipeline, the hand-over of a data set and the C-ABI in bhs_host_{launch,pipeline,setdata,cabi}.inc.h, the masked multiply
-// the sparse add, the entry selection, the transpose, the semiring multiply and the extraction in
-// bhs_host_{masked,add,select,transpose,semiring,extract}.inc.h (one translation unit).
+// the sparse add, the entry selection, the transpose, the reductions and the scaling, the semiring multiply and the extraction in
+// bhs_host_{masked,add,select,transpose,reduce,semiring,extract}.inc.h (one translation unit).
 //
 // Pipeline of one bhs_spgemm() (replaces bhsparse::spgemm_cuda, bhsparse.h:297-339):
 //   stage 1  k_upper_bound (ub per row, nnzCt, symbolic-bin histogram)          <- compute_nnzCt + statistics()
@@ -389,6 +389,10 @@ struct bhs_handle {
     hipEvent_t exEv[2] = {nullptr, nullptr};
     unsigned exEpoch = 0;
     long long exReordered = 0;           // bhs_get_info "extract_reordered_rows": Z rows the last numeric call had to put in order
+    // the reductions and the scaling (bhs_host_reduce.inc.h): buffers of their own as well
+    DevBuf rdCtl, rdQueue, rdAcc, rdPart; // counters; the queues of the rows beyond the short bin (2 x m ints); the accumulators, 8 bytes an output; the partials of a total
+    int* rdHost = nullptr;               // pinned mirror of rdCtl
+    hipEvent_t rdEv[2] = {nullptr, nullptr};
 };
 
 namespace {
@@ -544,5 +548,6 @@ inline int one_launch(int rc) { return rc != BHS_SUCCESS ? rc : 1; }
 #include "bhs_host_add.inc.h"
 #include "bhs_host_select.inc.h"
 #include "bhs_host_transpose.inc.h"
+#include "bhs_host_reduce.inc.h"
 #include "bhs_host_semiring.inc.h"
 #include "bhs_host_extract.inc.h"

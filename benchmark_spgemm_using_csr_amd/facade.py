@@ -63,6 +63,8 @@ class bhsparse(object):
         self.select_ms = 0.0
         self.transpose_ms = 0.0
         self.extract_ms = 0.0
+        self.reduce_ms = 0.0
+        self.scale_ms = 0.0
         self.semiring_ms = 0.0
         self.multiply_ms = 0.0
         self.quiet = True
@@ -446,6 +448,60 @@ class bhsparse(object):
         if err != BHSPARSE_SUCCESS:
             raise BhsparseError("bhs_csr_extract_numeric_device", err)
         return Zp, Zj[:nnzZ], (Zx[:nnzZ] if Zx is not None else None), (pm[:nnzZ] if pm is not None else None)
+
+    # -- extension (not in the reference): reductions and the diagonal scaling (include/bhsparse_hip.h, "reduce / scale")
+    def csr_reduce_raw_device(self, m, n, nnzX, d_valX, d_rowPtrX, d_colIndX, axis, op, flags, d_out):
+        """bhs_csr_reduce_device on caller-given arrays: the status code; sets reduce_ms."""
+        if self._h is None:
+            return _lib.BHS_ERR_NOT_READY
+        ms = C.c_double(0)
+        err = self._lib.bhs_csr_reduce_device(self._h, int(m), int(n), int(nnzX), _ptr(d_valX), _ptr(d_rowPtrX), _ptr(d_colIndX),
+                                              int(axis), int(op), int(flags), _ptr(d_out), C.byref(ms))
+        if err == BHSPARSE_SUCCESS:
+            self.reduce_ms = float(ms.value)
+        return err
+
+    def csr_scale_raw_device(self, m, n, nnzX, d_valX, d_rowPtrX, d_colIndX, alpha, d_left, d_right, flags, d_valZ):
+        """bhs_csr_scale_device on caller-given arrays: the status code; sets scale_ms."""
+        if self._h is None:
+            return _lib.BHS_ERR_NOT_READY
+        ms = C.c_double(0)
+        err = self._lib.bhs_csr_scale_device(self._h, int(m), int(n), int(nnzX), _ptr(d_valX), _ptr(d_rowPtrX), _ptr(d_colIndX),
+                                             float(alpha), _ptr(d_left), _ptr(d_right), int(flags), _ptr(d_valZ), C.byref(ms))
+        if err == BHSPARSE_SUCCESS:
+            self.scale_ms = float(ms.value)
+        return err
+
+    def csr_reduce_device(self, m, n, X, axis, op, offdiag=False):
+        """reduce(X) along `axis` (_lib.BHS_AXIS_*) with `op` (_lib.BHS_RED_*) on device arrays: X = (rowPtr, colInd, val)
+        torch tensors on this handle's GPU (val may be None: every entry counts as 1).  Returns a torch tensor of m, n, 1
+        or min(m, n) values of this handle's value type; raises BhsparseError on failure."""
+        import torch
+        torch.cuda.synchronize()                           # the library works on its own stream (see initData_device)
+        Xp, Xj, Xx = X
+        count = {_lib.BHS_AXIS_ROWS: m, _lib.BHS_AXIS_COLS: n, _lib.BHS_AXIS_ALL: 1, _lib.BHS_AXIS_DIAG: min(m, n)}.get(axis, 1)
+        tdt = torch.float32 if self._vdt == np.dtype(np.float32) else torch.float64
+        out = torch.empty(max(count, 1), dtype=tdt, device=Xp.device)
+        torch.cuda.synchronize()
+        err = self.csr_reduce_raw_device(m, n, Xj.numel(), Xx, Xp, Xj, axis, op, _lib.BHS_RED_OFFDIAG if offdiag else 0, out)
+        if err != BHSPARSE_SUCCESS:
+            raise BhsparseError("bhs_csr_reduce_device", err)
+        return out[:count]
+
+    def csr_scale_device(self, m, n, X, alpha=1.0, left=None, right=None, left_div=False, right_div=False, out=None):
+        """valZ of Z = alpha diag(left) X diag(right) on X's pattern: X = (rowPtr, colInd, val) torch tensors on this
+        handle's GPU, left / right torch tensors of m / n values there or None; *_div divides by the vector.  out: where
+        the values go (X's val itself: in place); a new tensor by default.  Returns it; raises BhsparseError on failure."""
+        import torch
+        Xp, Xj, Xx = X
+        if out is None:
+            out = torch.empty(max(Xx.numel(), 1), dtype=Xx.dtype, device=Xx.device)[:Xx.numel()]
+        torch.cuda.synchronize()
+        flags = (_lib.BHS_SCALE_LEFT_DIV if left_div else 0) | (_lib.BHS_SCALE_RIGHT_DIV if right_div else 0)
+        err = self.csr_scale_raw_device(m, n, Xj.numel(), Xx, Xp, Xj, alpha, left, right, flags, out)
+        if err != BHSPARSE_SUCCESS:
+            raise BhsparseError("bhs_csr_scale_device", err)
+        return out
 
     # -- extension (not in the reference): the multiply over a semiring (include/bhsparse_hip.h, "semiring multiply")
     def spgemm_semiring(self, semiring):
@@ -960,6 +1016,107 @@ def extract_csr(m, n, Xp, Xj, Xx, rows=None, cols=None, value_dtype=np.float64, 
 def permute_csr(n, Xp, Xj, Xx, p, value_dtype=np.float64, device=0):
     """Convenience: the symmetric reordering X(p, p) of an n x n matrix: extract_csr with rows = cols = p."""
     return extract_csr(n, n, Xp, Xj, Xx, rows=p, cols=p, value_dtype=value_dtype, device=device)
+
+
+def _device_csr(Xp, Xj, Xx, value_dtype, device):
+    import torch
+    dev = torch.device("cuda", device)
+
+    def up(a, dt):
+        return torch.from_numpy(np.ascontiguousarray(a, dt).copy()).to(dev)
+    return up(Xp, np.int32), up(Xj, np.int32), (None if Xx is None else up(Xx, value_dtype)), up
+
+
+def reduce_csr(m, n, Xp, Xj, Xx, axis, op, offdiag=False, value_dtype=np.float64, device=0):
+    """Convenience: reduce(X) once on host CSR arrays (X is m x n; Xx may be None: every entry counts as 1), staged as
+    torch tensors on the handle's device.  axis: _lib.BHS_AXIS_*, op: _lib.BHS_RED_*.  Returns (out value_dtype[...],
+    info) with info["kernels"], info["ms"].  Needs no multiply data."""
+    dXp, dXj, dXx, _ = _device_csr(Xp, Xj, Xx, value_dtype, device)
+    bh = _new_handle(value_dtype, device, None)
+    try:
+        out = bh.csr_reduce_device(m, n, (dXp, dXj, dXx), axis, op, offdiag=offdiag)
+        res = (out.cpu().numpy(), {"kernels": bh.kernel_stats(), "ms": bh.reduce_ms})
+    finally:
+        bh.freePlatform()
+    return res
+
+
+def diagonal_csr(m, n, Xp, Xj, Xx, value_dtype=np.float64, device=0):
+    """Convenience: diag(X), min(m, n) values (duplicate pairs add up, a missing diagonal entry is 0)."""
+    return reduce_csr(m, n, Xp, Xj, Xx, _lib.BHS_AXIS_DIAG, _lib.BHS_RED_PLUS, value_dtype=value_dtype, device=device)[0]
+
+
+def scale_csr(m, n, Xp, Xj, Xx, alpha=1.0, left=None, right=None, left_div=False, right_div=False, value_dtype=np.float64,
+              device=0):
+    """Convenience: the values of Z = alpha diag(left) X diag(right) once on host CSR arrays (Z has X's pattern).  Returns
+    (Zx value_dtype[nnzX], info) with info["kernels"], info["ms"]."""
+    dXp, dXj, dXx, up = _device_csr(Xp, Xj, Xx, value_dtype, device)
+    l = None if left is None else up(left, value_dtype)
+    r = None if right is None else up(right, value_dtype)
+    bh = _new_handle(value_dtype, device, None)
+    try:
+        Zx = bh.csr_scale_device(m, n, (dXp, dXj, dXx), alpha, l, r, left_div, right_div)
+        res = (Zx.cpu().numpy(), {"kernels": bh.kernel_stats(), "ms": bh.scale_ms})
+    finally:
+        bh.freePlatform()
+    return res
+
+
+def normalize_csr(m, n, Xp, Xj, Xx, axis, norm=1, value_dtype=np.float64, device=0):
+    """Convenience: X with every row (axis = _lib.BHS_AXIS_ROWS) or column (BHS_AXIS_COLS) divided by its norm, kept on the
+    device between the reduction and the scaling: norm 1 (sum |x|), "inf" (max |x|) or 2 (sqrt of sum x^2).  A zero norm
+    divides by 1 (the row or column stays as it is).  Returns (Zx value_dtype[nnzX], norms)."""
+    import torch
+    if axis not in (_lib.BHS_AXIS_ROWS, _lib.BHS_AXIS_COLS) or norm not in (1, 2, "inf"):
+        raise ValueError("axis is BHS_AXIS_ROWS or BHS_AXIS_COLS, norm 1, 2 or \"inf\"")
+    dXp, dXj, dXx, _ = _device_csr(Xp, Xj, Xx, value_dtype, device)
+    op = {1: _lib.BHS_RED_ABS_PLUS, "inf": _lib.BHS_RED_ABS_MAX, 2: _lib.BHS_RED_SQ_PLUS}[norm]
+    bh = _new_handle(value_dtype, device, None)
+    try:
+        nrm = bh.csr_reduce_device(m, n, (dXp, dXj, dXx), axis, op)
+        if norm == 2:
+            nrm = torch.sqrt(nrm)
+        div = torch.where(nrm == 0, torch.ones_like(nrm), nrm)
+        rows = axis == _lib.BHS_AXIS_ROWS
+        Zx = bh.csr_scale_device(m, n, (dXp, dXj, dXx), 1.0, div if rows else None, None if rows else div, rows, not rows)
+        res = (Zx.cpu().numpy(), nrm.cpu().numpy())
+    finally:
+        bh.freePlatform()
+    return res
+
+
+def smoothed_prolongator_csr(n, nc, Ap, Aj, Ax, Tp, Tj, Tx, omega, options=None, value_dtype=np.float64, device=0):
+    """Convenience: the smoothed prolongator P = T - omega D^-1 A T of an n x n matrix A (D = diag(A)) and an n x nc
+    tentative prolongator T (rows strictly ascending) on host CSR arrays, kept on the device between the upload and one
+    get_C: diag(A) (bhs_csr_reduce_device), -omega D^-1 A (bhs_csr_scale_device with LEFT_DIV), then the multiply with T
+    plus T (bhs_spgemm_add, alpha = beta = 1).  Returns (Pp int32[n+1], Pj, Px, info); info: "nnzCt", "nnzC",
+    "reduce_ms", "scale_ms", "add_ms", "kernels"."""
+    dAp, dAj, dAx, up = _device_csr(Ap, Aj, Ax, value_dtype, device)
+    T = (up(Tp, np.int32), up(Tj, np.int32), up(Tx, value_dtype))
+    bh = _new_handle(value_dtype, device, options)
+    try:
+        d = bh.csr_reduce_device(n, n, (dAp, dAj, dAx), _lib.BHS_AXIS_DIAG, _lib.BHS_RED_PLUS)
+        Sx = bh.csr_scale_device(n, n, (dAp, dAj, dAx), -float(omega), left=d, left_div=True)
+        nnzA, nnzT = dAj.numel(), T[1].numel()
+        err = bh.initData_device(n, n, nc, nnzA, Sx, dAp, dAj, nnzT, T[2], T[0], T[1])
+        if err:
+            raise BhsparseError("initData_device(-omega D^-1 A, T)", err)
+        err = bh.spgemm_add_device(1.0, 1.0, nnzT, T[2], T[0], T[1])
+        if err:
+            raise BhsparseError("bhs_spgemm_add_device", err)
+        nnzC = bh.get_nnzC()
+        Pp = bh.get_rowptrC()
+        Pj = np.empty(nnzC, np.int32)
+        Px = np.empty(nnzC, value_dtype)
+        err = bh.get_C(Pj, Px)
+        if err:
+            raise BhsparseError("get_C", err)
+        info = {"nnzCt": bh.nnzCt, "nnzC": nnzC, "reduce_ms": bh.reduce_ms, "scale_ms": bh.scale_ms, "add_ms": bh.add_ms,
+                "kernels": bh.kernel_stats()}
+        bh.free_mem()
+    finally:
+        bh.freePlatform()
+    return Pp, Pj, Px, info
 
 
 def galerkin_csr(m, nc, Pp, Pj, Px, Ap, Aj, Ax, options=None, value_dtype=np.float64, device=0):

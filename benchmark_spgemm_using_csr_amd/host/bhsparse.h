@@ -74,6 +74,17 @@ public:
                                    const index_type *d_cols, int nnzZ, const index_type *d_rowPtrZ, index_type *d_colIndZ,
                                    value_type *d_valZ, index_type *d_perm);
 
+    // EXTENSION, not part of the reference's API: reductions and the diagonal scaling (bhs_csr_reduce_device,
+    // bhs_csr_scale_device, include/bhsparse_hip.h, "reduce / scale") on DEVICE arrays; X is m x n.  axis: a BHS_AXIS_*
+    // constant, op: BHS_RED_*, flags: BHS_RED_OFFDIAG / BHS_SCALE_*_DIV; d_out holds m, n, 1 or min(m, n) values, d_valZ
+    // nnzX (it may be d_valX); d_left / d_right may be 0.  Needs initPlatform only; does not disturb the data of initData
+    // or get_C's result.
+    int csr_reduce_device(int m, int n, int nnzX, const value_type *d_valX, const index_type *d_rowPtrX,
+                          const index_type *d_colIndX, int axis, int op, int flags, value_type *d_out);
+    int csr_scale_device(int m, int n, int nnzX, const value_type *d_valX, const index_type *d_rowPtrX,
+                         const index_type *d_colIndX, double alpha, const value_type *d_left, const value_type *d_right,
+                         int flags, value_type *d_valZ);
+
     // EXTENSION, not part of the reference's API: the multiply over a semiring (bhs_spgemm_semiring*, include/bhsparse_hip.h,
     // "semiring multiply"; semiring: a BHS_SR_* constant) on the data of initData.  spgemm_semiring is the full product: it
     // fills the csrRowPtrC of initData, and get_nnzC / get_C then return A (+).(x) B on the pattern of A·B.
@@ -203,6 +214,21 @@ inline int bhsparse::csr_extract_numeric_device(int m, int n, int nnzX, const va
     if (!_h) return BHS_ERR_NOT_READY;
     return bhs_csr_extract_numeric_device(_h, m, n, nnzX, d_valX, d_rowPtrX, d_colIndX, mI, d_rows, nJ, d_cols, nnzZ, d_rowPtrZ,
                                           d_colIndZ, d_valZ, d_perm, 0);
+}
+
+inline int bhsparse::csr_reduce_device(int m, int n, int nnzX, const value_type *d_valX, const index_type *d_rowPtrX,
+                                       const index_type *d_colIndX, int axis, int op, int flags, value_type *d_out)
+{
+    if (!_h) return BHS_ERR_NOT_READY;
+    return bhs_csr_reduce_device(_h, m, n, nnzX, d_valX, d_rowPtrX, d_colIndX, axis, op, flags, d_out, 0);
+}
+
+inline int bhsparse::csr_scale_device(int m, int n, int nnzX, const value_type *d_valX, const index_type *d_rowPtrX,
+                                      const index_type *d_colIndX, double alpha, const value_type *d_left,
+                                      const value_type *d_right, int flags, value_type *d_valZ)
+{
+    if (!_h) return BHS_ERR_NOT_READY;
+    return bhs_csr_scale_device(_h, m, n, nnzX, d_valX, d_rowPtrX, d_colIndX, alpha, d_left, d_right, flags, d_valZ, 0);
 }
 
 inline int bhsparse::get_nnzC()

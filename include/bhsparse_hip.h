@@ -468,6 +468,99 @@ BHS_API int bhs_csr_extract_numeric_device(bhs_handle *h, int m, int n,
         int nnzZ, const int *d_rowPtrZ, int *d_colIndZ, bhs_value_t *d_valZ /* may be NULL */,
         int *d_perm /* may be NULL */, double *ms_out /* may be NULL */);
 
+/* ---- reduce / scale -------------------------------------------------------
+ * A CSR matrix to a vector or a scalar (GraphBLAS reduce: degrees, row / column sums, diag(X), the 1-, Inf- and
+ * Frobenius norms, the total of a PLUS_PAIR triangle count), and a matrix times diagonal matrices on its own pattern
+ * (the diagonal case of apply: D^-1 A of a smoothed prolongator, the column normalisation of Markov clustering); no
+ * reference counterpart; bhs_reduce.hip.h.
+ * X: m x n, 0-based int32 CSR; rows need NOT be ascending, duplicate (row, column) pairs are legal (as for the transpose
+ * and the extraction).  Both calls are synchronous, need no bound data (they work on a handle straight after
+ * bhs_create), return BHS_ERR_INVALID_ARG between bhs_spgemm_symbolic and bhs_spgemm_finish, and leave the handle as it
+ * was: counters, queues (2 m ints), accumulators (8 bytes an output), events and the pinned mirror are buffers of their
+ * own from the grow-only pool; C of the last multiply, a served sum or selection, "class_state", the speculative-launch
+ * figures and every option stay.  ms_out (may be NULL): device time of the call, validation included.
+ *
+ * bhs_csr_reduce_device: d_out = reduce(X) along `axis` with `op`.
+ *   axis  BHS_AXIS_ROWS  d_out has m values, one per row
+ *         BHS_AXIS_COLS  d_out has n values, one per column
+ *         BHS_AXIS_ALL   d_out has one value
+ *         BHS_AXIS_DIAG  d_out has min(m, n) values; out[i] reduces the entries with row == col == i (duplicate pairs
+ *                        reduce together; with PLUS this is diag(X))
+ *   op                    reduction            identity (a row, column or diagonal without an entry)
+ *     BHS_RED_PLUS        sum of x             +0
+ *     BHS_RED_MIN         min of x             +Inf
+ *     BHS_RED_MAX         max of x             -Inf
+ *     BHS_RED_ABS_PLUS    sum of |x|           +0
+ *     BHS_RED_ABS_MAX     max of |x|           +0
+ *     BHS_RED_SQ_PLUS     sum of x * x         +0
+ *     BHS_RED_COUNT       number of entries    +0      (never reads d_valX; exact up to 2^53 in the double build and
+ *                                                       2^24 in the float build, as BHS_SR_PLUS_PAIR)
+ *   flags BHS_RED_OFFDIAG skips the entries with col == row; refused with BHS_AXIS_DIAG.
+ *   d_valX may be NULL: every entry then counts as the value 1.
+ * Arithmetic (worded as for the semirings): every entry is converted to double and reduced in double -- for float
+ *   inputs |x| and x * x are exact there --, with ONE rounding to bhs_value_t per output.  min and max order values as
+ *   numbers with -0 below +0.  A NaN entry makes its output NaN, under ABS_MAX too; which NaN is not specified.  A sum
+ *   that is zero comes out as +0.
+ * Reproducibility: MIN, MAX, ABS_MAX and COUNT are bit-for-bit functions of the input on every axis.  The sum operators
+ *   (PLUS, ABS_PLUS, SQ_PLUS) on ROWS, DIAG and ALL add in an order that is a function of the input and the build alone
+ *   -- two calls on the same arrays give the same bits; ALL forms one partial per workgroup, their number a function of
+ *   nnzX alone, and adds the partials in a second pass of fixed order, never with atomics on one address.  The sum
+ *   operators on COLS accumulate with atomics (in LDS, then in memory): their last bits may differ from run to run.
+ * What is read: d_colIndX only where the call needs it -- BHS_AXIS_COLS, BHS_AXIS_DIAG (in the rows below min(m, n)) and
+ *   BHS_RED_OFFDIAG --, and it is checked where it is read.  A plain row sum or total reads rowPtrX and valX only, 8 bytes
+ *   an entry and not 12; COUNT on ROWS without OFFDIAG reads the row pointer alone.
+ * Validation: on the device, BEFORE d_out is written (every kernel reduces into scratch; the last one, reduce_finish,
+ *   rounds and stores only where nothing was refused).  rowPtrX[0] != 0, a decreasing rowPtrX, rowPtrX[m] != nnzX, or --
+ *   in the calls that read columns -- a column outside [0, n) return BHS_ERR_INVALID_ARG with d_out untouched.  On the
+ *   host: an unknown axis, op or flag bit, OFFDIAG with DIAG, d_out overlapping an input return BHS_ERR_INVALID_ARG.
+ *   m, n and nnzX may be 0; BHS_AXIS_ALL still writes the identity.
+ * bhs_get_kernel_stats then reports the families reduce_short (every row in order: the row pointer's check, the rows of
+ *   up to 32 entries, 16 lanes each), reduce_wave (up to 1024 entries, a wave each), reduce_long (a workgroup each) for
+ *   ROWS and DIAG; reduce_cols for COLS; reduce_all for ALL (after the three row families under OFFDIAG); reduce_finish.
+ *
+ * bhs_csr_scale_device: Z = alpha * Dl * X * Dr on X's pattern, Dl = diag(d_left) (m values), Dr = diag(d_right) (n
+ *   values); either may be NULL (no such factor).  The pattern arrays are not copied: the caller reuses d_rowPtrX and
+ *   d_colIndX for Z.  d_valZ (nnzX values) may equal d_valX (in place); any other overlap with an input is refused.
+ *   flags BHS_SCALE_LEFT_DIV divides by left[i] instead of multiplying, BHS_SCALE_RIGHT_DIV the same for right[j]:
+ *         D^-1 A needs no vector of reciprocals and is the correctly rounded quotient.  A DIV flag without its vector
+ *         returns BHS_ERR_INVALID_ARG.
+ * Arithmetic, in this order, so that numpy reproduces it bit for bit: t = double(x); with a left vector t = t * l[i]
+ *   (t / l[i] under LEFT_DIV); with a right vector t = t * r[j] (t / r[j] under RIGHT_DIV); t = t * alpha; one rounding
+ *   to bhs_value_t.  Only multiplications and divisions: FMA contraction cannot change a bit.  Division by zero and
+ *   non-finite values follow IEEE; nothing is skipped.
+ * Validation: rowPtrX is validated on the device before anything is written (BHS_ERR_INVALID_ARG, d_valZ untouched).
+ *   d_colIndX is read only when d_right is given; a column outside [0, n) is never used as an index and the call returns
+ *   BHS_ERR_INVALID_ARG -- scaling in place is legal, so that refusal may leave d_valZ[0, nnzX) partly written.  Nothing is
+ *   ever written outside [0, nnzX).
+ * Kernel-stat families: scale (no left vector: entry by entry), scale_short / scale_wave / scale_long (with a left
+ *   vector: by rows, binned as the reduction's).  16 compulsory bytes an entry, 4 more with d_right.                    */
+enum {
+  BHS_AXIS_ROWS = 0,
+  BHS_AXIS_COLS = 1,
+  BHS_AXIS_ALL  = 2,
+  BHS_AXIS_DIAG = 3
+};
+enum {
+  BHS_RED_PLUS     = 0,
+  BHS_RED_MIN      = 1,
+  BHS_RED_MAX      = 2,
+  BHS_RED_ABS_PLUS = 3,
+  BHS_RED_ABS_MAX  = 4,
+  BHS_RED_SQ_PLUS  = 5,
+  BHS_RED_COUNT    = 6
+};
+enum { BHS_RED_OFFDIAG = 1 };
+enum { BHS_SCALE_LEFT_DIV = 1, BHS_SCALE_RIGHT_DIV = 2 };
+BHS_API int bhs_csr_reduce_device(bhs_handle *h, int m, int n, int nnzX,
+        const bhs_value_t *d_valX /* may be NULL: every entry counts as 1 */,
+        const int *d_rowPtrX, const int *d_colIndX,
+        int axis, int op, int flags, bhs_value_t *d_out, double *ms_out /* may be NULL */);
+BHS_API int bhs_csr_scale_device(bhs_handle *h, int m, int n, int nnzX,
+        const bhs_value_t *d_valX, const int *d_rowPtrX, const int *d_colIndX,
+        double alpha, const bhs_value_t *d_left /* m values or NULL */,
+        const bhs_value_t *d_right /* n values or NULL */, int flags,
+        bhs_value_t *d_valZ /* nnzX; may equal d_valX */, double *ms_out /* may be NULL */);
+
 /* replaces bhsparse::get_nnzC (bhsparse.h: get_nnzC -> bhsparse_cuda::get_nnzC). */
 BHS_API int bhs_get_nnzC(bhs_handle *h, int *nnzC_out);
 
