@@ -1,8 +1,9 @@
 // bhs_host_add.inc.h -- the sparse add (bhs_csr_add_{symbolic,numeric}_device, bhs_spgemm_add[_device]; kernels in bhs_add.hip.h)
 // (A part of bhsparse_hip.hip's translation unit: included there after the masked multiply.)
 //
-// Like the masked multiply the add works beside the pipeline, never through its state: counters, queues, tile words, events and
-// staging copies are buffers of its own.  bhs_spgemm_add runs the ordinary multiply and then either adds into its valC in place
+// Like the masked multiply the add works beside the pipeline, never through its state: its workspace (h->addWs: counters,
+// queues, counts, tile words, events, the pinned mirror; set up, read and scanned by bhs_host_side.inc.h) and its staging
+// copies are buffers of its own.  bhs_spgemm_add runs the ordinary multiply and then either adds into its valC in place
 // (D inside the pattern of A·B) or writes the sum to a second set of arrays that the getters serve until the next multiply
 // (h->sumActive); the pipeline's own C arrays are never moved.
 
@@ -16,114 +17,54 @@ struct AddIn {
 
 int add_prepare(bhs_handle* h, int m)
 {
-    h->ls = h->stream;
-    if (!h->addEv[0]) {
-        BHS_HIP(hipEventCreate(&h->addEv[0]));
-        BHS_HIP(hipEventCreate(&h->addEv[1]));
-    }
-    if (!h->addHost) BHS_HIP(hipHostMalloc((void**)&h->addHost, sizeof(int) * AD_INTS, hipHostMallocDefault));
-    BHS_TRY(ensure(h, h->addCtl, sizeof(int) * AD_INTS));
-    BHS_TRY(ensure(h, h->addQueue, sizeof(int) * (size_t)kAddBins * (size_t)std::max(m, 1)));
-    BHS_TRY(ensure(h, h->addCnt, sizeof(int) * ((size_t)m + 1)));
-    BHS_TRY(ensure(h, h->addTiles, sizeof(unsigned long long) * (size_t)std::max((m + kScan1Tile - 1) / kScan1Tile, 1), true));
-    return BHS_SUCCESS;
+    return side_prepare(h, h->addWs, AD_INTS, sizeof(int) * (size_t)kAddBins * (size_t)std::max(m, 1), (size_t)m + 1);
 }
 
-void add_reset_stats(bhs_handle* h)
-{
-    h->evUsed = 0;
-    for (auto& s : h->stats) { s.launches = 0; s.ms = 0; s.rows = s.products = s.nnz_out = s.nnzA_rows = 0; }
-}
-
-int add_collect(bhs_handle* h, size_t evFirst)
-{
-    for (size_t i = evFirst; i < h->evUsed; ++i) {
-        float ms = 0;
-        BHS_HIP(hipEventElapsedTime(&ms, h->evPool[i].a, h->evPool[i].b));
-        h->stats[h->evPool[i].stat].ms += ms;
-    }
-    return BHS_SUCCESS;
-}
-
-// the control words to the host: the one round trip of an add
-int add_read_ctl(bhs_handle* h)
-{
-    BHS_HIP(hipMemcpyAsync(h->addHost, h->addCtl.p, sizeof(int) * AD_INTS, hipMemcpyDeviceToHost, h->stream));
-    BHS_TRY(wait_stream(h));
-    return BHS_SUCCESS;
-}
+constexpr SideScanWords kAddScanWords = {AD_TICKET, AD_SCANTOTAL, AD_SCANBINS, AD_MAXCNT};
 
 // validity of one matrix alone (bhs_spgemm_add: D before the multiply)
 int add_check(bhs_handle* h, int m, int n, int nnz, const int* P, const int* J)
 {
-    int* ctl = (int*)h->addCtl.p;
+    int* ctl = (int*)h->addWs.ctl.p;
     BHS_HIP(hipMemsetAsync(ctl, 0, sizeof(int) * AD_INTS, h->stream));
     BHS_TRY(timed(h, "add_count", m, [&] {
         const long long gs = std::max<long long>(1, ((long long)m + 15) / 16);
         hipLaunchKernelGGL(k_add_check, dim3((unsigned)gs), dim3(256), 0, h->stream, m, n, nnz, P, J, ctl);
         return 1;
     }));
-    BHS_TRY(add_read_ctl(h));
-    return h->addHost[AD_ERR] ? (int)BHS_ERR_INVALID_ARG : (int)BHS_SUCCESS;
+    BHS_TRY(side_read_ctl(h, h->addWs, AD_INTS));
+    return h->addWs.host[AD_ERR] ? (int)BHS_ERR_INVALID_ARG : (int)BHS_SUCCESS;
 }
 
-// The count pass and its round trip.  Afterwards h->addCnt holds the rows' counts, h->addQueue the bins' rows, h->addHost
+// The count pass and its round trip.  Afterwards h->addWs.cnt holds the rows' counts, h->addWs.queue the bins' rows, h->addWs.host
 // the control words; *nnzZ the size of the union.  ypos (may be NULL): where in X every entry of Y sits.
 int add_count(bhs_handle* h, const AddIn& in, int* ypos, long long* nnzZ)
 {
-    int* ctl = (int*)h->addCtl.p;
+    int* ctl = (int*)h->addWs.ctl.p;
     BHS_HIP(hipMemsetAsync(ctl, 0, sizeof(int) * AD_INTS, h->stream));
     int stat = 0;
     BHS_TRY(timed(h, "add_count", in.m, [&] {
         const long long gs = std::max<long long>(1, ((long long)in.m + kAddCountRows - 1) / kAddCountRows);
         hipLaunchKernelGGL(k_add_count, dim3((unsigned)gs), dim3(256), 0, h->stream, in.m, in.n, in.nnzX, in.Xp, in.Xj, in.nnzY,
-                           in.Yp, in.Yj, (int*)h->addCnt.p, ypos, ctl, (int*)h->addQueue.p);
+                           in.Yp, in.Yj, (int*)h->addWs.cnt.p, ypos, ctl, (int*)h->addWs.queue.p);
         return 1;
     }, &stat));
-    BHS_TRY(add_read_ctl(h));
-    if (h->addHost[AD_ERR]) return BHS_ERR_INVALID_ARG;
+    BHS_TRY(side_read_ctl(h, h->addWs, AD_INTS));
+    if (h->addWs.host[AD_ERR]) return BHS_ERR_INVALID_ARG;
     unsigned long long total = 0;
-    memcpy(&total, h->addHost + AD_TOTAL, 8);
+    memcpy(&total, h->addWs.host + AD_TOTAL, 8);
     if (total > 0x7fffffffull) return BHS_ERR_NNZ_OVERFLOW;
     h->stats[stat].nnz_out += (int64_t)total;
     *nnzZ = (long long)total;
     return BHS_SUCCESS;
 }
 
-// rowPtrZ from the counts of add_count: the library's one-pass scan over h->addCnt (tile words and epoch of the add's own),
-// then a copy to where the row pointer is wanted
-int add_scan(bhs_handle* h, int m, const int* anyRowPtr, int* d_rowPtrZ)
-{
-    int* ctl = (int*)h->addCtl.p;
-    int* cnt = (int*)h->addCnt.p;
-    const int nTiles = (m + kScan1Tile - 1) / kScan1Tile;
-    if (nTiles == 0) {
-        BHS_HIP(hipMemsetAsync(cnt, 0, sizeof(int), h->stream));
-    } else {
-        h->addEpoch = (h->addEpoch + 1) & 0x3FFFFu;
-        if (h->addEpoch == 0) {                                      // (see scan_rowptr)
-            BHS_HIP(hipMemsetAsync(h->addTiles.p, 0, sizeof(unsigned long long) * (size_t)nTiles, h->stream));
-            h->addEpoch = 1;
-        }
-        BinSpec none;                                                // (no bins: the scan's histogram stays empty)
-        memset(&none, 0, sizeof(none));
-        BHS_TRY(timed(h, "add_scan", m, [&] {
-            hipLaunchKernelGGL(k_scan_onepass, dim3((unsigned)nTiles), dim3(kScan1Block), 0, h->stream, m, cnt, anyRowPtr,
-                               (unsigned long long*)h->addTiles.p, h->addEpoch, ctl + AD_TICKET, (long long*)(ctl + AD_SCANTOTAL),
-                               ctl + AD_SCANBINS, none, ctl + AD_MAXCNT, (const int*)nullptr);
-            return 1;
-        }));
-    }
-    BHS_HIP(hipMemcpyAsync(d_rowPtrZ, cnt, sizeof(int) * ((size_t)m + 1), hipMemcpyDeviceToDevice, h->stream));
-    return BHS_SUCCESS;
-}
-
-// the fill pass on the queues and bin counts in h->addQueue / h->addHost
+// the fill pass on the queues and bin counts in h->addWs.queue / h->addWs.host
 int add_fill(bhs_handle* h, const AddIn& in, double alpha, double beta, const int* Zp, int* Zj, value_t* Zx)
 {
     const int m = in.m;
-    const int* queue = (const int*)h->addQueue.p;
-    const int* count = h->addHost + AD_COUNT;
+    const int* queue = (const int*)h->addWs.queue.p;
+    const int* count = h->addWs.host + AD_COUNT;
     if (count[kAddShort]) {
         const int nq = count[kAddShort];
         BHS_TRY(timed(h, "add_short", nq, [&] {
@@ -151,16 +92,6 @@ int add_fill(bhs_handle* h, const AddIn& in, double alpha, double beta, const in
     return BHS_SUCCESS;
 }
 
-int add_elapsed(bhs_handle* h, double* ms_out)
-{
-    if (ms_out) {
-        float ms = 0;
-        BHS_HIP(hipEventElapsedTime(&ms, h->addEv[0], h->addEv[1]));
-        *ms_out = ms;
-    }
-    return BHS_SUCCESS;
-}
-
 bool add_args_ok(int m, int n, int nnzX, const int* Xp, const int* Xj, int nnzY, const int* Yp, const int* Yj)
 {
     return m >= 0 && n >= 0 && nnzX >= 0 && nnzY >= 0 && Xp && Yp && (nnzX == 0 || Xj) && (nnzY == 0 || Yj);
@@ -169,37 +100,37 @@ bool add_args_ok(int m, int n, int nnzX, const int* Xp, const int* Xj, int nnzY,
 int add_symbolic_run(bhs_handle* h, const AddIn& in, int* d_rowPtrZ, int* nnzZ_out, int* inside_out)
 {
     BHS_TRY(add_prepare(h, in.m));
-    add_reset_stats(h);
+    side_reset_stats(h);
     long long nnzZ = 0;
     BHS_TRY(add_count(h, in, nullptr, &nnzZ));
-    BHS_TRY(add_scan(h, in.m, in.Xp, d_rowPtrZ));
+    BHS_TRY(side_scan(h, h->addWs, "add_scan", kAddScanWords, in.m, in.Xp, d_rowPtrZ));
     BHS_TRY(wait_stream(h));
-    BHS_TRY(add_collect(h, 0));
+    BHS_TRY(side_collect(h, 0));
     if (nnzZ_out) *nnzZ_out = (int)nnzZ;
-    if (inside_out) *inside_out = h->addHost[AD_OUTSIDE] ? 0 : 1;
+    if (inside_out) *inside_out = h->addWs.host[AD_OUTSIDE] ? 0 : 1;
     return BHS_SUCCESS;
 }
 
 int add_numeric_run(bhs_handle* h, const AddIn& in, double alpha, double beta, const int* Zp, int* Zj, value_t* Zx, double* ms_out)
 {
     BHS_TRY(add_prepare(h, in.m));
-    add_reset_stats(h);
-    int* ctl = (int*)h->addCtl.p;
-    BHS_HIP(hipEventRecord(h->addEv[0], h->stream));
+    side_reset_stats(h);
+    int* ctl = (int*)h->addWs.ctl.p;
+    BHS_TRY(side_begin(h, h->addWs));
     BHS_HIP(hipMemsetAsync(ctl, 0, sizeof(int) * AD_INTS, h->stream));
     BHS_TRY(timed(h, "add_bin", in.m, [&] {
         const long long gs = std::max<long long>(1, ((long long)in.m + 255) / 256);
         hipLaunchKernelGGL(k_add_bin, dim3((unsigned)gs), dim3(256), 0, h->stream, in.m, in.nnzX, in.Xp, in.nnzY, in.Yp, Zp, ctl,
-                           (int*)h->addQueue.p);
+                           (int*)h->addWs.queue.p);
         return 1;
     }));
-    BHS_TRY(add_read_ctl(h));
-    if (h->addHost[AD_ERR]) return BHS_ERR_INVALID_ARG;
+    BHS_TRY(side_read_ctl(h, h->addWs, AD_INTS));
+    if (h->addWs.host[AD_ERR]) return BHS_ERR_INVALID_ARG;
     BHS_TRY(add_fill(h, in, alpha, beta, Zp, Zj, Zx));
-    BHS_HIP(hipEventRecord(h->addEv[1], h->stream));
+    BHS_TRY(side_end(h, h->addWs));
     BHS_TRY(wait_stream(h));
-    BHS_TRY(add_elapsed(h, ms_out));
-    return add_collect(h, 0);
+    BHS_TRY(side_elapsed(h, h->addWs, ms_out));
+    return side_collect(h, 0);
 }
 
 // the add behind a finished multiply: X = the C of the pipeline, Y = D
@@ -218,10 +149,10 @@ int add_to_product(bhs_handle* h, double alpha, double beta, int nnzD, const val
         BHS_TRY(ensure(h, h->addPos, sizeof(int) * (size_t)std::max(nnzD, 1)));
         ypos = (int*)h->addPos.p;
     }
-    BHS_HIP(hipEventRecord(h->addEv[0], h->stream));
+    BHS_TRY(side_begin(h, h->addWs));
     long long nnzZ = 0;
     BHS_TRY(add_count(h, in, ypos, &nnzZ));
-    const bool inside = !h->addHost[AD_OUTSIDE];
+    const bool inside = !h->addWs.host[AD_OUTSIDE];
     if (inside && h->addInplace) {
         if (nnzD > 0 || alpha != 1.0) {
             int stat = 0;
@@ -248,18 +179,18 @@ int add_to_product(bhs_handle* h, double alpha, double beta, int nnzD, const val
         BHS_TRY(ensure(h, h->sumCp, sizeof(int) * ((size_t)m + 1)));
         BHS_TRY(ensure(h, h->sumCj, sizeof(int) * (size_t)std::max<long long>(nnzZ, 1)));
         BHS_TRY(ensure(h, h->sumCx, sizeof(value_t) * (size_t)std::max<long long>(nnzZ, 1)));
-        BHS_TRY(add_scan(h, m, in.Xp, (int*)h->sumCp.p));
+        BHS_TRY(side_scan(h, h->addWs, "add_scan", kAddScanWords, m, in.Xp, (int*)h->sumCp.p));
         BHS_TRY(add_fill(h, in, alpha, beta, (const int*)h->sumCp.p, (int*)h->sumCj.p, (value_t*)h->sumCx.p));
         h->addInplaceUsed = 0;
     }
-    BHS_HIP(hipEventRecord(h->addEv[1], h->stream));
+    BHS_TRY(side_end(h, h->addWs));
     BHS_TRY(wait_stream(h));
     if (!h->addInplaceUsed) {                                        // from here on the getters serve the sum
         h->sumActive = true;
         h->sumNnz = nnzZ;
     }
-    BHS_TRY(add_elapsed(h, ms_out));
-    return add_collect(h, evFirst);
+    BHS_TRY(side_elapsed(h, h->addWs, ms_out));
+    return side_collect(h, evFirst);
 }
 
 int spgemm_add_check(bhs_handle* h, int nnzD, const void* valD, const int* rowPtrD, const int* colIndD)
@@ -275,7 +206,7 @@ int spgemm_add_run(bhs_handle* h, double alpha, double beta, int nnzD, const val
                    int* rowPtrC_out, int64_t* nnzCt_out, int* nnzC_out, double* ms_out)
 {
     BHS_TRY(add_prepare(h, h->m));
-    add_reset_stats(h);
+    side_reset_stats(h);
     BHS_TRY(add_check(h, h->m, h->n, nnzD, dDp, dDj));               // an invalid D: nothing has been started, the last C stands
     double stage[4] = {0, 0, 0, 0};
     BHS_TRY(bhs_spgemm(h, rowPtrC_out, nnzCt_out, nullptr, stage));
@@ -299,14 +230,11 @@ int bhs_csr_add_symbolic_device(bhs_handle* h, int m, int n, int nnzX, const int
 {
     if (!h || h->ps.open || !d_rowPtrZ || !add_args_ok(m, n, nnzX, d_rowPtrX, d_colIndX, nnzY, d_rowPtrY, d_colIndY))
         return BHS_ERR_INVALID_ARG;
-    BHS_HIP(hipSetDevice(h->device));
     AddIn in;
     in.m = m; in.n = n;
     in.nnzX = nnzX; in.Xp = d_rowPtrX; in.Xj = d_colIndX; in.Xx = nullptr;
     in.nnzY = nnzY; in.Yp = d_rowPtrY; in.Yj = d_colIndY; in.Yx = nullptr;
-    const int rc = add_symbolic_run(h, in, d_rowPtrZ, nnzZ_out, y_inside_x_out);
-    if (rc) settle(h);
-    return rc;
+    return guarded(h, [&] { return add_symbolic_run(h, in, d_rowPtrZ, nnzZ_out, y_inside_x_out); });
 }
 
 int bhs_csr_add_numeric_device(bhs_handle* h, int m, int n, double alpha, int nnzX, const bhs_value_t* d_valX, const int* d_rowPtrX,
@@ -316,45 +244,40 @@ int bhs_csr_add_numeric_device(bhs_handle* h, int m, int n, double alpha, int nn
     if (!h || h->ps.open || !d_rowPtrZ || !add_args_ok(m, n, nnzX, d_rowPtrX, d_colIndX, nnzY, d_rowPtrY, d_colIndY))
         return BHS_ERR_INVALID_ARG;
     if ((nnzX > 0 && !d_valX) || (nnzY > 0 && !d_valY) || ((nnzX > 0 || nnzY > 0) && (!d_colIndZ || !d_valZ))) return BHS_ERR_INVALID_ARG;
-    BHS_HIP(hipSetDevice(h->device));
     AddIn in;
     in.m = m; in.n = n;
     in.nnzX = nnzX; in.Xp = d_rowPtrX; in.Xj = d_colIndX; in.Xx = (const value_t*)d_valX;
     in.nnzY = nnzY; in.Yp = d_rowPtrY; in.Yj = d_colIndY; in.Yx = (const value_t*)d_valY;
-    const int rc = add_numeric_run(h, in, alpha, beta, d_rowPtrZ, d_colIndZ, (value_t*)d_valZ, ms_out);
-    if (rc) settle(h);
-    return rc;
+    return guarded(h, [&] { return add_numeric_run(h, in, alpha, beta, d_rowPtrZ, d_colIndZ, (value_t*)d_valZ, ms_out); });
 }
 
 int bhs_spgemm_add_device(bhs_handle* h, double alpha, double beta, int nnzD, const bhs_value_t* d_valD, const int* d_rowPtrD,
                           const int* d_colIndD, int* rowPtrC_out, int64_t* nnzCt_out, int* nnzC_out, double ms_out[2])
 {
     BHS_TRY(spgemm_add_check(h, nnzD, d_valD, d_rowPtrD, d_colIndD));
-    BHS_HIP(hipSetDevice(h->device));
-    const int rc = spgemm_add_run(h, alpha, beta, nnzD, (const value_t*)d_valD, d_rowPtrD, d_colIndD, rowPtrC_out, nnzCt_out,
-                                  nnzC_out, ms_out);
-    if (rc) settle(h);
-    return rc;
+    return guarded(h, [&] {
+        return spgemm_add_run(h, alpha, beta, nnzD, (const value_t*)d_valD, d_rowPtrD, d_colIndD, rowPtrC_out, nnzCt_out, nnzC_out,
+                              ms_out);
+    });
 }
 
 int bhs_spgemm_add(bhs_handle* h, double alpha, double beta, int nnzD, const bhs_value_t* valD, const int* rowPtrD,
                    const int* colIndD, int* rowPtrC_out, int64_t* nnzCt_out, int* nnzC_out, double ms_out[2])
 {
     BHS_TRY(spgemm_add_check(h, nnzD, valD, rowPtrD, colIndD));
-    BHS_HIP(hipSetDevice(h->device));
-    BHS_TRY(ensure(h, h->addD[0], sizeof(int) * ((size_t)h->m + 1)));
-    BHS_TRY(ensure(h, h->addD[1], sizeof(int) * (size_t)std::max(nnzD, 1)));
-    BHS_TRY(ensure(h, h->addD[2], sizeof(value_t) * (size_t)std::max(nnzD, 1)));
-    BHS_HIP(hipMemcpyAsync(h->addD[0].p, rowPtrD, sizeof(int) * ((size_t)h->m + 1), hipMemcpyHostToDevice, h->stream));
-    if (nnzD) {
-        BHS_HIP(hipMemcpyAsync(h->addD[1].p, colIndD, sizeof(int) * (size_t)nnzD, hipMemcpyHostToDevice, h->stream));
-        BHS_HIP(hipMemcpyAsync(h->addD[2].p, valD, sizeof(value_t) * (size_t)nnzD, hipMemcpyHostToDevice, h->stream));
-    }
-    BHS_HIP(hipStreamSynchronize(h->stream));                        // (the caller's arrays are free again)
-    const int rc = spgemm_add_run(h, alpha, beta, nnzD, (const value_t*)h->addD[2].p, (const int*)h->addD[0].p,
-                                  (const int*)h->addD[1].p, rowPtrC_out, nnzCt_out, nnzC_out, ms_out);
-    if (rc) settle(h);
-    return rc;
+    return guarded(h, [&]() -> int {
+        BHS_TRY(ensure(h, h->addD[0], sizeof(int) * ((size_t)h->m + 1)));
+        BHS_TRY(ensure(h, h->addD[1], sizeof(int) * (size_t)std::max(nnzD, 1)));
+        BHS_TRY(ensure(h, h->addD[2], sizeof(value_t) * (size_t)std::max(nnzD, 1)));
+        BHS_HIP(hipMemcpyAsync(h->addD[0].p, rowPtrD, sizeof(int) * ((size_t)h->m + 1), hipMemcpyHostToDevice, h->stream));
+        if (nnzD) {
+            BHS_HIP(hipMemcpyAsync(h->addD[1].p, colIndD, sizeof(int) * (size_t)nnzD, hipMemcpyHostToDevice, h->stream));
+            BHS_HIP(hipMemcpyAsync(h->addD[2].p, valD, sizeof(value_t) * (size_t)nnzD, hipMemcpyHostToDevice, h->stream));
+        }
+        BHS_HIP(hipStreamSynchronize(h->stream));                    // (the caller's arrays are free again)
+        return spgemm_add_run(h, alpha, beta, nnzD, (const value_t*)h->addD[2].p, (const int*)h->addD[0].p, (const int*)h->addD[1].p,
+                              rowPtrC_out, nnzCt_out, nnzC_out, ms_out);
+    });
 }
 
 }  // extern "C"

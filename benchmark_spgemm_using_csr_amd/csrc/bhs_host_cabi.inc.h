@@ -113,26 +113,12 @@ int bhs_destroy(bhs_handle* h)
     release(h->bWin); release(h->bWinTab); release(h->bWinSpill);
     release(h->hubBits); release(h->hubRank); release(h->hubItems); release(h->hubSeg); release(h->hubCtl);
     release(h->spaBits);
-    release(h->maskCtl); release(h->maskQueue);
-    for (int i = 0; i < 3; ++i) release(h->maskM[i]);
-    release(h->addCtl); release(h->addQueue); release(h->addCnt); release(h->addTiles); release(h->addPos); release(h->sumCp);
-    for (int i = 0; i < 3; ++i) release(h->addD[i]);
-    release(h->selCtl); release(h->selQueue); release(h->selCnt); release(h->selTiles);
-    if (h->selHost) (void)hipHostFree(h->selHost);
-    for (int i = 0; i < 2; ++i) if (h->selEv[i]) (void)hipEventDestroy(h->selEv[i]);
-    release(h->trCtl); release(h->trCnt); release(h->trCur); release(h->trQueue); release(h->trWin); release(h->trKeys); release(h->trTiles);
-    if (h->trHost) (void)hipHostFree(h->trHost);
-    for (int i = 0; i < 2; ++i) if (h->trEv[i]) (void)hipEventDestroy(h->trEv[i]);
-    release(h->exCtl); release(h->exCnt); release(h->exQueue); release(h->exInv); release(h->exKeys); release(h->exTiles);
-    if (h->exHost) (void)hipHostFree(h->exHost);
-    for (int i = 0; i < 2; ++i) if (h->exEv[i]) (void)hipEventDestroy(h->exEv[i]);
-    release(h->rdCtl); release(h->rdQueue); release(h->rdAcc); release(h->rdPart);
-    if (h->rdHost) (void)hipHostFree(h->rdHost);
-    for (int i = 0; i < 2; ++i) if (h->rdEv[i]) (void)hipEventDestroy(h->rdEv[i]);
-    if (h->addHost) (void)hipHostFree(h->addHost);
-    for (int i = 0; i < 2; ++i) if (h->addEv[i]) (void)hipEventDestroy(h->addEv[i]);
-    if (h->maskHost) (void)hipHostFree(h->maskHost);
-    for (int i = 0; i < 2; ++i) if (h->maskEv[i]) (void)hipEventDestroy(h->maskEv[i]);
+    release(h->maskWs); release(h->addWs); release(h->selWs); release(h->trWs); release(h->exWs); release(h->rdWs);
+    for (int i = 0; i < 3; ++i) { release(h->maskM[i]); release(h->addD[i]); }
+    release(h->addPos); release(h->sumCp);
+    release(h->trCur); release(h->trWin); release(h->trKeys);
+    release(h->exInv); release(h->exKeys);
+    release(h->rdAcc); release(h->rdPart);
     if (h->hostSmall) (void)hipHostFree(h->hostSmall);
     if (h->hostRowPtr) (void)hipHostFree(h->hostRowPtr);
     for (int i = 0; i < bhs_handle::kBinStreams; ++i) {

@@ -2,9 +2,10 @@
 // bhs_extract.hip.h)
 // (A part of bhsparse_hip.hip's translation unit: included there last, after the semiring multiply.)
 //
-// Like the add, the selection and the transpose the extraction works beside the pipeline: counters, queues, tile words, epoch,
-// events, the pinned mirror, the column map and the scratch keys are buffers of its own from the grow-only pool.  It binds
-// nothing and serves nothing through the getters: every output array is the caller's.
+// Like the add, the selection and the transpose the extraction works beside the pipeline: its workspace (h->exWs: counters,
+// queues, counts, tile words, events, the pinned mirror; set up, read and scanned by bhs_host_side.inc.h), the column map and
+// the scratch keys are buffers of its own from the grow-only pool.  It binds nothing and serves nothing through the getters:
+// every output array is the caller's.
 //
 // The kernels' header is included here, not among the translation unit's kernel headers (as bhs_host_semiring.inc.h does).
 #include "bhs_extract.hip.h"
@@ -20,34 +21,19 @@ struct ExIn {
 
 int ex_prepare(bhs_handle* h, const ExIn& in)
 {
-    h->ls = h->stream;
-    if (!h->exEv[0]) {
-        BHS_HIP(hipEventCreate(&h->exEv[0]));
-        BHS_HIP(hipEventCreate(&h->exEv[1]));
-    }
-    if (!h->exHost) BHS_HIP(hipHostMalloc((void**)&h->exHost, sizeof(int) * EX_INTS, hipHostMallocDefault));
-    BHS_TRY(ensure(h, h->exCtl, sizeof(int) * EX_INTS));
-    BHS_TRY(ensure(h, h->exQueue, sizeof(int) * (size_t)kExBins * (size_t)std::max(in.mI, 1)));
-    BHS_TRY(ensure(h, h->exCnt, sizeof(int) * ((size_t)in.mI + 1)));
-    BHS_TRY(ensure(h, h->exTiles, sizeof(unsigned long long) * (size_t)std::max((in.mI + kScan1Tile - 1) / kScan1Tile, 1), true));
+    BHS_TRY(side_prepare(h, h->exWs, EX_INTS, sizeof(int) * (size_t)kExBins * (size_t)std::max(in.mI, 1), (size_t)in.mI + 1));
     if (in.cols) BHS_TRY(ensure(h, h->exInv, sizeof(int) * (size_t)std::max(in.n, 1)));
     return BHS_SUCCESS;
 }
 
-// the control words to the host: the one round trip of a symbolic call, the first of a numeric one
-int ex_read_ctl(bhs_handle* h, int ints = EX_HEAD)
-{
-    BHS_HIP(hipMemcpyAsync(h->exHost, h->exCtl.p, sizeof(int) * (size_t)ints, hipMemcpyDeviceToHost, h->stream));
-    BHS_TRY(wait_stream(h));
-    return BHS_SUCCESS;
-}
+constexpr SideScanWords kExScanWords = {EX_TICKET, EX_SCANTOTAL, EX_SCANBINS, EX_MAXCNT};
 
-// Validation, the column map, the count pass and their round trip.  Afterwards h->exCnt holds the Z rows' counts, h->exQueue
-// the bins' rows, h->exHost the control words; *nnzZ the number of survivors.  Zp (may be NULL): a row pointer of Z that
+// Validation, the column map, the count pass and their round trip.  Afterwards h->exWs.cnt holds the Z rows' counts, h->exWs.queue
+// the bins' rows, h->exWs.host the control words; *nnzZ the number of survivors.  Zp (may be NULL): a row pointer of Z that
 // every count must agree with.  Nothing caller-owned is written.
 int ex_count(bhs_handle* h, const ExIn& in, const int* Zp, int nnzZ, long long* total_out)
 {
-    int* ctl = (int*)h->exCtl.p;
+    int* ctl = (int*)h->exWs.ctl.p;
     const int* inv = in.cols ? (const int*)h->exInv.p : nullptr;
     BHS_HIP(hipMemsetAsync(ctl, 0, sizeof(int) * EX_INTS, h->stream));
     if (in.rows || in.cols) {
@@ -64,60 +50,31 @@ int ex_count(bhs_handle* h, const ExIn& in, const int* Zp, int nnzZ, long long* 
     BHS_TRY(timed(h, "extract_count", in.mI, [&] {
         const long long gs = std::max<long long>(1, ((long long)in.mI + kExRows - 1) / kExRows);
         hipLaunchKernelGGL(k_ex_count, dim3((unsigned)gs), dim3(256), 0, h->stream, in.m, in.n, in.nnzX, in.Xp, in.Xj, in.mI, in.rows,
-                           inv, Zp, nnzZ, (int*)h->exCnt.p, ctl, (int*)h->exQueue.p);
+                           inv, Zp, nnzZ, (int*)h->exWs.cnt.p, ctl, (int*)h->exWs.queue.p);
         if (in.nnzX <= kExWaveL) return 1;                           // (no row can be long)
         const long long gl = std::max<long long>(1, std::min<long long>(in.mI, (long long)h->numCU * 8));
         hipLaunchKernelGGL(k_ex_count_long, dim3((unsigned)gl), dim3(256), 0, h->stream, in.m, in.n, in.nnzX, in.Xp, in.Xj, in.mI,
-                           in.rows, inv, Zp, (int*)h->exCnt.p, ctl, (const int*)h->exQueue.p);
+                           in.rows, inv, Zp, (int*)h->exWs.cnt.p, ctl, (const int*)h->exWs.queue.p);
         return 2;
     }, &stat));
-    BHS_TRY(ex_read_ctl(h));
-    if (h->exHost[EX_ERR]) return BHS_ERR_INVALID_ARG;
+    BHS_TRY(side_read_ctl(h, h->exWs, EX_HEAD));                 // (the one round trip of a symbolic call, the first of a numeric one)
+    if (h->exWs.host[EX_ERR]) return BHS_ERR_INVALID_ARG;
     unsigned long long total = 0;
-    memcpy(&total, h->exHost + EX_TOTAL, 8);
+    memcpy(&total, h->exWs.host + EX_TOTAL, 8);
     h->stats[stat].nnz_out += (int64_t)total;
     *total_out = (long long)total;
     return BHS_SUCCESS;
 }
 
-// rowPtrZ from the counts of ex_count: the library's one-pass scan over h->exCnt (tile words and epoch of the extraction's
-// own), then a copy to where the row pointer is wanted
-int ex_scan(bhs_handle* h, int mI, int* d_rowPtrZ)
-{
-    int* ctl = (int*)h->exCtl.p;
-    int* cnt = (int*)h->exCnt.p;
-    const int nTiles = (mI + kScan1Tile - 1) / kScan1Tile;
-    if (nTiles == 0) {
-        BHS_HIP(hipMemsetAsync(cnt, 0, sizeof(int), h->stream));
-    } else {
-        h->exEpoch = (h->exEpoch + 1) & 0x3FFFFu;
-        if (h->exEpoch == 0) {                                       // (see scan_rowptr)
-            BHS_HIP(hipMemsetAsync(h->exTiles.p, 0, sizeof(unsigned long long) * (size_t)nTiles, h->stream));
-            h->exEpoch = 1;
-        }
-        BinSpec none;                                                // (no bins: the scan's histogram stays empty)
-        memset(&none, 0, sizeof(none));
-        BHS_TRY(timed(h, "extract_scan", mI, [&] {
-            // (the scan reads a row pointer of mI + 1 ints for its bins; without bins any such array will do: the queues)
-            hipLaunchKernelGGL(k_scan_onepass, dim3((unsigned)nTiles), dim3(kScan1Block), 0, h->stream, mI, cnt, (const int*)h->exQueue.p,
-                               (unsigned long long*)h->exTiles.p, h->exEpoch, ctl + EX_TICKET, (long long*)(ctl + EX_SCANTOTAL),
-                               ctl + EX_SCANBINS, none, ctl + EX_MAXCNT, (const int*)nullptr);
-            return 1;
-        }));
-    }
-    BHS_HIP(hipMemcpyAsync(d_rowPtrZ, cnt, sizeof(int) * ((size_t)mI + 1), hipMemcpyDeviceToDevice, h->stream));
-    return BHS_SUCCESS;
-}
-
-// the fill pass on the queues and bin counts in h->exQueue / h->exHost
+// the fill pass on the queues and bin counts in h->exWs.queue / h->exWs.host
 int ex_fill(bhs_handle* h, const ExIn& in, int nnzZ, const int* Zp, int* Zj, value_t* Zx, int* perm)
 {
     const int mI = in.mI;
-    const int* queue = (const int*)h->exQueue.p;
+    const int* queue = (const int*)h->exWs.queue.p;
     const int* inv = in.cols ? (const int*)h->exInv.p : nullptr;
     int count[kExBins];
-    for (int b = 0; b < kExBins; ++b) count[b] = h->exHost[EX_COUNT + b];
-    int* ctl = (int*)h->exCtl.p;
+    for (int b = 0; b < kExBins; ++b) count[b] = h->exWs.host[EX_COUNT + b];
+    int* ctl = (int*)h->exWs.ctl.p;
     if (count[kExShort]) {
         const int nq = count[kExShort];
         BHS_TRY(timed(h, "extract_short", nq, [&] {
@@ -152,13 +109,14 @@ int ex_fill(bhs_handle* h, const ExIn& in, int nnzZ, const int* Zp, int* Zj, val
 int ex_symbolic_run(bhs_handle* h, const ExIn& in, int* d_rowPtrZ, int* nnzZ_out)
 {
     BHS_TRY(ex_prepare(h, in));
-    add_reset_stats(h);
+    side_reset_stats(h);
     long long nnzZ = 0;
     BHS_TRY(ex_count(h, in, nullptr, 0, &nnzZ));
     if (nnzZ > 0x7fffffffLL) return BHS_ERR_NNZ_OVERFLOW;            // (nothing caller-owned has been written)
-    BHS_TRY(ex_scan(h, in.mI, d_rowPtrZ));
+    // (without bins any array of mI + 1 ints will do for the scan's row pointer: the queues)
+    BHS_TRY(side_scan(h, h->exWs, "extract_scan", kExScanWords, in.mI, (const int*)h->exWs.queue.p, d_rowPtrZ));
     BHS_TRY(wait_stream(h));
-    BHS_TRY(add_collect(h, 0));
+    BHS_TRY(side_collect(h, 0));
     if (nnzZ_out) *nnzZ_out = (int)nnzZ;
     return BHS_SUCCESS;
 }
@@ -166,23 +124,19 @@ int ex_symbolic_run(bhs_handle* h, const ExIn& in, int* d_rowPtrZ, int* nnzZ_out
 int ex_numeric_run(bhs_handle* h, const ExIn& in, int nnzZ, const int* Zp, int* Zj, value_t* Zx, int* perm, double* ms_out)
 {
     BHS_TRY(ex_prepare(h, in));
-    add_reset_stats(h);
-    BHS_HIP(hipEventRecord(h->exEv[0], h->stream));
+    side_reset_stats(h);
+    BHS_TRY(side_begin(h, h->exWs));
     long long total = 0;
     BHS_TRY(ex_count(h, in, Zp, nnzZ, &total));                      // (every row's survivors are what rowPtrZ says, or nothing is written)
     if (total != (long long)nnzZ) return BHS_ERR_INVALID_ARG;
     BHS_TRY(ex_fill(h, in, nnzZ, Zp, Zj, Zx, perm));
-    BHS_HIP(hipEventRecord(h->exEv[1], h->stream));
-    BHS_TRY(ex_read_ctl(h, EX_INTS));
-    if (ms_out) {
-        float ms = 0;
-        BHS_HIP(hipEventElapsedTime(&ms, h->exEv[0], h->exEv[1]));
-        *ms_out = ms;
-    }
-    BHS_TRY(add_collect(h, 0));
-    if (h->exHost[EX_ERR]) return BHS_ERR_INVALID_ARG;
+    BHS_TRY(side_end(h, h->exWs));
+    BHS_TRY(side_read_ctl(h, h->exWs, EX_INTS));
+    BHS_TRY(side_elapsed(h, h->exWs, ms_out));
+    BHS_TRY(side_collect(h, 0));
+    if (h->exWs.host[EX_ERR]) return BHS_ERR_INVALID_ARG;
     long long reordered = 0;
-    for (int s = 0; s < kExReordSlots; ++s) reordered += h->exHost[EX_REORD + s * kExReordStride];
+    for (int s = 0; s < kExReordSlots; ++s) reordered += h->exWs.host[EX_REORD + s * kExReordStride];
     h->exReordered = reordered;
     return BHS_SUCCESS;
 }
@@ -231,13 +185,10 @@ int bhs_csr_extract_symbolic_device(bhs_handle* h, int m, int n, int nnzX, const
     const ExSpan ins[4] = {{d_rowPtrX, sizeof(int) * ((size_t)m + 1)}, {d_colIndX, sizeof(int) * (size_t)nnzX},
                            {d_rows, sizeof(int) * (size_t)mI}, {d_cols, sizeof(int) * (size_t)nJ}};
     if (ex_aliased(outs, 1, ins, 4)) return BHS_ERR_INVALID_ARG;    // (outputs must not overlap inputs)
-    BHS_HIP(hipSetDevice(h->device));
     ExIn in;
     in.m = m; in.n = n; in.nnzX = nnzX; in.Xp = d_rowPtrX; in.Xj = d_colIndX; in.Xx = nullptr;
     in.mI = mI; in.rows = d_rows; in.nJ = nJ; in.cols = d_cols;
-    const int rc = ex_symbolic_run(h, in, d_rowPtrZ, nnzZ_out);
-    if (rc) settle(h);
-    return rc;
+    return guarded(h, [&] { return ex_symbolic_run(h, in, d_rowPtrZ, nnzZ_out); });
 }
 
 int bhs_csr_extract_numeric_device(bhs_handle* h, int m, int n, int nnzX, const bhs_value_t* d_valX, const int* d_rowPtrX,
@@ -252,13 +203,10 @@ int bhs_csr_extract_numeric_device(bhs_handle* h, int m, int n, int nnzX, const 
                            {d_valX, sizeof(value_t) * (size_t)nnzX}, {d_rows, sizeof(int) * (size_t)mI},
                            {d_cols, sizeof(int) * (size_t)nJ}, {d_rowPtrZ, sizeof(int) * ((size_t)mI + 1)}};
     if (ex_aliased(outs, 3, ins, 6)) return BHS_ERR_INVALID_ARG;    // (outputs must not overlap inputs or one another)
-    BHS_HIP(hipSetDevice(h->device));
     ExIn in;
     in.m = m; in.n = n; in.nnzX = nnzX; in.Xp = d_rowPtrX; in.Xj = d_colIndX; in.Xx = (const value_t*)d_valX;
     in.mI = mI; in.rows = d_rows; in.nJ = nJ; in.cols = d_cols;
-    const int rc = ex_numeric_run(h, in, nnzZ, d_rowPtrZ, d_colIndZ, (value_t*)d_valZ, d_perm, ms_out);
-    if (rc) settle(h);
-    return rc;
+    return guarded(h, [&] { return ex_numeric_run(h, in, nnzZ, d_rowPtrZ, d_colIndZ, (value_t*)d_valZ, d_perm, ms_out); });
 }
 
 }  // extern "C"

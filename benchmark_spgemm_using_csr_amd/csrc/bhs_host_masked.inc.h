@@ -1,9 +1,9 @@
 // bhs_host_masked.inc.h -- the masked multiply (bhs_spgemm_masked[_device], kernels in bhs_masked.hip.h)
 // (A part of bhsparse_hip.hip's translation unit: included there after the C-ABI of the ordinary multiply.)
 //
-// The call works beside the ordinary multiply, never through it: its counters, queues, events and (host-array entry)
-// staging copies are buffers of its own, so C of the last bhs_spgemm, the pipeline state, the class path's state and the
-// speculative-launch figures stay as they were.  Only the kernel records are replaced: bhs_get_kernel_stats reports
+// The call works beside the ordinary multiply, never through it: its workspace (h->maskWs: counters, queues, events, the
+// pinned mirror; set up and read by bhs_host_side.inc.h) and its (host-array entry) staging copies are buffers of its own,
+// so C of the last bhs_spgemm, the pipeline state, the class path's state and the speculative-launch figures stay as they were.  Only the kernel records are replaced: bhs_get_kernel_stats reports
 // the last call, whichever it was.
 
 namespace {
@@ -61,21 +61,12 @@ int mask_drive(bhs_handle* h, const int* dMp, const int* dMj, int nnzM, value_t*
                double* ms_out)
 {
     const int m = h->m;
-    h->ls = h->stream;
-    if (!keepStats) {
-        h->evUsed = 0;
-        for (auto& s : h->stats) { s.launches = 0; s.ms = 0; s.rows = s.products = s.nnz_out = s.nnzA_rows = 0; }
-    }
+    SideWs& ws = h->maskWs;
+    if (!keepStats) side_reset_stats(h);
     const size_t evFirst = h->evUsed;
-    if (!h->maskEv[0]) {
-        BHS_HIP(hipEventCreate(&h->maskEv[0]));
-        BHS_HIP(hipEventCreate(&h->maskEv[1]));
-    }
-    if (!h->maskHost) BHS_HIP(hipHostMalloc((void**)&h->maskHost, sizeof(int) * MS_INTS, hipHostMallocDefault));
-    BHS_TRY(ensure(h, h->maskCtl, sizeof(int) * MS_INTS));
-    BHS_TRY(ensure(h, h->maskQueue, sizeof(int2) * (size_t)kMaskBins * (size_t)std::max(m, 1)));
-    int* ctl = (int*)h->maskCtl.p;
-    const int2* queue = (const int2*)h->maskQueue.p;
+    BHS_TRY(side_prepare(h, ws, MS_INTS, sizeof(int2) * (size_t)kMaskBins * (size_t)std::max(m, 1), 0));
+    int* ctl = (int*)ws.ctl.p;
+    const int2* queue = (const int2*)ws.queue.p;
     const int cap = 1 << h->maskTableLog2;
     MaskSpec spec;
     spec.shortLM = std::min(kMaskShortLM, cap);
@@ -84,18 +75,17 @@ int mask_drive(bhs_handle* h, const int* dMp, const int* dMj, int nnzM, value_t*
     spec.waveL = cap;
     spec.hubMin = h->maskHubMin;
 
-    BHS_HIP(hipEventRecord(h->maskEv[0], h->stream));
+    BHS_TRY(side_begin(h, ws));
     BHS_HIP(hipMemsetAsync(ctl, 0, sizeof(int) * MS_INTS, h->stream));
     int scanStat = 0;
     BHS_TRY(timed(h, K::family(kMaskFamScan), m, [&] {
         const long long gs = std::max<long long>(1, ((long long)m + kMaskScanRows - 1) / kMaskScanRows);
         hipLaunchKernelGGL(k_masked_scan, dim3((unsigned)gs), dim3(256), 0, h->stream, m, h->n, nnzM, dMp, dMj, h->dAp, h->dAj,
-                           h->dBp, spec, ctl, (int2*)h->maskQueue.p);
+                           h->dBp, spec, ctl, (int2*)ws.queue.p);
         return 1;
     }, &scanStat));
-    int* hs = h->maskHost;
-    BHS_HIP(hipMemcpyAsync(hs, ctl, sizeof(int) * MS_INTS, hipMemcpyDeviceToHost, h->stream));
-    BHS_TRY(wait_stream(h));
+    BHS_TRY(side_read_ctl(h, ws, MS_INTS));
+    const int* hs = ws.host;
     if (hs[MS_ERR]) return BHS_ERR_INVALID_ARG;                    // (nothing has touched valC)
     unsigned long long total = 0, hubMax = 0, sums[kMaskBins];
     memcpy(&total, hs + MS_TOTAL, 8);
@@ -143,20 +133,11 @@ int mask_drive(bhs_handle* h, const int* dMp, const int* dMj, int nnzM, value_t*
         BHS_TRY(timed(h, K::family(kMaskFamHub), a.nq, [&] { return K::hub(a, parts, gy, std::min(kMaskHubLds, cap)); }, &stat));
         h->stats[stat].products += (int64_t)sums[kMaskHub];
     }
-    BHS_HIP(hipEventRecord(h->maskEv[1], h->stream));
+    BHS_TRY(side_end(h, ws));
     BHS_TRY(wait_stream(h));
     if (nnzCt_out) *nnzCt_out = (int64_t)total;
-    if (ms_out) {
-        float ms = 0;
-        BHS_HIP(hipEventElapsedTime(&ms, h->maskEv[0], h->maskEv[1]));
-        *ms_out = ms;
-    }
-    for (size_t i = evFirst; i < h->evUsed; ++i) {
-        float ms = 0;
-        BHS_HIP(hipEventElapsedTime(&ms, h->evPool[i].a, h->evPool[i].b));
-        h->stats[h->evPool[i].stat].ms += ms;
-    }
-    return BHS_SUCCESS;
+    BHS_TRY(side_elapsed(h, ws, ms_out));
+    return side_collect(h, evFirst);
 }
 
 int masked_run(bhs_handle* h, const int* dMp, const int* dMj, int nnzM, value_t* dValC, int64_t* nnzCt_out, double* ms_out)
@@ -164,18 +145,29 @@ int masked_run(bhs_handle* h, const int* dMp, const int* dMj, int nnzM, value_t*
     return mask_drive<MaskedKernels>(h, dMp, dMj, nnzM, dValC, false, nnzCt_out, ms_out);
 }
 
-// after a failed call: nothing of it stays queued (the pipeline's own state is not touched)
-void settle(bhs_handle* h)
-{
-    (void)hipStreamSynchronize(h->stream);
-    (void)hipGetLastError();
-}
-
 int masked_check(bhs_handle* h, int nnzM)
 {
     if (!h) return BHS_ERR_INVALID_ARG;
     if (!h->hasData) return BHS_ERR_NOT_READY;
     if (h->ps.open || nnzM < 0) return BHS_ERR_INVALID_ARG;          // (a split multiply owns the stream until its finish)
+    return BHS_SUCCESS;
+}
+
+// The host-array entries (this one's and the semiring multiply's): M to the device copies of the masked multiply's own, `run`
+// on them, valC back to the caller
+template <typename F>
+int mask_staged(bhs_handle* h, const int* rowPtrM, const int* colIndM, int nnzM, bhs_value_t* valC, F&& run)
+{
+    BHS_TRY(ensure(h, h->maskM[0], sizeof(int) * ((size_t)h->m + 1)));
+    BHS_TRY(ensure(h, h->maskM[1], sizeof(int) * (size_t)std::max(nnzM, 1)));
+    BHS_TRY(ensure(h, h->maskM[2], sizeof(value_t) * (size_t)std::max(nnzM, 1)));
+    BHS_HIP(hipMemcpyAsync(h->maskM[0].p, rowPtrM, sizeof(int) * ((size_t)h->m + 1), hipMemcpyHostToDevice, h->stream));
+    if (nnzM) BHS_HIP(hipMemcpyAsync(h->maskM[1].p, colIndM, sizeof(int) * (size_t)nnzM, hipMemcpyHostToDevice, h->stream));
+    BHS_TRY(run((const int*)h->maskM[0].p, (const int*)h->maskM[1].p, (value_t*)h->maskM[2].p));
+    if (nnzM) {
+        BHS_HIP(hipMemcpyAsync(valC, h->maskM[2].p, sizeof(value_t) * (size_t)nnzM, hipMemcpyDeviceToHost, h->stream));
+        BHS_HIP(hipStreamSynchronize(h->stream));
+    }
     return BHS_SUCCESS;
 }
 
@@ -188,10 +180,7 @@ int bhs_spgemm_masked_device(bhs_handle* h, const int* d_rowPtrM, const int* d_c
 {
     BHS_TRY(masked_check(h, nnzM));
     if (!d_rowPtrM || (nnzM > 0 && (!d_colIndM || !d_valC))) return BHS_ERR_INVALID_ARG;
-    BHS_HIP(hipSetDevice(h->device));
-    const int rc = masked_run(h, d_rowPtrM, d_colIndM, nnzM, (value_t*)d_valC, nnzCt_out, ms_out);
-    if (rc) settle(h);
-    return rc;
+    return guarded(h, [&] { return masked_run(h, d_rowPtrM, d_colIndM, nnzM, (value_t*)d_valC, nnzCt_out, ms_out); });
 }
 
 int bhs_spgemm_masked(bhs_handle* h, const int* rowPtrM, const int* colIndM, int nnzM, bhs_value_t* valC, int64_t* nnzCt_out,
@@ -199,19 +188,11 @@ int bhs_spgemm_masked(bhs_handle* h, const int* rowPtrM, const int* colIndM, int
 {
     BHS_TRY(masked_check(h, nnzM));
     if (!rowPtrM || (nnzM > 0 && (!colIndM || !valC))) return BHS_ERR_INVALID_ARG;
-    BHS_HIP(hipSetDevice(h->device));
-    BHS_TRY(ensure(h, h->maskM[0], sizeof(int) * ((size_t)h->m + 1)));
-    BHS_TRY(ensure(h, h->maskM[1], sizeof(int) * (size_t)std::max(nnzM, 1)));
-    BHS_TRY(ensure(h, h->maskM[2], sizeof(value_t) * (size_t)std::max(nnzM, 1)));
-    BHS_HIP(hipMemcpyAsync(h->maskM[0].p, rowPtrM, sizeof(int) * ((size_t)h->m + 1), hipMemcpyHostToDevice, h->stream));
-    if (nnzM) BHS_HIP(hipMemcpyAsync(h->maskM[1].p, colIndM, sizeof(int) * (size_t)nnzM, hipMemcpyHostToDevice, h->stream));
-    int rc = masked_run(h, (const int*)h->maskM[0].p, (const int*)h->maskM[1].p, nnzM, (value_t*)h->maskM[2].p, nnzCt_out, ms_out);
-    if (rc == BHS_SUCCESS && nnzM) {
-        BHS_HIP(hipMemcpyAsync(valC, h->maskM[2].p, sizeof(value_t) * (size_t)nnzM, hipMemcpyDeviceToHost, h->stream));
-        BHS_HIP(hipStreamSynchronize(h->stream));
-    }
-    if (rc) settle(h);
-    return rc;
+    return guarded(h, [&] {
+        return mask_staged(h, rowPtrM, colIndM, nnzM, valC, [&](const int* dMp, const int* dMj, value_t* dValC) {
+            return masked_run(h, dMp, dMj, nnzM, dValC, nnzCt_out, ms_out);
+        });
+    });
 }
 
 }  // extern "C"

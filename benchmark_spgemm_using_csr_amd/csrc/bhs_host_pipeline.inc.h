@@ -660,11 +660,7 @@ int scan_rowptr(bhs_handle* h, bool useClass, const SymChoices& sc)
         if (h->scanOnePass) {
             // one pass with look-back over the tiles before (k_scan_onepass); the tile words carry this multiply's epoch
             const int nTiles = (m + kScan1Tile - 1) / kScan1Tile;
-            h->scanEpoch = (h->scanEpoch + 1) & 0x3FFFFu;
-            if (h->scanEpoch == 0) {                                    // (every 2^18 multiplies the words of 2^18 multiplies ago could match)
-                BHS_HIP(hipMemsetAsync(h->blockSum.p, 0, sizeof(unsigned long long) * (size_t)std::max(nTiles, 1), h->stream));
-                h->scanEpoch = 1;
-            }
+            BHS_TRY(scan_next_epoch(h, h->scanEpoch, h->blockSum.p, nTiles));
             hipLaunchKernelGGL(k_scan_onepass, dim3((unsigned)nTiles), dim3(kScan1Block), 0, h->stream, m, (int*)h->Cp.p, h->dAp,
                                (unsigned long long*)h->blockSum.p, h->scanEpoch, small + S_SCAN_TICKET, (long long*)(small + S_TOTAL_C),
                                small + S_NUM_COUNT, numSpec, small + S_MAXCNT, (const int*)h->ub.p);

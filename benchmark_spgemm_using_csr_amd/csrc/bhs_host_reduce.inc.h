@@ -2,9 +2,10 @@
 // bhs_reduce.hip.h)
 // (A part of bhsparse_hip.hip's translation unit: included there after the transpose.)
 //
-// Like the add, the selection, the transpose and the extraction both calls work beside the pipeline: counters, queues,
-// accumulators, partials, events and the pinned mirror are buffers of their own from the grow-only pool.  They bind nothing
-// and serve nothing through the getters: every output array is the caller's.
+// Like the add, the selection, the transpose and the extraction both calls work beside the pipeline: their workspace (h->rdWs:
+// counters, queues, events, the pinned mirror; set up and read by bhs_host_side.inc.h), the accumulators and the partials
+// are buffers of their own from the grow-only pool.  They bind nothing and serve nothing through the getters: every output
+// array is the caller's.
 //
 // The kernels' header is included here, not among the translation unit's kernel headers (as bhs_host_extract.inc.h does).
 #include "bhs_reduce.hip.h"
@@ -16,35 +17,11 @@ struct RdIn {
     const int* Xp; const int* Xj; const value_t* Xx;
 };
 
+// (no counts: nothing is scanned)
 int rd_prepare(bhs_handle* h, int m)
 {
-    h->ls = h->stream;
-    if (!h->rdEv[0]) {
-        BHS_HIP(hipEventCreate(&h->rdEv[0]));
-        BHS_HIP(hipEventCreate(&h->rdEv[1]));
-    }
-    if (!h->rdHost) BHS_HIP(hipHostMalloc((void**)&h->rdHost, sizeof(int) * RD_INTS, hipHostMallocDefault));
-    BHS_TRY(ensure(h, h->rdCtl, sizeof(int) * RD_INTS));
-    BHS_TRY(ensure(h, h->rdQueue, sizeof(int) * 2 * (size_t)std::max(m, 1)));
-    BHS_HIP(hipMemsetAsync(h->rdCtl.p, 0, sizeof(int) * RD_INTS, h->stream));
-    return BHS_SUCCESS;
-}
-
-// the control words to the host
-int rd_read_ctl(bhs_handle* h)
-{
-    BHS_HIP(hipMemcpyAsync(h->rdHost, h->rdCtl.p, sizeof(int) * RD_INTS, hipMemcpyDeviceToHost, h->stream));
-    BHS_TRY(wait_stream(h));
-    return BHS_SUCCESS;
-}
-
-int rd_elapsed(bhs_handle* h, double* ms_out)
-{
-    if (ms_out) {
-        float ms = 0;
-        BHS_HIP(hipEventElapsedTime(&ms, h->rdEv[0], h->rdEv[1]));
-        *ms_out = ms;
-    }
+    BHS_TRY(side_prepare(h, h->rdWs, RD_INTS, sizeof(int) * 2 * (size_t)std::max(m, 1), 0));
+    BHS_HIP(hipMemsetAsync(h->rdWs.ctl.p, 0, sizeof(int) * RD_INTS, h->stream));
     return BHS_SUCCESS;
 }
 
@@ -56,8 +33,8 @@ unsigned rd_grid(long long items, int per) { return (unsigned)std::max<long long
 template <int KIND>
 int rd_rows(bhs_handle* h, const RdIn& in, int op, int filt, int nRead, rd_u64 id, rd_u64* acc)
 {
-    int* ctl = (int*)h->rdCtl.p;
-    int* queue = (int*)h->rdQueue.p;
+    int* ctl = (int*)h->rdWs.ctl.p;
+    int* queue = (int*)h->rdWs.queue.p;
     const int m = in.m;
     if (!in.Xx && op == kRdOpPlus && filt == kRdAll) {               // COUNT: the row pointer alone
         return timed(h, "reduce_short", m, [&] {
@@ -71,16 +48,16 @@ int rd_rows(bhs_handle* h, const RdIn& in, int op, int filt, int nRead, rd_u64 i
         return 1;
     }));
     if (in.nnzX <= kRdShortL) return BHS_SUCCESS;                    // (no row can be longer)
-    BHS_TRY(rd_read_ctl(h));
-    if (h->rdHost[RD_ERR]) return BHS_ERR_INVALID_ARG;
-    if (const int nq = h->rdHost[RD_CNT_WAVE]) {
+    BHS_TRY(side_read_ctl(h, h->rdWs, RD_INTS));
+    if (h->rdWs.host[RD_ERR]) return BHS_ERR_INVALID_ARG;
+    if (const int nq = h->rdWs.host[RD_CNT_WAVE]) {
         BHS_TRY(timed(h, "reduce_wave", nq, [&] {
             hipLaunchKernelGGL(k_red_wave<KIND>, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, h->stream, nq,
                                queue + (size_t)RD_CNT_WAVE * m, m, in.n, in.nnzX, in.Xp, in.Xj, in.Xx, op, filt, id, acc, ctl);
             return 1;
         }));
     }
-    if (const int nq = h->rdHost[RD_CNT_LONG]) {
+    if (const int nq = h->rdWs.host[RD_CNT_LONG]) {
         BHS_TRY(timed(h, "reduce_long", nq, [&] {
             hipLaunchKernelGGL(k_red_long<KIND>, dim3((unsigned)std::min<long long>(nq, (long long)h->numCU * 8)), dim3(256), 0,
                                h->stream, nq, queue + (size_t)RD_CNT_LONG * m, m, in.n, in.nnzX, in.Xp, in.Xj, in.Xx, op, filt, id,
@@ -100,7 +77,7 @@ int rd_all(bhs_handle* h, const RdIn& in, const rd_u64* raw, long long count, in
     *nPart = (int)g;
     return timed(h, "reduce_all", in.m, [&] {
         hipLaunchKernelGGL((k_red_all<KIND, RAW>), dim3(g), dim3(256), 0, h->stream, in.m, in.nnzX, in.Xp, in.Xx, raw, count, op, id,
-                           (rd_u64*)h->rdPart.p, (int*)h->rdCtl.p);
+                           (rd_u64*)h->rdPart.p, (int*)h->rdWs.ctl.p);
         return 1;
     });
 }
@@ -109,9 +86,9 @@ template <int KIND>
 int rd_run(bhs_handle* h, const RdIn& in, int axis, int op, int filt, value_t* out, double* ms_out)
 {
     BHS_TRY(rd_prepare(h, in.m));
-    add_reset_stats(h);
-    BHS_HIP(hipEventRecord(h->rdEv[0], h->stream));
-    int* ctl = (int*)h->rdCtl.p;
+    side_reset_stats(h);
+    BHS_TRY(side_begin(h, h->rdWs));
+    int* ctl = (int*)h->rdWs.ctl.p;
     const rd_u64 id = rd_identity(KIND, op);
     const int nDiag = std::min(in.m, in.n);
     const int nOut = axis == BHS_AXIS_ROWS ? in.m : axis == BHS_AXIS_COLS ? in.n : axis == BHS_AXIS_DIAG ? nDiag : 1;
@@ -143,20 +120,20 @@ int rd_run(bhs_handle* h, const RdIn& in, int axis, int op, int filt, value_t* o
                            out, ctl);
         return 1;
     }));
-    BHS_HIP(hipEventRecord(h->rdEv[1], h->stream));
-    BHS_TRY(rd_read_ctl(h));
-    BHS_TRY(rd_elapsed(h, ms_out));
-    BHS_TRY(add_collect(h, 0));
-    return h->rdHost[RD_ERR] ? (int)BHS_ERR_INVALID_ARG : (int)BHS_SUCCESS;
+    BHS_TRY(side_end(h, h->rdWs));
+    BHS_TRY(side_read_ctl(h, h->rdWs, RD_INTS));
+    BHS_TRY(side_elapsed(h, h->rdWs, ms_out));
+    BHS_TRY(side_collect(h, 0));
+    return h->rdWs.host[RD_ERR] ? (int)BHS_ERR_INVALID_ARG : (int)BHS_SUCCESS;
 }
 
 int sc_run(bhs_handle* h, const ScArgs& s, double* ms_out)
 {
     BHS_TRY(rd_prepare(h, s.m));
-    add_reset_stats(h);
-    BHS_HIP(hipEventRecord(h->rdEv[0], h->stream));
-    int* ctl = (int*)h->rdCtl.p;
-    int* queue = (int*)h->rdQueue.p;
+    side_reset_stats(h);
+    BHS_TRY(side_begin(h, h->rdWs));
+    int* ctl = (int*)h->rdWs.ctl.p;
+    int* queue = (int*)h->rdWs.queue.p;
     const unsigned gCheck = (unsigned)std::min<long long>(rd_grid(s.m, 256), (long long)h->numCU * 8);
     if (!s.left) {
         BHS_TRY(timed(h, "scale", s.m, [&] {
@@ -171,16 +148,16 @@ int sc_run(bhs_handle* h, const ScArgs& s, double* ms_out)
             return 2;
         }));
         if (s.nnzX > kRdShortL) {                                    // (else no row can be longer)
-            BHS_TRY(rd_read_ctl(h));
-            if (h->rdHost[RD_ERR]) return BHS_ERR_INVALID_ARG;
-            if (const int nq = h->rdHost[RD_CNT_WAVE]) {
+            BHS_TRY(side_read_ctl(h, h->rdWs, RD_INTS));
+            if (h->rdWs.host[RD_ERR]) return BHS_ERR_INVALID_ARG;
+            if (const int nq = h->rdWs.host[RD_CNT_WAVE]) {
                 BHS_TRY(timed(h, "scale_wave", nq, [&] {
                     hipLaunchKernelGGL(k_sc_wave, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, h->stream, nq,
                                        queue + (size_t)RD_CNT_WAVE * s.m, s, ctl);
                     return 1;
                 }));
             }
-            if (const int nq = h->rdHost[RD_CNT_LONG]) {
+            if (const int nq = h->rdWs.host[RD_CNT_LONG]) {
                 BHS_TRY(timed(h, "scale_long", nq, [&] {
                     hipLaunchKernelGGL(k_sc_long, dim3((unsigned)std::min<long long>(nq, (long long)h->numCU * 8)), dim3(256), 0,
                                        h->stream, nq, queue + (size_t)RD_CNT_LONG * s.m, s, ctl);
@@ -189,11 +166,11 @@ int sc_run(bhs_handle* h, const ScArgs& s, double* ms_out)
             }
         }
     }
-    BHS_HIP(hipEventRecord(h->rdEv[1], h->stream));
-    BHS_TRY(rd_read_ctl(h));
-    BHS_TRY(rd_elapsed(h, ms_out));
-    BHS_TRY(add_collect(h, 0));
-    return h->rdHost[RD_ERR] ? (int)BHS_ERR_INVALID_ARG : (int)BHS_SUCCESS;
+    BHS_TRY(side_end(h, h->rdWs));
+    BHS_TRY(side_read_ctl(h, h->rdWs, RD_INTS));
+    BHS_TRY(side_elapsed(h, h->rdWs, ms_out));
+    BHS_TRY(side_collect(h, 0));
+    return h->rdWs.host[RD_ERR] ? (int)BHS_ERR_INVALID_ARG : (int)BHS_SUCCESS;
 }
 
 // do [a, a + na) and [b, b + nb) share a byte
@@ -225,16 +202,14 @@ int bhs_csr_reduce_device(bhs_handle* h, int m, int n, int nnzX, const bhs_value
         rd_overlap(d_out, outBytes, d_colIndX, sizeof(int) * (size_t)nnzX) ||
         rd_overlap(d_out, outBytes, d_valX, sizeof(value_t) * (size_t)nnzX))
         return BHS_ERR_INVALID_ARG;                                  // (the output must not overlap an input)
-    BHS_HIP(hipSetDevice(h->device));
     RdIn in;
     in.m = m; in.n = n; in.nnzX = nnzX; in.Xp = d_rowPtrX; in.Xj = d_colIndX; in.Xx = (const value_t*)d_valX;
     if (op == BHS_RED_COUNT) { in.Xx = nullptr; op = BHS_RED_PLUS; } // (a sum of ones: no value is read)
-    int rc;
-    if (op == BHS_RED_MIN) rc = rd_run<kRdMin>(h, in, axis, op, filt, (value_t*)d_out, ms_out);
-    else if (op == BHS_RED_MAX || op == BHS_RED_ABS_MAX) rc = rd_run<kRdMax>(h, in, axis, op, filt, (value_t*)d_out, ms_out);
-    else rc = rd_run<kRdSum>(h, in, axis, op, filt, (value_t*)d_out, ms_out);
-    if (rc) settle(h);
-    return rc;
+    return guarded(h, [&] {
+        if (op == BHS_RED_MIN) return rd_run<kRdMin>(h, in, axis, op, filt, (value_t*)d_out, ms_out);
+        if (op == BHS_RED_MAX || op == BHS_RED_ABS_MAX) return rd_run<kRdMax>(h, in, axis, op, filt, (value_t*)d_out, ms_out);
+        return rd_run<kRdSum>(h, in, axis, op, filt, (value_t*)d_out, ms_out);
+    });
 }
 
 int bhs_csr_scale_device(bhs_handle* h, int m, int n, int nnzX, const bhs_value_t* d_valX, const int* d_rowPtrX,
@@ -252,15 +227,12 @@ int bhs_csr_scale_device(bhs_handle* h, int m, int n, int nnzX, const bhs_value_
         rd_overlap(d_valZ, zBytes, d_right, sizeof(value_t) * (size_t)n) ||
         ((const void*)d_valZ != (const void*)d_valX && rd_overlap(d_valZ, zBytes, d_valX, zBytes)))
         return BHS_ERR_INVALID_ARG;                                  // (in place on valX exactly, or apart from every input)
-    BHS_HIP(hipSetDevice(h->device));
     ScArgs s;
     s.m = m; s.n = n; s.nnzX = nnzX; s.Xp = d_rowPtrX; s.Xj = d_colIndX; s.Xx = (const value_t*)d_valX;
     s.left = (const value_t*)d_left; s.right = (const value_t*)d_right; s.alpha = alpha;
     s.leftDiv = (flags & BHS_SCALE_LEFT_DIV) ? 1 : 0; s.rightDiv = (flags & BHS_SCALE_RIGHT_DIV) ? 1 : 0;
     s.Zx = (value_t*)d_valZ;
-    const int rc = sc_run(h, s, ms_out);
-    if (rc) settle(h);
-    return rc;
+    return guarded(h, [&] { return sc_run(h, s, ms_out); });
 }
 
 }  // extern "C"

@@ -2,10 +2,11 @@
 // bhs_select.hip.h)
 // (A part of bhsparse_hip.hip's translation unit: included there after the sparse add.)
 //
-// Like the masked multiply and the add the selection works beside the pipeline: counters, queues, tile words, events and the
-// pinned mirror are buffers of its own.  bhs_spgemm_select runs the ordinary multiply and then selects from its C; where
-// entries were dropped the selected C goes to the second set of arrays bhs_spgemm_add uses (h->sumActive, served by the
-// getters until the next multiply); the pipeline's own C arrays are never moved.
+// Like the masked multiply and the add the selection works beside the pipeline: its workspace (h->selWs: counters, queues,
+// counts, tile words, events, the pinned mirror; set up, read and scanned by bhs_host_side.inc.h) is its own.
+// bhs_spgemm_select runs the ordinary multiply and then selects from its C; where entries were dropped the selected C goes
+// to the second set of arrays bhs_spgemm_add uses (h->sumActive, served by the getters until the next multiply); the
+// pipeline's own C arrays are never moved.
 
 namespace {
 
@@ -35,78 +36,34 @@ bool sel_spec_from(const bhs_select* s, SelSpec* out)
 
 int sel_prepare(bhs_handle* h, int m)
 {
-    h->ls = h->stream;
-    if (!h->selEv[0]) {
-        BHS_HIP(hipEventCreate(&h->selEv[0]));
-        BHS_HIP(hipEventCreate(&h->selEv[1]));
-    }
-    if (!h->selHost) BHS_HIP(hipHostMalloc((void**)&h->selHost, sizeof(int) * SL_INTS, hipHostMallocDefault));
-    BHS_TRY(ensure(h, h->selCtl, sizeof(int) * SL_INTS));
-    BHS_TRY(ensure(h, h->selQueue, sizeof(int) * (size_t)kSelBins * (size_t)std::max(m, 1)));
-    BHS_TRY(ensure(h, h->selCnt, sizeof(int) * ((size_t)m + 1)));
-    BHS_TRY(ensure(h, h->selTiles, sizeof(unsigned long long) * (size_t)std::max((m + kScan1Tile - 1) / kScan1Tile, 1), true));
-    return BHS_SUCCESS;
+    return side_prepare(h, h->selWs, SL_INTS, sizeof(int) * (size_t)kSelBins * (size_t)std::max(m, 1), (size_t)m + 1);
 }
 
-// the control words to the host: the one round trip of a selection
-int sel_read_ctl(bhs_handle* h)
-{
-    BHS_HIP(hipMemcpyAsync(h->selHost, h->selCtl.p, sizeof(int) * SL_INTS, hipMemcpyDeviceToHost, h->stream));
-    BHS_TRY(wait_stream(h));
-    return BHS_SUCCESS;
-}
+constexpr SideScanWords kSelScanWords = {SL_TICKET, SL_SCANTOTAL, SL_SCANBINS, SL_MAXCNT};
 
-// The count pass and its round trip.  Afterwards h->selCnt holds the rows' counts, h->selQueue the bins' rows, h->selHost
+// The count pass and its round trip.  Afterwards h->selWs.cnt holds the rows' counts, h->selWs.queue the bins' rows, h->selWs.host
 // the control words; *nnzZ the number of survivors.
 int sel_count(bhs_handle* h, const SelIn& in, const SelSpec& spec, long long* nnzZ)
 {
-    int* ctl = (int*)h->selCtl.p;
+    int* ctl = (int*)h->selWs.ctl.p;
     BHS_HIP(hipMemsetAsync(ctl, 0, sizeof(int) * SL_INTS, h->stream));
     int stat = 0;
     BHS_TRY(timed(h, "select_count", in.m, [&] {
         const long long gs = std::max<long long>(1, ((long long)in.m + kSelCountRows - 1) / kSelCountRows);
         hipLaunchKernelGGL(k_sel_count, dim3((unsigned)gs), dim3(256), 0, h->stream, in.m, in.n, in.nnzX, in.Xp, in.Xj, in.Xx, spec,
-                           (int*)h->selCnt.p, ctl, (int*)h->selQueue.p);
+                           (int*)h->selWs.cnt.p, ctl, (int*)h->selWs.queue.p);
         if (in.nnzX <= kSelWaveL) return 1;                          // (no row can be long)
         const long long gl = std::max<long long>(1, std::min<long long>(in.m, (long long)h->numCU * 8));
         hipLaunchKernelGGL(k_sel_count_long, dim3((unsigned)gl), dim3(256), 0, h->stream, in.m, in.n, in.Xp, in.Xj, in.Xx, spec,
-                           (int*)h->selCnt.p, ctl, (const int*)h->selQueue.p);
+                           (int*)h->selWs.cnt.p, ctl, (const int*)h->selWs.queue.p);
         return 2;
     }, &stat));
-    BHS_TRY(sel_read_ctl(h));
-    if (h->selHost[SL_ERR]) return BHS_ERR_INVALID_ARG;
+    BHS_TRY(side_read_ctl(h, h->selWs, SL_INTS));
+    if (h->selWs.host[SL_ERR]) return BHS_ERR_INVALID_ARG;
     unsigned long long total = 0;
-    memcpy(&total, h->selHost + SL_TOTAL, 8);
+    memcpy(&total, h->selWs.host + SL_TOTAL, 8);
     h->stats[stat].nnz_out += (int64_t)total;
     *nnzZ = (long long)total;                                        // (at most nnz(X): no overflow of its own)
-    return BHS_SUCCESS;
-}
-
-// rowPtrZ from the counts of sel_count: the library's one-pass scan over h->selCnt (tile words and epoch of the selection's
-// own), then a copy to where the row pointer is wanted
-int sel_scan(bhs_handle* h, int m, const int* anyRowPtr, int* d_rowPtrZ)
-{
-    int* ctl = (int*)h->selCtl.p;
-    int* cnt = (int*)h->selCnt.p;
-    const int nTiles = (m + kScan1Tile - 1) / kScan1Tile;
-    if (nTiles == 0) {
-        BHS_HIP(hipMemsetAsync(cnt, 0, sizeof(int), h->stream));
-    } else {
-        h->selEpoch = (h->selEpoch + 1) & 0x3FFFFu;
-        if (h->selEpoch == 0) {                                      // (see scan_rowptr)
-            BHS_HIP(hipMemsetAsync(h->selTiles.p, 0, sizeof(unsigned long long) * (size_t)nTiles, h->stream));
-            h->selEpoch = 1;
-        }
-        BinSpec none;                                                // (no bins: the scan's histogram stays empty)
-        memset(&none, 0, sizeof(none));
-        BHS_TRY(timed(h, "select_scan", m, [&] {
-            hipLaunchKernelGGL(k_scan_onepass, dim3((unsigned)nTiles), dim3(kScan1Block), 0, h->stream, m, cnt, anyRowPtr,
-                               (unsigned long long*)h->selTiles.p, h->selEpoch, ctl + SL_TICKET, (long long*)(ctl + SL_SCANTOTAL),
-                               ctl + SL_SCANBINS, none, ctl + SL_MAXCNT, (const int*)nullptr);
-            return 1;
-        }));
-    }
-    BHS_HIP(hipMemcpyAsync(d_rowPtrZ, cnt, sizeof(int) * ((size_t)m + 1), hipMemcpyDeviceToDevice, h->stream));
     return BHS_SUCCESS;
 }
 
@@ -114,9 +71,9 @@ template <bool TOPK>
 int sel_fill_bins(bhs_handle* h, const SelIn& in, const SelSpec& spec, const int* Zp, int* Zj, value_t* Zx)
 {
     const int m = in.m;
-    const int* queue = (const int*)h->selQueue.p;
-    const int* count = h->selHost + SL_COUNT;
-    int* ctl = (int*)h->selCtl.p;
+    const int* queue = (const int*)h->selWs.queue.p;
+    const int* count = h->selWs.host + SL_COUNT;
+    int* ctl = (int*)h->selWs.ctl.p;
     if (count[kSelShort]) {
         const int nq = count[kSelShort];
         BHS_TRY(timed(h, "select_short", nq, [&] {
@@ -148,20 +105,10 @@ int sel_fill_bins(bhs_handle* h, const SelIn& in, const SelSpec& spec, const int
     return BHS_SUCCESS;
 }
 
-// the fill pass on the queues and bin counts in h->selQueue / h->selHost
+// the fill pass on the queues and bin counts in h->selWs.queue / h->selWs.host
 int sel_fill(bhs_handle* h, const SelIn& in, const SelSpec& spec, const int* Zp, int* Zj, value_t* Zx)
 {
     return (spec.flags & SEL_TOPK) ? sel_fill_bins<true>(h, in, spec, Zp, Zj, Zx) : sel_fill_bins<false>(h, in, spec, Zp, Zj, Zx);
-}
-
-int sel_elapsed(bhs_handle* h, double* ms_out)
-{
-    if (ms_out) {
-        float ms = 0;
-        BHS_HIP(hipEventElapsedTime(&ms, h->selEv[0], h->selEv[1]));
-        *ms_out = ms;
-    }
-    return BHS_SUCCESS;
 }
 
 bool sel_args_ok(int m, int n, int nnzX, const value_t* Xx, const int* Xp, const int* Xj, const SelSpec& spec)
@@ -172,12 +119,12 @@ bool sel_args_ok(int m, int n, int nnzX, const value_t* Xx, const int* Xp, const
 int sel_symbolic_run(bhs_handle* h, const SelIn& in, const SelSpec& spec, int* d_rowPtrZ, int* nnzZ_out)
 {
     BHS_TRY(sel_prepare(h, in.m));
-    add_reset_stats(h);
+    side_reset_stats(h);
     long long nnzZ = 0;
     BHS_TRY(sel_count(h, in, spec, &nnzZ));
-    BHS_TRY(sel_scan(h, in.m, in.Xp, d_rowPtrZ));
+    BHS_TRY(side_scan(h, h->selWs, "select_scan", kSelScanWords, in.m, in.Xp, d_rowPtrZ));
     BHS_TRY(wait_stream(h));
-    BHS_TRY(add_collect(h, 0));
+    BHS_TRY(side_collect(h, 0));
     if (nnzZ_out) *nnzZ_out = (int)nnzZ;
     return BHS_SUCCESS;
 }
@@ -185,24 +132,24 @@ int sel_symbolic_run(bhs_handle* h, const SelIn& in, const SelSpec& spec, int* d
 int sel_numeric_run(bhs_handle* h, const SelIn& in, const SelSpec& spec, const int* Zp, int* Zj, value_t* Zx, double* ms_out)
 {
     BHS_TRY(sel_prepare(h, in.m));
-    add_reset_stats(h);
-    int* ctl = (int*)h->selCtl.p;
-    BHS_HIP(hipEventRecord(h->selEv[0], h->stream));
+    side_reset_stats(h);
+    int* ctl = (int*)h->selWs.ctl.p;
+    BHS_TRY(side_begin(h, h->selWs));
     BHS_HIP(hipMemsetAsync(ctl, 0, sizeof(int) * SL_INTS, h->stream));
     BHS_TRY(timed(h, "select_count", in.m, [&] {
         const long long gs = std::max<long long>(1, ((long long)in.m + 255) / 256);
-        hipLaunchKernelGGL(k_sel_bin, dim3((unsigned)gs), dim3(256), 0, h->stream, in.m, in.nnzX, in.Xp, Zp, ctl, (int*)h->selQueue.p);
+        hipLaunchKernelGGL(k_sel_bin, dim3((unsigned)gs), dim3(256), 0, h->stream, in.m, in.nnzX, in.Xp, Zp, ctl, (int*)h->selWs.queue.p);
         return 1;
     }));
-    BHS_TRY(sel_read_ctl(h));
-    if (h->selHost[SL_ERR]) return BHS_ERR_INVALID_ARG;
+    BHS_TRY(side_read_ctl(h, h->selWs, SL_INTS));
+    if (h->selWs.host[SL_ERR]) return BHS_ERR_INVALID_ARG;
     BHS_TRY(sel_fill(h, in, spec, Zp, Zj, Zx));
-    BHS_HIP(hipEventRecord(h->selEv[1], h->stream));
-    BHS_HIP(hipMemcpyAsync(h->selHost, ctl, sizeof(int) * SL_INTS, hipMemcpyDeviceToHost, h->stream));   // (a row that no longer matches rowPtrZ)
+    BHS_TRY(side_end(h, h->selWs));
+    BHS_HIP(hipMemcpyAsync(h->selWs.host, ctl, sizeof(int) * SL_INTS, hipMemcpyDeviceToHost, h->stream));   // (a row that no longer matches rowPtrZ)
     BHS_TRY(wait_stream(h));
-    BHS_TRY(sel_elapsed(h, ms_out));
-    BHS_TRY(add_collect(h, 0));
-    return h->selHost[SL_ERR] ? (int)BHS_ERR_INVALID_ARG : (int)BHS_SUCCESS;
+    BHS_TRY(side_elapsed(h, h->selWs, ms_out));
+    BHS_TRY(side_collect(h, 0));
+    return h->selWs.host[SL_ERR] ? (int)BHS_ERR_INVALID_ARG : (int)BHS_SUCCESS;
 }
 
 // the selection behind a finished multiply: X = the C of the pipeline
@@ -214,7 +161,7 @@ int sel_from_product(bhs_handle* h, const SelSpec& spec, double* ms_out)
     SelIn in;
     in.m = m; in.n = h->n; in.nnzX = (int)h->nnzC;
     in.Xp = (const int*)h->Cp.p; in.Xj = (const int*)h->Cj.p; in.Xx = (const value_t*)h->Cx.p;
-    BHS_HIP(hipEventRecord(h->selEv[0], h->stream));
+    BHS_TRY(side_begin(h, h->selWs));
     long long nnzZ = 0;
     BHS_TRY(sel_count(h, in, spec, &nnzZ));
     h->selDropped = h->nnzC - nnzZ;
@@ -222,17 +169,17 @@ int sel_from_product(bhs_handle* h, const SelSpec& spec, double* ms_out)
         BHS_TRY(ensure(h, h->sumCp, sizeof(int) * ((size_t)m + 1)));
         BHS_TRY(ensure(h, h->sumCj, sizeof(int) * (size_t)std::max<long long>(nnzZ, 1)));
         BHS_TRY(ensure(h, h->sumCx, sizeof(value_t) * (size_t)std::max<long long>(nnzZ, 1)));
-        BHS_TRY(sel_scan(h, m, in.Xp, (int*)h->sumCp.p));
+        BHS_TRY(side_scan(h, h->selWs, "select_scan", kSelScanWords, m, in.Xp, (int*)h->sumCp.p));
         BHS_TRY(sel_fill(h, in, spec, (const int*)h->sumCp.p, (int*)h->sumCj.p, (value_t*)h->sumCx.p));
     }
-    BHS_HIP(hipEventRecord(h->selEv[1], h->stream));
+    BHS_TRY(side_end(h, h->selWs));
     BHS_TRY(wait_stream(h));
     if (h->selDropped) {                                             // from here on the getters serve the selection
         h->sumActive = true;
         h->sumNnz = nnzZ;
     }
-    BHS_TRY(sel_elapsed(h, ms_out));
-    return add_collect(h, evFirst);
+    BHS_TRY(side_elapsed(h, h->selWs, ms_out));
+    return side_collect(h, evFirst);
 }
 
 int spgemm_select_check(bhs_handle* h, const bhs_select* sel, SelSpec* spec)
@@ -272,12 +219,9 @@ int bhs_csr_select_symbolic_device(bhs_handle* h, int m, int n, int nnzX, const 
     if (!h || h->ps.open || !d_rowPtrZ || !sel_spec_from(sel, &spec) ||
         !sel_args_ok(m, n, nnzX, (const value_t*)d_valX, d_rowPtrX, d_colIndX, spec))
         return BHS_ERR_INVALID_ARG;
-    BHS_HIP(hipSetDevice(h->device));
     SelIn in;
     in.m = m; in.n = n; in.nnzX = nnzX; in.Xp = d_rowPtrX; in.Xj = d_colIndX; in.Xx = (const value_t*)d_valX;
-    const int rc = sel_symbolic_run(h, in, spec, d_rowPtrZ, nnzZ_out);
-    if (rc) settle(h);
-    return rc;
+    return guarded(h, [&] { return sel_symbolic_run(h, in, spec, d_rowPtrZ, nnzZ_out); });
 }
 
 int bhs_csr_select_numeric_device(bhs_handle* h, int m, int n, int nnzX, const bhs_value_t* d_valX, const int* d_rowPtrX,
@@ -290,12 +234,9 @@ int bhs_csr_select_numeric_device(bhs_handle* h, int m, int n, int nnzX, const b
         return BHS_ERR_INVALID_ARG;
     if (nnzX > 0 && (!d_colIndZ || (d_valZ && !d_valX))) return BHS_ERR_INVALID_ARG;
     if (nnzX > 0 && (d_colIndZ == d_colIndX || (d_valZ && d_valZ == d_valX))) return BHS_ERR_INVALID_ARG;   // (Z must not overlap X)
-    BHS_HIP(hipSetDevice(h->device));
     SelIn in;
     in.m = m; in.n = n; in.nnzX = nnzX; in.Xp = d_rowPtrX; in.Xj = d_colIndX; in.Xx = (const value_t*)d_valX;
-    const int rc = sel_numeric_run(h, in, spec, d_rowPtrZ, d_colIndZ, (value_t*)d_valZ, ms_out);
-    if (rc) settle(h);
-    return rc;
+    return guarded(h, [&] { return sel_numeric_run(h, in, spec, d_rowPtrZ, d_colIndZ, (value_t*)d_valZ, ms_out); });
 }
 
 int bhs_spgemm_select_device(bhs_handle* h, const bhs_select* sel, int* d_rowPtrC_out, int64_t* nnzCt_out, int* nnzC_out,
@@ -303,20 +244,14 @@ int bhs_spgemm_select_device(bhs_handle* h, const bhs_select* sel, int* d_rowPtr
 {
     SelSpec spec;
     BHS_TRY(spgemm_select_check(h, sel, &spec));
-    BHS_HIP(hipSetDevice(h->device));
-    const int rc = spgemm_select_run(h, spec, d_rowPtrC_out, true, nnzCt_out, nnzC_out, ms_out);
-    if (rc) settle(h);
-    return rc;
+    return guarded(h, [&] { return spgemm_select_run(h, spec, d_rowPtrC_out, true, nnzCt_out, nnzC_out, ms_out); });
 }
 
 int bhs_spgemm_select(bhs_handle* h, const bhs_select* sel, int* rowPtrC_out, int64_t* nnzCt_out, int* nnzC_out, double ms_out[2])
 {
     SelSpec spec;
     BHS_TRY(spgemm_select_check(h, sel, &spec));
-    BHS_HIP(hipSetDevice(h->device));
-    const int rc = spgemm_select_run(h, spec, rowPtrC_out, false, nnzCt_out, nnzC_out, ms_out);
-    if (rc) settle(h);
-    return rc;
+    return guarded(h, [&] { return spgemm_select_run(h, spec, rowPtrC_out, false, nnzCt_out, nnzC_out, ms_out); });
 }
 
 }  // extern "C"

@@ -2,7 +2,7 @@
 // (A part of bhsparse_hip.hip's translation unit: included there last.)
 //
 // The masked calls are bhs_spgemm_masked[_device] with another product and another reduction: the same driver (mask_drive), validation and
-// binning pass (k_masked_scan), the same counters, queues, events and staging copies (the masked multiply's own buffers),
+// binning pass (k_masked_scan), the same workspace and staging copies (the masked multiply's own: h->maskWs, h->maskM),
 // the same bins and launch shapes -- so they leave the handle as the masked multiply does.  bhs_spgemm_semiring runs the
 // ordinary multiply and then re-values its C in place, with M = C's own device arrays.
 //
@@ -77,10 +77,7 @@ int bhs_spgemm_semiring_masked_device(bhs_handle* h, int semiring, const int* d_
     if (!sr_known(semiring)) return BHS_ERR_INVALID_ARG;
     if (semiring == BHS_SR_PLUS_TIMES) return bhs_spgemm_masked_device(h, d_rowPtrM, d_colIndM, nnzM, d_valC, nnzCt_out, ms_out);
     if (!d_rowPtrM || (nnzM > 0 && (!d_colIndM || !d_valC))) return BHS_ERR_INVALID_ARG;
-    BHS_HIP(hipSetDevice(h->device));
-    const int rc = sr_dispatch(h, semiring, d_rowPtrM, d_colIndM, nnzM, (value_t*)d_valC, false, nnzCt_out, ms_out);
-    if (rc) settle(h);
-    return rc;
+    return guarded(h, [&] { return sr_dispatch(h, semiring, d_rowPtrM, d_colIndM, nnzM, (value_t*)d_valC, false, nnzCt_out, ms_out); });
 }
 
 int bhs_spgemm_semiring_masked(bhs_handle* h, int semiring, const int* rowPtrM, const int* colIndM, int nnzM, bhs_value_t* valC,
@@ -90,20 +87,11 @@ int bhs_spgemm_semiring_masked(bhs_handle* h, int semiring, const int* rowPtrM, 
     if (!sr_known(semiring)) return BHS_ERR_INVALID_ARG;
     if (semiring == BHS_SR_PLUS_TIMES) return bhs_spgemm_masked(h, rowPtrM, colIndM, nnzM, valC, nnzCt_out, ms_out);
     if (!rowPtrM || (nnzM > 0 && (!colIndM || !valC))) return BHS_ERR_INVALID_ARG;
-    BHS_HIP(hipSetDevice(h->device));
-    BHS_TRY(ensure(h, h->maskM[0], sizeof(int) * ((size_t)h->m + 1)));
-    BHS_TRY(ensure(h, h->maskM[1], sizeof(int) * (size_t)std::max(nnzM, 1)));
-    BHS_TRY(ensure(h, h->maskM[2], sizeof(value_t) * (size_t)std::max(nnzM, 1)));
-    BHS_HIP(hipMemcpyAsync(h->maskM[0].p, rowPtrM, sizeof(int) * ((size_t)h->m + 1), hipMemcpyHostToDevice, h->stream));
-    if (nnzM) BHS_HIP(hipMemcpyAsync(h->maskM[1].p, colIndM, sizeof(int) * (size_t)nnzM, hipMemcpyHostToDevice, h->stream));
-    int rc = sr_dispatch(h, semiring, (const int*)h->maskM[0].p, (const int*)h->maskM[1].p, nnzM, (value_t*)h->maskM[2].p, false,
-                         nnzCt_out, ms_out);
-    if (rc == BHS_SUCCESS && nnzM) {
-        BHS_HIP(hipMemcpyAsync(valC, h->maskM[2].p, sizeof(value_t) * (size_t)nnzM, hipMemcpyDeviceToHost, h->stream));
-        BHS_HIP(hipStreamSynchronize(h->stream));
-    }
-    if (rc) settle(h);
-    return rc;
+    return guarded(h, [&] {
+        return mask_staged(h, rowPtrM, colIndM, nnzM, valC, [&](const int* dMp, const int* dMj, value_t* dValC) {
+            return sr_dispatch(h, semiring, dMp, dMj, nnzM, dValC, false, nnzCt_out, ms_out);
+        });
+    });
 }
 
 int bhs_spgemm_semiring(bhs_handle* h, int semiring, int* rowPtrC_out, int64_t* nnzCt_out, int* nnzC_out, double ms_out[2])
@@ -112,20 +100,18 @@ int bhs_spgemm_semiring(bhs_handle* h, int semiring, int* rowPtrC_out, int64_t* 
     if (!sr_known(semiring)) return BHS_ERR_INVALID_ARG;             // (before anything is started: the last C stands)
     if (!h->hasData) return BHS_ERR_NOT_READY;
     if (h->ps.open || h->extCj) return BHS_ERR_INVALID_ARG;          // (as bhs_spgemm_add: a split multiply owns the stream; bound output arrays are the caller's)
-    double stage[4] = {0, 0, 0, 0};
-    BHS_TRY(bhs_spgemm(h, rowPtrC_out, nnzCt_out, nnzC_out, stage));
-    double srMs = 0;
-    if (semiring != BHS_SR_PLUS_TIMES && h->nnzC > 0) {
-        BHS_HIP(hipSetDevice(h->device));
-        const int rc = sr_dispatch(h, semiring, (const int*)h->Cp.p, (const int*)h->Cj.p, (int)h->nnzC, (value_t*)h->Cx.p, true,
-                                   nullptr, &srMs);
-        if (rc) {
-            settle(h);
-            return rc == BHS_ERR_INVALID_ARG ? (int)BHS_ERR_INTERNAL : rc;   // (C's own pattern did not pass the mask's validation)
+    return guarded(h, [&]() -> int {
+        double stage[4] = {0, 0, 0, 0};
+        BHS_TRY(bhs_spgemm(h, rowPtrC_out, nnzCt_out, nnzC_out, stage));
+        double srMs = 0;
+        if (semiring != BHS_SR_PLUS_TIMES && h->nnzC > 0) {
+            const int rc = sr_dispatch(h, semiring, (const int*)h->Cp.p, (const int*)h->Cj.p, (int)h->nnzC, (value_t*)h->Cx.p, true,
+                                       nullptr, &srMs);
+            if (rc) return rc == BHS_ERR_INVALID_ARG ? (int)BHS_ERR_INTERNAL : rc;   // (C's own pattern did not pass the mask's validation)
         }
-    }
-    if (ms_out) { ms_out[0] = stage[0] + stage[1] + stage[2] + stage[3]; ms_out[1] = srMs; }
-    return BHS_SUCCESS;
+        if (ms_out) { ms_out[0] = stage[0] + stage[1] + stage[2] + stage[3]; ms_out[1] = srMs; }
+        return BHS_SUCCESS;
+    });
 }
 
 }  // extern "C"

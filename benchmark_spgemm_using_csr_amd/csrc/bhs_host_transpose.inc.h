@@ -2,9 +2,10 @@
 // bhs_transpose.hip.h)
 // (A part of bhsparse_hip.hip's translation unit: included there after the entry selection.)
 //
-// Like the masked multiply, the add and the selection the transpose works beside the pipeline: counters, queues, tile words,
-// epoch, events, the pinned mirror and the scratch arrays are buffers of its own from the grow-only pool.  It binds nothing
-// and serves nothing through the getters: every output array is the caller's.
+// Like the masked multiply, the add and the selection the transpose works beside the pipeline: its workspace (h->trWs: counters,
+// queues, counts, tile words, events, the pinned mirror; set up, read and scanned by bhs_host_side.inc.h) and the scratch
+// arrays are buffers of its own from the grow-only pool.  It binds nothing and serves nothing through the getters: every
+// output array is the caller's.
 
 namespace {
 
@@ -13,43 +14,15 @@ struct TrIn {
     const int* Xp; const int* Xj; const value_t* Xx;
 };
 
-int tr_prepare(bhs_handle* h)
-{
-    h->ls = h->stream;
-    if (!h->trEv[0]) {
-        BHS_HIP(hipEventCreate(&h->trEv[0]));
-        BHS_HIP(hipEventCreate(&h->trEv[1]));
-    }
-    if (!h->trHost) BHS_HIP(hipHostMalloc((void**)&h->trHost, sizeof(int) * TR_INTS, hipHostMallocDefault));
-    BHS_TRY(ensure(h, h->trCtl, sizeof(int) * TR_INTS));
-    return BHS_SUCCESS;
-}
+constexpr SideScanWords kTrScanWords = {TR_TICKET, TR_SCANTOTAL, TR_SCANBINS, TR_MAXCNT};
 
-// the control words to the host: the one round trip of a transpose
-int tr_read_ctl(bhs_handle* h)
-{
-    BHS_HIP(hipMemcpyAsync(h->trHost, h->trCtl.p, sizeof(int) * TR_INTS, hipMemcpyDeviceToHost, h->stream));
-    BHS_TRY(wait_stream(h));
-    return BHS_SUCCESS;
-}
-
-int tr_elapsed(bhs_handle* h, double* ms_out)
-{
-    if (ms_out) {
-        float ms = 0;
-        BHS_HIP(hipEventElapsedTime(&ms, h->trEv[0], h->trEv[1]));
-        *ms_out = ms;
-    }
-    return BHS_SUCCESS;
-}
-
-// the ordering and fill pass on the queues and bin counts in h->trQueue / h->trHost
+// the ordering and fill pass on the queues and bin counts in h->trWs.queue / h->trWs.host
 int tr_fill(bhs_handle* h, const TrIn& in, int* Tj, value_t* Tx, int* perm)
 {
     const int n = in.n;
-    const int* queue = (const int*)h->trQueue.p;
-    const int* count = h->trHost + TR_COUNT;
-    const int* Tp = (const int*)h->trCnt.p;
+    const int* queue = (const int*)h->trWs.queue.p;
+    const int* count = h->trWs.host + TR_COUNT;
+    const int* Tp = (const int*)h->trWs.cnt.p;
     tr_u64* keys = (tr_u64*)h->trKeys.p;
     if (count[kTrShort]) {
         const int nq = count[kTrShort];
@@ -81,19 +54,16 @@ int tr_fill(bhs_handle* h, const TrIn& in, int* Tj, value_t* Tx, int* perm)
 int tr_run(bhs_handle* h, const TrIn& in, int* d_rowPtrT, int* Tj, value_t* Tx, int* perm, double* ms_out)
 {
     const int m = in.m, n = in.n;
-    BHS_TRY(tr_prepare(h));
+    SideWs& ws = h->trWs;
+    BHS_TRY(side_prepare(h, ws, TR_INTS, sizeof(int) * (size_t)kTrBins * (size_t)std::max(n, 1), (size_t)n + 1));
     const long long nWg = std::max<long long>(1, ((long long)m + kTrRows - 1) / kTrRows);
-    const int nTiles = (n + kScan1Tile - 1) / kScan1Tile;
-    BHS_TRY(ensure(h, h->trCnt, sizeof(int) * ((size_t)n + 1)));
     BHS_TRY(ensure(h, h->trCur, sizeof(int) * ((size_t)n + 1)));
-    BHS_TRY(ensure(h, h->trQueue, sizeof(int) * (size_t)kTrBins * (size_t)std::max(n, 1)));
     BHS_TRY(ensure(h, h->trWin, sizeof(int2) * (size_t)nWg));
     BHS_TRY(ensure(h, h->trKeys, sizeof(tr_u64) * (size_t)std::max(in.nnzX, 1)));
-    BHS_TRY(ensure(h, h->trTiles, sizeof(unsigned long long) * (size_t)std::max(nTiles, 1), true));
-    add_reset_stats(h);
-    int* ctl = (int*)h->trCtl.p;
-    int* cnt = (int*)h->trCnt.p;
-    BHS_HIP(hipEventRecord(h->trEv[0], h->stream));
+    side_reset_stats(h);
+    int* ctl = (int*)ws.ctl.p;
+    int* cnt = (int*)ws.cnt.p;
+    BHS_TRY(side_begin(h, ws));
     BHS_HIP(hipMemsetAsync(ctl, 0, sizeof(int) * TR_INTS, h->stream));
     BHS_HIP(hipMemsetAsync(cnt, 0, sizeof(int) * ((size_t)n + 1), h->stream));
     int stat = 0;
@@ -102,29 +72,16 @@ int tr_run(bhs_handle* h, const TrIn& in, int* d_rowPtrT, int* Tj, value_t* Tx, 
                            (int2*)h->trWin.p);
         if (n == 0) return 1;
         hipLaunchKernelGGL(k_tr_bin, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, n, (const int*)cnt, ctl,
-                           (int*)h->trQueue.p);
+                           (int*)ws.queue.p);
         return 2;
     }, &stat));
-    BHS_TRY(tr_read_ctl(h));
-    if (h->trHost[TR_ERR]) return BHS_ERR_INVALID_ARG;               // (nothing caller-owned has been written)
+    BHS_TRY(side_read_ctl(h, ws, TR_INTS));
+    if (ws.host[TR_ERR]) return BHS_ERR_INVALID_ARG;               // (nothing caller-owned has been written)
     h->stats[stat].nnz_out += in.nnzX;
-    if (nTiles == 0 || in.nnzX == 0) {
+    if (n == 0 || in.nnzX == 0) {
         BHS_HIP(hipMemsetAsync(d_rowPtrT, 0, sizeof(int) * ((size_t)n + 1), h->stream));
     } else {
-        h->trEpoch = (h->trEpoch + 1) & 0x3FFFFu;
-        if (h->trEpoch == 0) {                                       // (see scan_rowptr)
-            BHS_HIP(hipMemsetAsync(h->trTiles.p, 0, sizeof(unsigned long long) * (size_t)nTiles, h->stream));
-            h->trEpoch = 1;
-        }
-        BinSpec none;                                                // (no bins: the scan's histogram stays empty)
-        memset(&none, 0, sizeof(none));
-        BHS_TRY(timed(h, "transpose_scan", n, [&] {
-            hipLaunchKernelGGL(k_scan_onepass, dim3((unsigned)nTiles), dim3(kScan1Block), 0, h->stream, n, cnt, (const int*)h->trCur.p,
-                               (unsigned long long*)h->trTiles.p, h->trEpoch, ctl + TR_TICKET, (long long*)(ctl + TR_SCANTOTAL),
-                               ctl + TR_SCANBINS, none, ctl + TR_MAXCNT, (const int*)nullptr);
-            return 1;
-        }));
-        BHS_HIP(hipMemcpyAsync(d_rowPtrT, cnt, sizeof(int) * ((size_t)n + 1), hipMemcpyDeviceToDevice, h->stream));
+        BHS_TRY(side_scan(h, ws, "transpose_scan", kTrScanWords, n, (const int*)h->trCur.p, d_rowPtrT));
         BHS_HIP(hipMemcpyAsync(h->trCur.p, cnt, sizeof(int) * ((size_t)n + 1), hipMemcpyDeviceToDevice, h->stream));
         BHS_TRY(timed(h, "transpose_scatter", m, [&] {
             hipLaunchKernelGGL(k_tr_scatter, dim3((unsigned)nWg), dim3(256), 0, h->stream, m, in.nnzX, in.Xp, in.Xj, (int*)h->trCur.p,
@@ -133,18 +90,19 @@ int tr_run(bhs_handle* h, const TrIn& in, int* d_rowPtrT, int* Tj, value_t* Tx, 
         }));
         BHS_TRY(tr_fill(h, in, Tj, Tx, perm));
     }
-    BHS_HIP(hipEventRecord(h->trEv[1], h->stream));
+    BHS_TRY(side_end(h, ws));
     BHS_TRY(wait_stream(h));
-    BHS_TRY(tr_elapsed(h, ms_out));
-    return add_collect(h, 0);
+    BHS_TRY(side_elapsed(h, ws, ms_out));
+    return side_collect(h, 0);
 }
 
 int tr_values_run(bhs_handle* h, int nnzX, const value_t* Xx, const int* perm, value_t* Tx, double* ms_out)
 {
-    BHS_TRY(tr_prepare(h));
-    add_reset_stats(h);
-    int* ctl = (int*)h->trCtl.p;
-    BHS_HIP(hipEventRecord(h->trEv[0], h->stream));
+    SideWs& ws = h->trWs;
+    BHS_TRY(side_prepare(h, ws, TR_INTS, 0, 0));
+    side_reset_stats(h);
+    int* ctl = (int*)ws.ctl.p;
+    BHS_TRY(side_begin(h, ws));
     BHS_HIP(hipMemsetAsync(ctl, 0, sizeof(int) * TR_INTS, h->stream));
     if (nnzX > 0) {
         int stat = 0;
@@ -157,11 +115,11 @@ int tr_values_run(bhs_handle* h, int nnzX, const value_t* Xx, const int* perm, v
         }, &stat));
         h->stats[stat].nnz_out += nnzX;
     }
-    BHS_HIP(hipEventRecord(h->trEv[1], h->stream));
-    BHS_TRY(tr_read_ctl(h));
-    BHS_TRY(tr_elapsed(h, ms_out));
-    BHS_TRY(add_collect(h, 0));
-    return h->trHost[TR_ERR] ? (int)BHS_ERR_INVALID_ARG : (int)BHS_SUCCESS;
+    BHS_TRY(side_end(h, ws));
+    BHS_TRY(side_read_ctl(h, ws, TR_INTS));
+    BHS_TRY(side_elapsed(h, ws, ms_out));
+    BHS_TRY(side_collect(h, 0));
+    return ws.host[TR_ERR] ? (int)BHS_ERR_INVALID_ARG : (int)BHS_SUCCESS;
 }
 
 }  // namespace
@@ -176,12 +134,9 @@ int bhs_csr_transpose_device(bhs_handle* h, int m, int n, int nnzX, const bhs_va
     if (d_rowPtrT == d_rowPtrX || (nnzX > 0 && (d_colIndT == d_colIndX || (d_valT && d_valT == d_valX) || d_perm == d_colIndX ||
                                                 d_perm == d_colIndT)))
         return BHS_ERR_INVALID_ARG;                                  // (outputs must not overlap inputs)
-    BHS_HIP(hipSetDevice(h->device));
     TrIn in;
     in.m = m; in.n = n; in.nnzX = nnzX; in.Xp = d_rowPtrX; in.Xj = d_colIndX; in.Xx = (const value_t*)d_valX;
-    const int rc = tr_run(h, in, d_rowPtrT, d_colIndT, (value_t*)d_valT, d_perm, ms_out);
-    if (rc) settle(h);
-    return rc;
+    return guarded(h, [&] { return tr_run(h, in, d_rowPtrT, d_colIndT, (value_t*)d_valT, d_perm, ms_out); });
 }
 
 int bhs_csr_transpose_values_device(bhs_handle* h, int nnzX, const bhs_value_t* d_valX, const int* d_perm, bhs_value_t* d_valT,
@@ -189,10 +144,7 @@ int bhs_csr_transpose_values_device(bhs_handle* h, int nnzX, const bhs_value_t* 
 {
     if (!h || h->ps.open || nnzX < 0) return BHS_ERR_INVALID_ARG;
     if (nnzX > 0 && (!d_valX || !d_perm || !d_valT || d_valT == d_valX)) return BHS_ERR_INVALID_ARG;
-    BHS_HIP(hipSetDevice(h->device));
-    const int rc = tr_values_run(h, nnzX, (const value_t*)d_valX, d_perm, (value_t*)d_valT, ms_out);
-    if (rc) settle(h);
-    return rc;
+    return guarded(h, [&] { return tr_values_run(h, nnzX, (const value_t*)d_valX, d_perm, (value_t*)d_valT, ms_out); });
 }
 
 }  // extern "C"

@@ -1,7 +1,8 @@
 // bhsparse_hip.hip — libbhsparse_hip.so (see include/bhsparse_hip.h): the handle and its helpers here; the launch helpers,
 // the pipeline, the hand-over of a data set and the C-ABI in bhs_host_{launch,pipeline,setdata,cabi}.inc.h, the masked multiply
 // the sparse add, the entry selection, the transpose, the reductions and the scaling, the semiring multiply and the extraction in
-// bhs_host_{masked,add,select,transpose,reduce,semiring,extract}.inc.h (one translation unit).
+// bhs_host_{masked,add,select,transpose,reduce,semiring,extract}.inc.h on the shared plumbing of bhs_host_side.inc.h (one
+// translation unit).
 //
 // Pipeline of one bhs_spgemm() (replaces bhsparse::spgemm_cuda, bhsparse.h:297-339):
 //   stage 1  k_upper_bound (ub per row, nnzCt, symbolic-bin histogram)          <- compute_nnzCt + statistics()
@@ -83,6 +84,15 @@ namespace {
 struct DevBuf {
     void*  p = nullptr;
     size_t cap = 0;
+};
+
+// What every operation beside the pipeline keeps for itself (bhs_host_side.inc.h sets it up, reads it and scans in it): one
+// instance per family on the handle, so that no family's call moves another's buffers or the pipeline's
+struct SideWs {
+    DevBuf ctl, queue, cnt, tiles;       // the control block (counters); per-bin queues; the counts, scanned in place; the tile words of that scan
+    int* host = nullptr;                 // pinned mirror of ctl
+    hipEvent_t ev[2] = {nullptr, nullptr};   // the span a call reports as its time
+    unsigned epoch = 0;                  // tag of the last scan's tile words
 };
 
 // ---- bin tables ------------------------------------------------------------
@@ -348,20 +358,16 @@ struct bhs_handle {
     const int* resCj = nullptr;          // the colIndC array the finished multiply wrote (own or bound): get_C serves no other
     value_t* extCx = nullptr;
     long long extCap = 0;
-    // the masked multiply (bhs_host_masked.inc.h): buffers of its own, so that it leaves the ordinary multiply's state alone
-    DevBuf maskCtl, maskQueue;           // counters; per-bin queues of (row, products)
+    // the masked multiply (bhs_host_masked.inc.h, and the semiring multiply through it): a workspace of its own, so that it
+    // leaves the ordinary multiply's state alone -- queues of (row, products), no counts
+    SideWs maskWs;
     DevBuf maskM[3];                     // bhs_spgemm_masked: device copies of rowPtrM, colIndM and valC
-    int* maskHost = nullptr;             // pinned mirror of maskCtl
-    hipEvent_t maskEv[2] = {nullptr, nullptr};
     int maskTableLog2 = 11;              // option "masked_max_table_log2": mask rows beyond 2^v entries take k_masked_long
     long long maskHubMin = 1 << 17;      // option "masked_hub_min_products": rows of this many products go to k_masked_hub
-    // the sparse add (bhs_host_add.inc.h): buffers of its own as well
-    DevBuf addCtl, addQueue, addCnt;     // counters; per-bin queues of rows; the rows' counts, scanned in place
-    DevBuf addTiles, addPos;             // tile words of its scan (epoch addEpoch); where in C every entry of D sits (in-place path)
+    // the sparse add (bhs_host_add.inc.h): queues of rows, the rows' counts
+    SideWs addWs;
+    DevBuf addPos;                       // where in C every entry of D sits (in-place path)
     DevBuf addD[3];                      // bhs_spgemm_add: device copies of rowPtrD, colIndD and valD
-    int* addHost = nullptr;              // pinned mirror of addCtl
-    hipEvent_t addEv[2] = {nullptr, nullptr};
-    unsigned addEpoch = 0;
     int addInplace = 1;                  // option "add_inplace": 0 the sum always goes to the second set of arrays
     int addInplaceUsed = 0;              // bhs_get_info "add_inplace_used": the last bhs_spgemm_add added into valC in place
     // C = alpha A·B + beta D where D reaches outside A·B: the sum, served by the getters until the next multiply drops it
@@ -370,29 +376,21 @@ struct bhs_handle {
     DevBuf sumCp, sumCj, sumCx;
     bool sumActive = false;
     long long sumNnz = 0;
-    // the entry selection (bhs_host_select.inc.h): buffers of its own as well
-    DevBuf selCtl, selQueue, selCnt, selTiles;   // counters; per-bin queues of rows; the rows' counts, scanned in place; its scan's tile words (epoch selEpoch)
-    int* selHost = nullptr;              // pinned mirror of selCtl
-    hipEvent_t selEv[2] = {nullptr, nullptr};
-    unsigned selEpoch = 0;
+    // the entry selection (bhs_host_select.inc.h): queues of rows, the rows' counts
+    SideWs selWs;
     long long selDropped = 0;            // bhs_get_info "select_dropped": entries the last bhs_spgemm_select removed
-    // the transpose (bhs_host_transpose.inc.h): buffers of its own as well
-    DevBuf trCtl, trCnt, trCur, trQueue;  // counters; the columns' counts, scanned in place (rowPtrT); the T rows' next free places; per-bin queues of T rows
-    DevBuf trWin, trKeys, trTiles;       // the column window of every workgroup of k_tr_count; the keys (row << 32 | position in X), 8 bytes an entry; its scan's tile words (epoch trEpoch)
-    int* trHost = nullptr;               // pinned mirror of trCtl
-    hipEvent_t trEv[2] = {nullptr, nullptr};
-    unsigned trEpoch = 0;
-    // the extraction (bhs_host_extract.inc.h): buffers of its own as well
-    DevBuf exCtl, exCnt, exQueue, exInv;  // counters; the Z rows' counts, scanned in place (rowPtrZ); per-bin queues of Z rows; the inverse column map, n ints
-    DevBuf exKeys, exTiles;              // the keys (place << 32 | position in X) of Z rows beyond the LDS, 8 bytes an entry of Z, only where such rows exist; its scan's tile words (epoch exEpoch)
-    int* exHost = nullptr;               // pinned mirror of exCtl
-    hipEvent_t exEv[2] = {nullptr, nullptr};
-    unsigned exEpoch = 0;
+    // the transpose (bhs_host_transpose.inc.h): queues of T rows, the columns' counts (scanned: rowPtrT)
+    SideWs trWs;
+    DevBuf trCur;                        // the T rows' next free places
+    DevBuf trWin, trKeys;                // the column window of every workgroup of k_tr_count; the keys (row << 32 | position in X), 8 bytes an entry
+    // the extraction (bhs_host_extract.inc.h): queues of Z rows, the Z rows' counts (scanned: rowPtrZ)
+    SideWs exWs;
+    DevBuf exInv;                        // the inverse column map, n ints
+    DevBuf exKeys;                       // the keys (place << 32 | position in X) of Z rows beyond the LDS, 8 bytes an entry of Z, only where such rows exist
     long long exReordered = 0;           // bhs_get_info "extract_reordered_rows": Z rows the last numeric call had to put in order
-    // the reductions and the scaling (bhs_host_reduce.inc.h): buffers of their own as well
-    DevBuf rdCtl, rdQueue, rdAcc, rdPart; // counters; the queues of the rows beyond the short bin (2 x m ints); the accumulators, 8 bytes an output; the partials of a total
-    int* rdHost = nullptr;               // pinned mirror of rdCtl
-    hipEvent_t rdEv[2] = {nullptr, nullptr};
+    // the reductions and the scaling (bhs_host_reduce.inc.h): the queues of the rows beyond the short bin (2 x m ints), no counts
+    SideWs rdWs;
+    DevBuf rdAcc, rdPart;                // the accumulators, 8 bytes an output; the partials of a total
 };
 
 namespace {
@@ -452,6 +450,14 @@ void release(DevBuf& b)
     if (b.p) (void)hipFree(b.p);
     b.p = nullptr;
     b.cap = 0;
+}
+
+void release(SideWs& ws)
+{
+    release(ws.ctl); release(ws.queue); release(ws.cnt); release(ws.tiles);
+    if (ws.host) (void)hipHostFree(ws.host);
+    ws.host = nullptr;
+    for (hipEvent_t& e : ws.ev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
 }
 
 // resident workgroups per CU of `kern` on this handle's device (>= 1), cached per handle; kernels with more than
@@ -538,6 +544,7 @@ int timed(bhs_handle* h, const char* name, int64_t rows, F&& enqueue, int* stat 
 inline int one_launch(int rc) { return rc != BHS_SUCCESS ? rc : 1; }
 
 #include "bhs_host_launch.inc.h"
+#include "bhs_host_side.inc.h"
 #include "bhs_host_pipeline.inc.h"
 #include "bhs_host_setdata.inc.h"
 
