@@ -10,7 +10,9 @@ is a thin call into the C-ABI of libbhsparse_hip.so; arrays are numpy buffers
 (host entry, like the reference) or raw device pointers / torch tensors
 (`initData_device`, used by the benchmark and the multi-GPU path).
 """
+import contextlib
 import ctypes as C
+import time
 
 import numpy as np
 
@@ -39,6 +41,30 @@ def _ptr(a):
     if hasattr(a, "data_ptr"):          # torch tensor (device or host)
         return C.c_void_p(a.data_ptr())
     raise TypeError("unsupported buffer type %r" % type(a))
+
+
+def _sync(*arrays):
+    """The library works on its own stream (see initData_device): before it reads torch tensors of the GPU, wait for the
+    kernels torch has queued on them.  Host arrays and raw addresses need no wait."""
+    if any(hasattr(t, "is_cuda") and t.is_cuda for t in arrays):
+        import torch
+        torch.cuda.synchronize()
+
+
+def _alloc(n, dtype, device):
+    """Room for n entries as a torch tensor, never a zero-size allocation (its data pointer would be null): the caller
+    slices [:n]."""
+    import torch
+    return torch.empty(max(n, 1), dtype=dtype, device=device)
+
+
+def _head(a, n):
+    return None if a is None else a[:n]
+
+
+def _check(err, where):
+    if err != BHSPARSE_SUCCESS:
+        raise BhsparseError(where, err)
 
 
 class bhsparse(object):
@@ -155,43 +181,94 @@ class bhsparse(object):
         return BHSPARSE_SUCCESS
 
     # -- extension (not in the reference): the masked multiply C<M> = A·B (bhs_spgemm_masked, include/bhsparse_hip.h)
-    def spgemm_masked(self, rowPtrM, colIndM, valC=None):
-        """valC[p] = (A·B)(i, colIndM[p]) for every entry p of row i of the pattern M (numpy int32 CSR, m x n, rows strictly
-        ascending), 0 where no product lands.  Returns valC (allocated when None).  Raises BhsparseError on failure (an
-        invalid M: code BHS_ERR_INVALID_ARG, valC untouched).  Sets nnzCt (products of A·B) and masked_ms (device time)."""
+    def _masked_call(self, fn, semiring, rowPtrM, colIndM, nnzM, valC):
+        """One of the four masked entries (host or device arrays, with or without a leading semiring): the status code;
+        sets nnzCt and masked_ms / semiring_ms on success."""
+        nnzCt, ms = C.c_int64(0), C.c_double(0)
+        lead = () if semiring is None else (semiring,)
+        err = fn(self._h, *lead, rowPtrM, colIndM, nnzM, valC, C.byref(nnzCt), C.byref(ms))
+        if err == BHSPARSE_SUCCESS:
+            self.nnzCt = int(nnzCt.value)
+            setattr(self, "masked_ms" if semiring is None else "semiring_ms", float(ms.value))
+        return err
+
+    def _masked_host(self, semiring, rowPtrM, colIndM, valC):
+        where = "bhs_spgemm_masked" if semiring is None else "bhs_spgemm_semiring_masked"
         if self._h is None:
-            raise BhsparseError("bhs_spgemm_masked", _lib.BHS_ERR_NOT_READY)
+            raise BhsparseError(where, _lib.BHS_ERR_NOT_READY)
         rowPtrM = np.ascontiguousarray(rowPtrM, np.int32)
         colIndM = np.ascontiguousarray(colIndM, np.int32)
         if rowPtrM.size < self._m + 1:
-            raise BhsparseError("bhs_spgemm_masked", _lib.BHS_ERR_INVALID_ARG)
+            raise BhsparseError(where, _lib.BHS_ERR_INVALID_ARG)
         nnzM = colIndM.size
         if valC is None:
             valC = np.empty(nnzM, self._vdt)
         elif not (isinstance(valC, np.ndarray) and valC.dtype == self._vdt and valC.size >= nnzM and valC.flags.c_contiguous):
-            raise BhsparseError("bhs_spgemm_masked", _lib.BHS_ERR_INVALID_ARG)
-        nnzCt, ms = C.c_int64(0), C.c_double(0)
-        err = self._lib.bhs_spgemm_masked(self._h, _ptr(rowPtrM), _ptr(colIndM) if nnzM else None, nnzM,
-                                          _ptr(valC) if nnzM else None, C.byref(nnzCt), C.byref(ms))
-        if err != BHSPARSE_SUCCESS:
-            raise BhsparseError("bhs_spgemm_masked", err)
-        self.nnzCt, self.masked_ms = int(nnzCt.value), float(ms.value)
+            raise BhsparseError(where, _lib.BHS_ERR_INVALID_ARG)
+        fn = self._lib.bhs_spgemm_masked if semiring is None else self._lib.bhs_spgemm_semiring_masked
+        _check(self._masked_call(fn, semiring, _ptr(rowPtrM), _ptr(colIndM) if nnzM else None, nnzM,
+                                 _ptr(valC) if nnzM else None), where)
         return valC
+
+    def _masked_device(self, semiring, d_rowPtrM, d_colIndM, nnzM, d_valC):
+        if self._h is None:
+            return _lib.BHS_ERR_NOT_READY
+        _sync(d_rowPtrM, d_colIndM, d_valC)
+        fn = self._lib.bhs_spgemm_masked_device if semiring is None else self._lib.bhs_spgemm_semiring_masked_device
+        return self._masked_call(fn, semiring, _ptr(d_rowPtrM), _ptr(d_colIndM), int(nnzM), _ptr(d_valC))
+
+    def spgemm_masked(self, rowPtrM, colIndM, valC=None):
+        """valC[p] = (A·B)(i, colIndM[p]) for every entry p of row i of the pattern M (numpy int32 CSR, m x n, rows strictly
+        ascending), 0 where no product lands.  Returns valC (allocated when None).  Raises BhsparseError on failure (an
+        invalid M: code BHS_ERR_INVALID_ARG, valC untouched).  Sets nnzCt (products of A·B) and masked_ms (device time)."""
+        return self._masked_host(None, rowPtrM, colIndM, valC)
 
     def spgemm_masked_device(self, d_rowPtrM, d_colIndM, nnzM, d_valC):
         """The same on device arrays (torch tensors on this handle's GPU, or raw device addresses); valC is written in
         place.  Returns the status code (0 on success) and sets nnzCt / masked_ms."""
-        if self._h is None:
-            return _lib.BHS_ERR_NOT_READY
-        if any(hasattr(t, "is_cuda") and t.is_cuda for t in (d_rowPtrM, d_colIndM, d_valC)):
-            import torch
-            torch.cuda.synchronize()                       # the library works on its own stream (see initData_device)
-        nnzCt, ms = C.c_int64(0), C.c_double(0)
-        err = self._lib.bhs_spgemm_masked_device(self._h, _ptr(d_rowPtrM), _ptr(d_colIndM), int(nnzM), _ptr(d_valC),
-                                                 C.byref(nnzCt), C.byref(ms))
+        return self._masked_device(None, d_rowPtrM, d_colIndM, nnzM, d_valC)
+
+    def _multiply(self, fn, lead, ms1, ms0=None, wall=False):
+        """A multiply-then-post-operation entry of the C-ABI, fn(handle, *lead, nnzCt, nnzC, ms[2]): the status code.  On
+        success sets nnzCt, nnzC, the attribute `ms1` from ms[1] (device time of the post-operation) and, where named,
+        `ms0` from ms[0] (device time of the multiply).  wall: time_ms is taken around the call, as spgemm() does."""
+        nnzCt, nnzC = C.c_int64(0), C.c_int(0)
+        ms = (C.c_double * 2)()
+        t0 = time.perf_counter()
+        err = fn(self._h, *lead, C.byref(nnzCt), C.byref(nnzC), ms)
+        if wall:
+            self.time_ms = (time.perf_counter() - t0) * 1e3
         if err == BHSPARSE_SUCCESS:
-            self.nnzCt, self.masked_ms = int(nnzCt.value), float(ms.value)
+            self.nnzCt, self.nnzC = int(nnzCt.value), int(nnzC.value)
+            setattr(self, ms1, float(ms[1]))
+            if ms0 is not None:
+                setattr(self, ms0, float(ms[0]))
         return err
+
+    def _timed(self, fn, ms_attr, *args):
+        """A side operation of the C-ABI, fn(handle, *args, ms): the status code; sets `ms_attr` (device time) on success."""
+        ms = C.c_double(0)
+        err = fn(self._h, *args, C.byref(ms))
+        if err == BHSPARSE_SUCCESS:
+            setattr(self, ms_attr, float(ms.value))
+        return err
+
+    def _symbolic_numeric(self, family, rows, device, vdtype, perm, symbolic, numeric):
+        """The two calls of `family` (add, select, extract) on arrays made here: symbolic(Zp) -> (status, nnzZ, ...) fills
+        the row pointer of rows + 1 ints, then numeric(nnzZ, Zp, Zj, Zx, pm) -> status fills arrays of nnzZ entries (Zx only
+        for a `vdtype`, pm only for `perm`).  Returns (Zp, Zj, Zx, pm) cut to nnzZ entries, followed by whatever else
+        symbolic returned; raises BhsparseError naming the call that failed."""
+        import torch
+        torch.cuda.synchronize()                           # the library works on its own stream (see initData_device)
+        Zp = torch.empty(rows + 1, dtype=torch.int32, device=device)
+        err, nnzZ, *rest = symbolic(Zp)
+        _check(err, family + "_symbolic_device")
+        Zj = _alloc(nnzZ, torch.int32, device)
+        Zx = None if vdtype is None else _alloc(nnzZ, vdtype, device)
+        pm = _alloc(nnzZ, torch.int32, device) if perm else None
+        torch.cuda.synchronize()
+        _check(numeric(nnzZ, Zp, Zj, Zx, pm), family + "_numeric_device")
+        return (Zp, Zj[:nnzZ], _head(Zx, nnzZ), _head(pm, nnzZ)) + tuple(rest)
 
     # -- extension (not in the reference): C = alpha A·B + beta D and the sparse add (include/bhsparse_hip.h, "sparse add")
     def spgemm_add(self, alpha, beta, rowPtrD, colIndD, valD):
@@ -201,37 +278,23 @@ class bhsparse(object):
         get_nnzC / get_C / get_rowptrC / get_C_device then return this C."""
         if self._h is None:
             return _lib.BHS_ERR_NOT_READY
-        import time
         rowPtrD = np.ascontiguousarray(rowPtrD, np.int32)
         colIndD = np.ascontiguousarray(colIndD, np.int32)
         valD = np.ascontiguousarray(valD, self._vdt)
         if rowPtrD.size < self._m + 1 or valD.size != colIndD.size:
             return _lib.BHS_ERR_INVALID_ARG
         nnzD = colIndD.size
-        nnzCt, nnzC = C.c_int64(0), C.c_int(0)
-        ms = (C.c_double * 2)()
-        t0 = time.perf_counter()
-        err = self._lib.bhs_spgemm_add(self._h, float(alpha), float(beta), nnzD, _ptr(valD) if nnzD else None, _ptr(rowPtrD),
-                                       _ptr(colIndD) if nnzD else None, _ptr(self._rowptrC), C.byref(nnzCt), C.byref(nnzC), ms)
-        self.time_ms = (time.perf_counter() - t0) * 1e3
-        if err == BHSPARSE_SUCCESS:
-            self.nnzCt, self.nnzC, self.add_ms = int(nnzCt.value), int(nnzC.value), float(ms[1])
-        return err
+        return self._multiply(self._lib.bhs_spgemm_add, (float(alpha), float(beta), nnzD, _ptr(valD) if nnzD else None,
+                                                         _ptr(rowPtrD), _ptr(colIndD) if nnzD else None,
+                                                         _ptr(self._rowptrC)), "add_ms", wall=True)
 
     def spgemm_add_device(self, alpha, beta, nnzD, d_valD, d_rowPtrD, d_colIndD):
         """The same with D on the device (torch tensors on this handle's GPU, or raw device addresses)."""
         if self._h is None:
             return _lib.BHS_ERR_NOT_READY
-        if any(hasattr(t, "is_cuda") and t.is_cuda for t in (d_valD, d_rowPtrD, d_colIndD)):
-            import torch
-            torch.cuda.synchronize()                       # the library works on its own stream (see initData_device)
-        nnzCt, nnzC = C.c_int64(0), C.c_int(0)
-        ms = (C.c_double * 2)()
-        err = self._lib.bhs_spgemm_add_device(self._h, float(alpha), float(beta), int(nnzD), _ptr(d_valD), _ptr(d_rowPtrD),
-                                              _ptr(d_colIndD), _ptr(self._rowptrC), C.byref(nnzCt), C.byref(nnzC), ms)
-        if err == BHSPARSE_SUCCESS:
-            self.nnzCt, self.nnzC, self.add_ms = int(nnzCt.value), int(nnzC.value), float(ms[1])
-        return err
+        _sync(d_valD, d_rowPtrD, d_colIndD)
+        return self._multiply(self._lib.bhs_spgemm_add_device, (float(alpha), float(beta), int(nnzD), _ptr(d_valD),
+                                                                _ptr(d_rowPtrD), _ptr(d_colIndD), _ptr(self._rowptrC)), "add_ms")
 
     def csr_add_symbolic_device(self, m, n, nnzX, d_rowPtrX, d_colIndX, nnzY, d_rowPtrY, d_colIndY, d_rowPtrZ):
         """bhs_csr_add_symbolic_device: (status, nnz(Z), y_inside_x); d_rowPtrZ (m+1 ints on the device) is written."""
@@ -244,32 +307,21 @@ class bhsparse(object):
     def csr_add_numeric_device(self, m, n, alpha, nnzX, d_valX, d_rowPtrX, d_colIndX, beta, nnzY, d_valY, d_rowPtrY, d_colIndY,
                                d_rowPtrZ, d_colIndZ, d_valZ):
         """bhs_csr_add_numeric_device: the status code; sets add_ms."""
-        ms = C.c_double(0)
-        err = self._lib.bhs_csr_add_numeric_device(self._h, int(m), int(n), float(alpha), int(nnzX), _ptr(d_valX), _ptr(d_rowPtrX),
-                                                   _ptr(d_colIndX), float(beta), int(nnzY), _ptr(d_valY), _ptr(d_rowPtrY),
-                                                   _ptr(d_colIndY), _ptr(d_rowPtrZ), _ptr(d_colIndZ), _ptr(d_valZ), C.byref(ms))
-        if err == BHSPARSE_SUCCESS:
-            self.add_ms = float(ms.value)
-        return err
+        return self._timed(self._lib.bhs_csr_add_numeric_device, "add_ms", int(m), int(n), float(alpha), int(nnzX),
+                           _ptr(d_valX), _ptr(d_rowPtrX), _ptr(d_colIndX), float(beta), int(nnzY), _ptr(d_valY),
+                           _ptr(d_rowPtrY), _ptr(d_colIndY), _ptr(d_rowPtrZ), _ptr(d_colIndZ), _ptr(d_valZ))
 
     def csr_add_device(self, m, n, alpha, X, beta, Y):
         """Z = alpha X + beta Y on device arrays: X, Y = (rowPtr, colInd, val) torch tensors on this handle's GPU.  Returns
         (rowPtrZ, colIndZ, valZ, y_inside_x) as torch tensors; raises BhsparseError on failure."""
-        import torch
-        torch.cuda.synchronize()                           # the library works on its own stream (see initData_device)
         Xp, Xj, Xx = X
         Yp, Yj, Yx = Y
-        Zp = torch.empty(m + 1, dtype=torch.int32, device=Xp.device)
-        err, nnzZ, inside = self.csr_add_symbolic_device(m, n, Xj.numel(), Xp, Xj, Yj.numel(), Yp, Yj, Zp)
-        if err != BHSPARSE_SUCCESS:
-            raise BhsparseError("bhs_csr_add_symbolic_device", err)
-        Zj = torch.empty(max(nnzZ, 1), dtype=torch.int32, device=Xp.device)
-        Zx = torch.empty(max(nnzZ, 1), dtype=Xx.dtype, device=Xp.device)
-        torch.cuda.synchronize()
-        err = self.csr_add_numeric_device(m, n, alpha, Xj.numel(), Xx, Xp, Xj, beta, Yj.numel(), Yx, Yp, Yj, Zp, Zj, Zx)
-        if err != BHSPARSE_SUCCESS:
-            raise BhsparseError("bhs_csr_add_numeric_device", err)
-        return Zp, Zj[:nnzZ], Zx[:nnzZ], inside
+        Zp, Zj, Zx, _, inside = self._symbolic_numeric(
+            "bhs_csr_add", m, Xp.device, Xx.dtype, False,
+            lambda Zp: self.csr_add_symbolic_device(m, n, Xj.numel(), Xp, Xj, Yj.numel(), Yp, Yj, Zp),
+            lambda nnzZ, Zp, Zj, Zx, pm: self.csr_add_numeric_device(m, n, alpha, Xj.numel(), Xx, Xp, Xj, beta, Yj.numel(), Yx,
+                                                                     Yp, Yj, Zp, Zj, Zx))
+        return Zp, Zj, Zx, inside
 
     # -- extension (not in the reference): entry selection and the pruned multiply (include/bhsparse_hip.h, "entry selection")
     def spgemm_select(self, spec):
@@ -279,26 +331,13 @@ class bhsparse(object):
         then return the selected C."""
         if self._h is None:
             return _lib.BHS_ERR_NOT_READY
-        import time
-        nnzCt, nnzC = C.c_int64(0), C.c_int(0)
-        ms = (C.c_double * 2)()
-        t0 = time.perf_counter()
-        err = self._lib.bhs_spgemm_select(self._h, C.byref(spec), _ptr(self._rowptrC), C.byref(nnzCt), C.byref(nnzC), ms)
-        self.time_ms = (time.perf_counter() - t0) * 1e3
-        if err == BHSPARSE_SUCCESS:
-            self.nnzCt, self.nnzC, self.select_ms = int(nnzCt.value), int(nnzC.value), float(ms[1])
-        return err
+        return self._multiply(self._lib.bhs_spgemm_select, (C.byref(spec), _ptr(self._rowptrC)), "select_ms", wall=True)
 
     def spgemm_select_device(self, spec, d_rowPtrC=None):
         """The same; d_rowPtrC (may be None): m+1 ints on the device that receive the selected C's row pointer."""
         if self._h is None:
             return _lib.BHS_ERR_NOT_READY
-        nnzCt, nnzC = C.c_int64(0), C.c_int(0)
-        ms = (C.c_double * 2)()
-        err = self._lib.bhs_spgemm_select_device(self._h, C.byref(spec), _ptr(d_rowPtrC), C.byref(nnzCt), C.byref(nnzC), ms)
-        if err == BHSPARSE_SUCCESS:
-            self.nnzCt, self.nnzC, self.select_ms = int(nnzCt.value), int(nnzC.value), float(ms[1])
-        return err
+        return self._multiply(self._lib.bhs_spgemm_select_device, (C.byref(spec), _ptr(d_rowPtrC)), "select_ms")
 
     def csr_select_symbolic_device(self, m, n, nnzX, d_valX, d_rowPtrX, d_colIndX, spec, d_rowPtrZ):
         """bhs_csr_select_symbolic_device: (status, nnz(Z)); d_rowPtrZ (m+1 ints on the device) is written."""
@@ -309,44 +348,26 @@ class bhsparse(object):
 
     def csr_select_numeric_device(self, m, n, nnzX, d_valX, d_rowPtrX, d_colIndX, spec, d_rowPtrZ, d_colIndZ, d_valZ):
         """bhs_csr_select_numeric_device: the status code; sets select_ms."""
-        ms = C.c_double(0)
-        err = self._lib.bhs_csr_select_numeric_device(self._h, int(m), int(n), int(nnzX), _ptr(d_valX), _ptr(d_rowPtrX),
-                                                      _ptr(d_colIndX), C.byref(spec), _ptr(d_rowPtrZ), _ptr(d_colIndZ),
-                                                      _ptr(d_valZ), C.byref(ms))
-        if err == BHSPARSE_SUCCESS:
-            self.select_ms = float(ms.value)
-        return err
+        return self._timed(self._lib.bhs_csr_select_numeric_device, "select_ms", int(m), int(n), int(nnzX), _ptr(d_valX),
+                           _ptr(d_rowPtrX), _ptr(d_colIndX), C.byref(spec), _ptr(d_rowPtrZ), _ptr(d_colIndZ), _ptr(d_valZ))
 
     def csr_select_device(self, m, n, X, spec, values=True):
         """Z = select(X) on device arrays: X = (rowPtr, colInd, val) torch tensors on this handle's GPU (val may be None for
         a rule without value flags).  Returns (rowPtrZ, colIndZ, valZ) as torch tensors (valZ None when values is false or
         X has none); raises BhsparseError on failure."""
-        import torch
-        torch.cuda.synchronize()                           # the library works on its own stream (see initData_device)
         Xp, Xj, Xx = X
-        Zp = torch.empty(m + 1, dtype=torch.int32, device=Xp.device)
-        err, nnzZ = self.csr_select_symbolic_device(m, n, Xj.numel(), Xx, Xp, Xj, spec, Zp)
-        if err != BHSPARSE_SUCCESS:
-            raise BhsparseError("bhs_csr_select_symbolic_device", err)
-        Zj = torch.empty(max(nnzZ, 1), dtype=torch.int32, device=Xp.device)
-        Zx = torch.empty(max(nnzZ, 1), dtype=Xx.dtype, device=Xp.device) if (values and Xx is not None) else None
-        torch.cuda.synchronize()
-        err = self.csr_select_numeric_device(m, n, Xj.numel(), Xx, Xp, Xj, spec, Zp, Zj, Zx)
-        if err != BHSPARSE_SUCCESS:
-            raise BhsparseError("bhs_csr_select_numeric_device", err)
-        return Zp, Zj[:nnzZ], (Zx[:nnzZ] if Zx is not None else None)
+        return self._symbolic_numeric(
+            "bhs_csr_select", m, Xp.device, Xx.dtype if (values and Xx is not None) else None, False,
+            lambda Zp: self.csr_select_symbolic_device(m, n, Xj.numel(), Xx, Xp, Xj, spec, Zp),
+            lambda nnzZ, Zp, Zj, Zx, pm: self.csr_select_numeric_device(m, n, Xj.numel(), Xx, Xp, Xj, spec, Zp, Zj, Zx))[:3]
 
     # -- extension (not in the reference): the stable transpose and its pattern reuse (include/bhsparse_hip.h, "transpose")
     def csr_transpose_raw_device(self, m, n, nnzX, d_valX, d_rowPtrX, d_colIndX, d_rowPtrT, d_colIndT, d_valT, d_perm):
         """bhs_csr_transpose_device: the status code; sets transpose_ms."""
         if self._h is None:
             return _lib.BHS_ERR_NOT_READY
-        ms = C.c_double(0)
-        err = self._lib.bhs_csr_transpose_device(self._h, int(m), int(n), int(nnzX), _ptr(d_valX), _ptr(d_rowPtrX), _ptr(d_colIndX),
-                                                 _ptr(d_rowPtrT), _ptr(d_colIndT), _ptr(d_valT), _ptr(d_perm), C.byref(ms))
-        if err == BHSPARSE_SUCCESS:
-            self.transpose_ms = float(ms.value)
-        return err
+        return self._timed(self._lib.bhs_csr_transpose_device, "transpose_ms", int(m), int(n), int(nnzX), _ptr(d_valX),
+                           _ptr(d_rowPtrX), _ptr(d_colIndX), _ptr(d_rowPtrT), _ptr(d_colIndT), _ptr(d_valT), _ptr(d_perm))
 
     def csr_transpose_device(self, m, n, X, values=True, perm=False):
         """T = X^T on device arrays: X = (rowPtr, colInd, val) torch tensors on this handle's GPU (val may be None: the
@@ -357,14 +378,12 @@ class bhsparse(object):
         Xp, Xj, Xx = X
         nnz = Xj.numel()
         Tp = torch.empty(n + 1, dtype=torch.int32, device=Xp.device)
-        Tj = torch.empty(max(nnz, 1), dtype=torch.int32, device=Xp.device)
-        Tx = torch.empty(max(nnz, 1), dtype=Xx.dtype, device=Xp.device) if (values and Xx is not None) else None
-        pm = torch.empty(max(nnz, 1), dtype=torch.int32, device=Xp.device) if perm else None
+        Tj = _alloc(nnz, torch.int32, Xp.device)
+        Tx = _alloc(nnz, Xx.dtype, Xp.device) if (values and Xx is not None) else None
+        pm = _alloc(nnz, torch.int32, Xp.device) if perm else None
         torch.cuda.synchronize()
-        err = self.csr_transpose_raw_device(m, n, nnz, Xx, Xp, Xj, Tp, Tj, Tx, pm)
-        if err != BHSPARSE_SUCCESS:
-            raise BhsparseError("bhs_csr_transpose_device", err)
-        return Tp, Tj[:nnz], (Tx[:nnz] if Tx is not None else None), (pm[:nnz] if pm is not None else None)
+        _check(self.csr_transpose_raw_device(m, n, nnz, Xx, Xp, Xj, Tp, Tj, Tx, pm), "bhs_csr_transpose_device")
+        return Tp, Tj[:nnz], _head(Tx, nnz), _head(pm, nnz)
 
     def csr_transpose_values_device(self, d_valX, d_perm, d_valT=None):
         """valT[q] = valX[perm[q]] on torch tensors of this handle's GPU (bhs_csr_transpose_values_device): the values of a
@@ -372,12 +391,11 @@ class bhsparse(object):
         import torch
         nnz = d_perm.numel()
         if d_valT is None:
-            d_valT = torch.empty(max(nnz, 1), dtype=d_valX.dtype, device=d_valX.device)[:nnz]
+            d_valT = _alloc(nnz, d_valX.dtype, d_valX.device)[:nnz]
         torch.cuda.synchronize()
         ms = C.c_double(0)
-        err = self._lib.bhs_csr_transpose_values_device(self._h, int(nnz), _ptr(d_valX), _ptr(d_perm), _ptr(d_valT), C.byref(ms))
-        if err != BHSPARSE_SUCCESS:
-            raise BhsparseError("bhs_csr_transpose_values_device", err)
+        _check(self._lib.bhs_csr_transpose_values_device(self._h, int(nnz), _ptr(d_valX), _ptr(d_perm), _ptr(d_valT),
+                                                         C.byref(ms)), "bhs_csr_transpose_values_device")
         self.transpose_ms = float(ms.value)
         return d_valT
 
@@ -407,13 +425,9 @@ class bhsparse(object):
         if self._h is None:
             return _lib.BHS_ERR_NOT_READY
         d_rows, d_cols = self._index_list(d_rows), self._index_list(d_cols)
-        ms = C.c_double(0)
-        err = self._lib.bhs_csr_extract_numeric_device(self._h, int(m), int(n), int(nnzX), _ptr(d_valX), _ptr(d_rowPtrX),
-                                                       _ptr(d_colIndX), int(mI), _ptr(d_rows), int(nJ), _ptr(d_cols), int(nnzZ),
-                                                       _ptr(d_rowPtrZ), _ptr(d_colIndZ), _ptr(d_valZ), _ptr(d_perm), C.byref(ms))
-        if err == BHSPARSE_SUCCESS:
-            self.extract_ms = float(ms.value)
-        return err
+        return self._timed(self._lib.bhs_csr_extract_numeric_device, "extract_ms", int(m), int(n), int(nnzX), _ptr(d_valX),
+                           _ptr(d_rowPtrX), _ptr(d_colIndX), int(mI), _ptr(d_rows), int(nJ), _ptr(d_cols), int(nnzZ),
+                           _ptr(d_rowPtrZ), _ptr(d_colIndZ), _ptr(d_valZ), _ptr(d_perm))
 
     def csr_extract_raw_device(self, m, n, nnzX, d_valX, d_rowPtrX, d_colIndX, mI, d_rows, nJ, d_cols, d_rowPtrZ, d_colIndZ,
                                d_valZ, d_perm):
@@ -430,47 +444,30 @@ class bhsparse(object):
         the pattern alone); rows / cols: int32 torch tensors there, or None for all of them in order.  Returns (rowPtrZ,
         colIndZ, valZ, perm) as torch tensors (valZ None when values is false or X has none, perm None unless asked for);
         raises BhsparseError on failure."""
-        import torch
-        torch.cuda.synchronize()                           # the library works on its own stream (see initData_device)
         Xp, Xj, Xx = X
         nnzX = Xj.numel()
         mI = m if rows is None else rows.numel()
         nJ = n if cols is None else cols.numel()
-        Zp = torch.empty(mI + 1, dtype=torch.int32, device=Xp.device)
-        err, nnzZ = self.csr_extract_symbolic_device(m, n, nnzX, Xp, Xj, mI, rows, nJ, cols, Zp)
-        if err != BHSPARSE_SUCCESS:
-            raise BhsparseError("bhs_csr_extract_symbolic_device", err)
-        Zj = torch.empty(max(nnzZ, 1), dtype=torch.int32, device=Xp.device)
-        Zx = torch.empty(max(nnzZ, 1), dtype=Xx.dtype, device=Xp.device) if (values and Xx is not None) else None
-        pm = torch.empty(max(nnzZ, 1), dtype=torch.int32, device=Xp.device) if perm else None
-        torch.cuda.synchronize()
-        err = self.csr_extract_numeric_device(m, n, nnzX, Xx, Xp, Xj, mI, rows, nJ, cols, nnzZ, Zp, Zj, Zx, pm)
-        if err != BHSPARSE_SUCCESS:
-            raise BhsparseError("bhs_csr_extract_numeric_device", err)
-        return Zp, Zj[:nnzZ], (Zx[:nnzZ] if Zx is not None else None), (pm[:nnzZ] if pm is not None else None)
+        return self._symbolic_numeric(
+            "bhs_csr_extract", mI, Xp.device, Xx.dtype if (values and Xx is not None) else None, perm,
+            lambda Zp: self.csr_extract_symbolic_device(m, n, nnzX, Xp, Xj, mI, rows, nJ, cols, Zp),
+            lambda nnzZ, Zp, Zj, Zx, pm: self.csr_extract_numeric_device(m, n, nnzX, Xx, Xp, Xj, mI, rows, nJ, cols, nnzZ, Zp,
+                                                                         Zj, Zx, pm))
 
     # -- extension (not in the reference): reductions and the diagonal scaling (include/bhsparse_hip.h, "reduce / scale")
     def csr_reduce_raw_device(self, m, n, nnzX, d_valX, d_rowPtrX, d_colIndX, axis, op, flags, d_out):
         """bhs_csr_reduce_device on caller-given arrays: the status code; sets reduce_ms."""
         if self._h is None:
             return _lib.BHS_ERR_NOT_READY
-        ms = C.c_double(0)
-        err = self._lib.bhs_csr_reduce_device(self._h, int(m), int(n), int(nnzX), _ptr(d_valX), _ptr(d_rowPtrX), _ptr(d_colIndX),
-                                              int(axis), int(op), int(flags), _ptr(d_out), C.byref(ms))
-        if err == BHSPARSE_SUCCESS:
-            self.reduce_ms = float(ms.value)
-        return err
+        return self._timed(self._lib.bhs_csr_reduce_device, "reduce_ms", int(m), int(n), int(nnzX), _ptr(d_valX),
+                           _ptr(d_rowPtrX), _ptr(d_colIndX), int(axis), int(op), int(flags), _ptr(d_out))
 
     def csr_scale_raw_device(self, m, n, nnzX, d_valX, d_rowPtrX, d_colIndX, alpha, d_left, d_right, flags, d_valZ):
         """bhs_csr_scale_device on caller-given arrays: the status code; sets scale_ms."""
         if self._h is None:
             return _lib.BHS_ERR_NOT_READY
-        ms = C.c_double(0)
-        err = self._lib.bhs_csr_scale_device(self._h, int(m), int(n), int(nnzX), _ptr(d_valX), _ptr(d_rowPtrX), _ptr(d_colIndX),
-                                             float(alpha), _ptr(d_left), _ptr(d_right), int(flags), _ptr(d_valZ), C.byref(ms))
-        if err == BHSPARSE_SUCCESS:
-            self.scale_ms = float(ms.value)
-        return err
+        return self._timed(self._lib.bhs_csr_scale_device, "scale_ms", int(m), int(n), int(nnzX), _ptr(d_valX), _ptr(d_rowPtrX),
+                           _ptr(d_colIndX), float(alpha), _ptr(d_left), _ptr(d_right), int(flags), _ptr(d_valZ))
 
     def csr_reduce_device(self, m, n, X, axis, op, offdiag=False):
         """reduce(X) along `axis` (_lib.BHS_AXIS_*) with `op` (_lib.BHS_RED_*) on device arrays: X = (rowPtr, colInd, val)
@@ -481,11 +478,10 @@ class bhsparse(object):
         Xp, Xj, Xx = X
         count = {_lib.BHS_AXIS_ROWS: m, _lib.BHS_AXIS_COLS: n, _lib.BHS_AXIS_ALL: 1, _lib.BHS_AXIS_DIAG: min(m, n)}.get(axis, 1)
         tdt = torch.float32 if self._vdt == np.dtype(np.float32) else torch.float64
-        out = torch.empty(max(count, 1), dtype=tdt, device=Xp.device)
+        out = _alloc(count, tdt, Xp.device)
         torch.cuda.synchronize()
-        err = self.csr_reduce_raw_device(m, n, Xj.numel(), Xx, Xp, Xj, axis, op, _lib.BHS_RED_OFFDIAG if offdiag else 0, out)
-        if err != BHSPARSE_SUCCESS:
-            raise BhsparseError("bhs_csr_reduce_device", err)
+        _check(self.csr_reduce_raw_device(m, n, Xj.numel(), Xx, Xp, Xj, axis, op, _lib.BHS_RED_OFFDIAG if offdiag else 0, out),
+               "bhs_csr_reduce_device")
         return out[:count]
 
     def csr_scale_device(self, m, n, X, alpha=1.0, left=None, right=None, left_div=False, right_div=False, out=None):
@@ -495,12 +491,10 @@ class bhsparse(object):
         import torch
         Xp, Xj, Xx = X
         if out is None:
-            out = torch.empty(max(Xx.numel(), 1), dtype=Xx.dtype, device=Xx.device)[:Xx.numel()]
+            out = _alloc(Xx.numel(), Xx.dtype, Xx.device)[:Xx.numel()]
         torch.cuda.synchronize()
         flags = (_lib.BHS_SCALE_LEFT_DIV if left_div else 0) | (_lib.BHS_SCALE_RIGHT_DIV if right_div else 0)
-        err = self.csr_scale_raw_device(m, n, Xj.numel(), Xx, Xp, Xj, alpha, left, right, flags, out)
-        if err != BHSPARSE_SUCCESS:
-            raise BhsparseError("bhs_csr_scale_device", err)
+        _check(self.csr_scale_raw_device(m, n, Xj.numel(), Xx, Xp, Xj, alpha, left, right, flags, out), "bhs_csr_scale_device")
         return out
 
     # -- extension (not in the reference): the multiply over a semiring (include/bhsparse_hip.h, "semiring multiply")
@@ -511,54 +505,19 @@ class bhsparse(object):
         get_nnzC / get_C / get_rowptrC / get_C_device then return the semiring's values."""
         if self._h is None:
             return _lib.BHS_ERR_NOT_READY
-        import time
-        nnzCt, nnzC = C.c_int64(0), C.c_int(0)
-        ms = (C.c_double * 2)()
-        t0 = time.perf_counter()
-        err = self._lib.bhs_spgemm_semiring(self._h, int(semiring), _ptr(self._rowptrC), C.byref(nnzCt), C.byref(nnzC), ms)
-        self.time_ms = (time.perf_counter() - t0) * 1e3
-        if err == BHSPARSE_SUCCESS:
-            self.nnzCt, self.nnzC, self.semiring_ms = int(nnzCt.value), int(nnzC.value), float(ms[1])
-            self.multiply_ms = float(ms[0])
-        return err
+        return self._multiply(self._lib.bhs_spgemm_semiring, (int(semiring), _ptr(self._rowptrC)), "semiring_ms",
+                              ms0="multiply_ms", wall=True)
 
     def spgemm_semiring_masked(self, semiring, rowPtrM, colIndM, valC=None):
         """spgemm_masked over a semiring: valC[p] = the (+)-reduction of A(i,k) (x) B(k, colIndM[p]) for every entry p of row i
         of the pattern M, the (+)-identity where no product lands.  Returns valC (allocated when None); raises BhsparseError
         (an invalid M or an unknown semiring: code BHS_ERR_INVALID_ARG, valC untouched).  Sets nnzCt and semiring_ms."""
-        if self._h is None:
-            raise BhsparseError("bhs_spgemm_semiring_masked", _lib.BHS_ERR_NOT_READY)
-        rowPtrM = np.ascontiguousarray(rowPtrM, np.int32)
-        colIndM = np.ascontiguousarray(colIndM, np.int32)
-        if rowPtrM.size < self._m + 1:
-            raise BhsparseError("bhs_spgemm_semiring_masked", _lib.BHS_ERR_INVALID_ARG)
-        nnzM = colIndM.size
-        if valC is None:
-            valC = np.empty(nnzM, self._vdt)
-        elif not (isinstance(valC, np.ndarray) and valC.dtype == self._vdt and valC.size >= nnzM and valC.flags.c_contiguous):
-            raise BhsparseError("bhs_spgemm_semiring_masked", _lib.BHS_ERR_INVALID_ARG)
-        nnzCt, ms = C.c_int64(0), C.c_double(0)
-        err = self._lib.bhs_spgemm_semiring_masked(self._h, int(semiring), _ptr(rowPtrM), _ptr(colIndM) if nnzM else None, nnzM,
-                                                   _ptr(valC) if nnzM else None, C.byref(nnzCt), C.byref(ms))
-        if err != BHSPARSE_SUCCESS:
-            raise BhsparseError("bhs_spgemm_semiring_masked", err)
-        self.nnzCt, self.semiring_ms = int(nnzCt.value), float(ms.value)
-        return valC
+        return self._masked_host(int(semiring), rowPtrM, colIndM, valC)
 
     def spgemm_semiring_masked_device(self, semiring, d_rowPtrM, d_colIndM, nnzM, d_valC):
         """The same on device arrays (torch tensors on this handle's GPU, or raw device addresses); valC is written in
         place.  Returns the status code (0 on success) and sets nnzCt / semiring_ms."""
-        if self._h is None:
-            return _lib.BHS_ERR_NOT_READY
-        if any(hasattr(t, "is_cuda") and t.is_cuda for t in (d_rowPtrM, d_colIndM, d_valC)):
-            import torch
-            torch.cuda.synchronize()                       # the library works on its own stream (see initData_device)
-        nnzCt, ms = C.c_int64(0), C.c_double(0)
-        err = self._lib.bhs_spgemm_semiring_masked_device(self._h, int(semiring), _ptr(d_rowPtrM), _ptr(d_colIndM), int(nnzM),
-                                                          _ptr(d_valC), C.byref(nnzCt), C.byref(ms))
-        if err == BHSPARSE_SUCCESS:
-            self.nnzCt, self.semiring_ms = int(nnzCt.value), float(ms.value)
-        return err
+        return self._masked_device(int(semiring), d_rowPtrM, d_colIndM, nnzM, d_valC)
 
     def get_nnzC(self):
         if self._h is None:
@@ -630,9 +589,7 @@ class bhsparse(object):
         (ref_spgemm::csr_sort_indices, SpGEMM_cuda/ref_spgemm.h:37-62, on the GPU)."""
         if self._h is None:
             return _lib.BHS_ERR_NOT_READY
-        if any(hasattr(t, "is_cuda") and t.is_cuda for t in (d_rowPtr, d_colInd, d_val)):
-            import torch
-            torch.cuda.synchronize()                       # the library works on its own stream (see initData_device)
+        _sync(d_rowPtr, d_colInd, d_val)
         return self._lib.bhs_csr_sort_indices_device(self._h, n_row, _ptr(d_rowPtr), _ptr(d_colInd), _ptr(d_val))
 
     def get_rowptrC(self, out=None):
@@ -655,13 +612,7 @@ class bhsparse(object):
 
     def kernel_stats(self):
         arr = (_lib.KernelStat * 64)()
-        nrec = self._lib.bhs_get_kernel_stats(self._h, arr, 64)
-        out = []
-        for i in range(min(nrec, 64)):
-            s = arr[i]
-            out.append({"name": s.name.decode(), "launches": s.launches, "ms": s.ms, "rows": s.rows,
-                        "products": s.products, "nnz_out": s.nnz_out, "nnzA_rows": s.nnzA_rows})
-        return out
+        return self.decode_kernel_stats(arr, self.kernel_stats_raw(arr))
 
     def set_option(self, key, value):
         return self._lib.bhs_set_option(self._h, key.encode(), int(value))
@@ -689,111 +640,94 @@ class bhsparse(object):
         return err
 
 
-def spgemm_csr(m, k, n, Ap, Aj, Ax, Bp, Bj, Bx, device=0, warmups=0, options=None, value_dtype=np.float64):
-    """Convenience: run the reference call sequence once on host CSR arrays and
-    return (rowPtrC int32[m+1], colIndC int32[nnzC], valC value_dtype[nnzC], info)."""
+@contextlib.contextmanager
+def _handle(value_dtype, device, options):
+    """A handle on `device` with `options` set, for one `with` block; always destroyed.  free_mem() is left to the block's
+    success path (_free)."""
     plats = [False] * NUM_PLATFORMS
     plats[BHSPARSE_HIP] = True
     bh = bhsparse(value_dtype=value_dtype)
-    err = bh.initPlatform(plats, device=device)
-    if err:
-        raise BhsparseError("initPlatform", err)
+    _check(bh.initPlatform(plats, device=device), "initPlatform")
     try:
         for key, val in (options or {}).items():
-            err = bh.set_option(key, val)
-            if err:
-                raise BhsparseError("set_option(%s)" % key, err)
-        Ap, Aj, Ax = (np.ascontiguousarray(Ap, np.int32), np.ascontiguousarray(Aj, np.int32),
-                      np.ascontiguousarray(Ax, value_dtype))
-        Bp, Bj, Bx = (np.ascontiguousarray(Bp, np.int32), np.ascontiguousarray(Bj, np.int32),
-                      np.ascontiguousarray(Bx, value_dtype))
-        Cp = np.zeros(m + 1, np.int32)
-        err = bh.initData(m, k, n, len(Aj), Ax, Ap, Aj, len(Bj), Bx, Bp, Bj, Cp)
-        if err:
-            raise BhsparseError("initData", err)
-        for _ in range(warmups):
-            err = bh.warmup()
-            if err:
-                raise BhsparseError("warmup", err)
-        err = bh.spgemm()
-        if err:
-            raise BhsparseError("spgemm", err)
-        nnzC = bh.get_nnzC()
-        Cj = np.empty(nnzC, np.int32)
-        Cx = np.empty(nnzC, value_dtype)
-        err = bh.get_C(Cj, Cx)
-        if err:
-            raise BhsparseError("get_C", err)
-        info = {"nnzCt": bh.nnzCt, "nnzC": nnzC, "stage_ms": bh.stage_ms, "time_ms": bh.time_ms,
-                "kernels": bh.kernel_stats(), "mixed_rows": bh.get_info("mixed_rows"),
-                "class_state": bh.get_info("class_state")}
-        err = bh.free_mem()
-        if err:
-            raise BhsparseError("free_mem", err)
+            _check(bh.set_option(key, val), "set_option(%s)" % key)
+        yield bh
     finally:
         bh.freePlatform()
+
+
+def _bind(bh, m, k, n, Ap, Aj, Ax, Bp, Bj, Bx, Cp):
+    """initData on host CSR arrays of any integer / float type (converted here); Cp: int32[m+1] for rowPtrC, or None."""
+    Ap, Aj, Ax = np.ascontiguousarray(Ap, np.int32), np.ascontiguousarray(Aj, np.int32), np.ascontiguousarray(Ax, bh._vdt)
+    Bp, Bj, Bx = np.ascontiguousarray(Bp, np.int32), np.ascontiguousarray(Bj, np.int32), np.ascontiguousarray(Bx, bh._vdt)
+    _check(bh.initData(m, k, n, len(Aj), Ax, Ap, Aj, len(Bj), Bx, Bp, Bj, Cp), "initData")
+
+
+def _fetch(bh):
+    """(rowPtrC, colIndC, valC) of the last result as numpy arrays: the row pointer given to initData, or a new one."""
+    nnzC = bh.get_nnzC()
+    Cp = bh.get_rowptrC() if bh._rowptrC is None else bh._rowptrC
+    Cj = np.empty(nnzC, np.int32)
+    Cx = np.empty(nnzC, bh._vdt)
+    _check(bh.get_C(Cj, Cx), "get_C")
+    return Cp, Cj, Cx
+
+
+def _free(bh):
+    _check(bh.free_mem(), "free_mem")
+
+
+def _upload(a, dt, device):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a, dt).copy()).to(torch.device("cuda", device))
+
+
+def _device_csr(Xp, Xj, Xx, value_dtype, device):
+    """(rowPtr, colInd, val) as torch tensors on the device; val stays None."""
+    return (_upload(Xp, np.int32, device), _upload(Xj, np.int32, device),
+            None if Xx is None else _upload(Xx, value_dtype, device))
+
+
+def _host(*tensors):
+    return tuple(t.cpu().numpy() for t in tensors)
+
+
+def spgemm_csr(m, k, n, Ap, Aj, Ax, Bp, Bj, Bx, device=0, warmups=0, options=None, value_dtype=np.float64):
+    """Convenience: run the reference call sequence once on host CSR arrays and
+    return (rowPtrC int32[m+1], colIndC int32[nnzC], valC value_dtype[nnzC], info)."""
+    with _handle(value_dtype, device, options) as bh:
+        _bind(bh, m, k, n, Ap, Aj, Ax, Bp, Bj, Bx, np.zeros(m + 1, np.int32))
+        for _ in range(warmups):
+            _check(bh.warmup(), "warmup")
+        _check(bh.spgemm(), "spgemm")
+        Cp, Cj, Cx = _fetch(bh)
+        info = {"nnzCt": bh.nnzCt, "nnzC": len(Cj), "stage_ms": bh.stage_ms, "time_ms": bh.time_ms,
+                "kernels": bh.kernel_stats(), "mixed_rows": bh.get_info("mixed_rows"),
+                "class_state": bh.get_info("class_state")}
+        _free(bh)
     return Cp, Cj, Cx, info
 
 
 def spgemm_masked_csr(m, k, n, Ap, Aj, Ax, Bp, Bj, Bx, Mp, Mj, options=None, value_dtype=np.float64, device=0):
     """Convenience: the masked multiply once on host CSR arrays.  Returns (valC value_dtype[nnzM], info); the result's
     pattern is the caller's (Mp, Mj)."""
-    plats = [False] * NUM_PLATFORMS
-    plats[BHSPARSE_HIP] = True
-    bh = bhsparse(value_dtype=value_dtype)
-    err = bh.initPlatform(plats, device=device)
-    if err:
-        raise BhsparseError("initPlatform", err)
-    try:
-        for key, val in (options or {}).items():
-            err = bh.set_option(key, val)
-            if err:
-                raise BhsparseError("set_option(%s)" % key, err)
-        Ap, Aj, Ax = (np.ascontiguousarray(Ap, np.int32), np.ascontiguousarray(Aj, np.int32),
-                      np.ascontiguousarray(Ax, value_dtype))
-        Bp, Bj, Bx = (np.ascontiguousarray(Bp, np.int32), np.ascontiguousarray(Bj, np.int32),
-                      np.ascontiguousarray(Bx, value_dtype))
-        err = bh.initData(m, k, n, len(Aj), Ax, Ap, Aj, len(Bj), Bx, Bp, Bj, None)
-        if err:
-            raise BhsparseError("initData", err)
+    with _handle(value_dtype, device, options) as bh:
+        _bind(bh, m, k, n, Ap, Aj, Ax, Bp, Bj, Bx, None)
         valC = bh.spgemm_masked(Mp, Mj)
         info = {"nnzCt": bh.nnzCt, "ms": bh.masked_ms, "kernels": bh.kernel_stats()}
-        err = bh.free_mem()
-        if err:
-            raise BhsparseError("free_mem", err)
-    finally:
-        bh.freePlatform()
+        _free(bh)
     return valC, info
 
 
 def spgemm_semiring_csr(m, k, n, Ap, Aj, Ax, Bp, Bj, Bx, semiring, options=None, value_dtype=np.float64, device=0):
     """Convenience: C = A (+).(x) B once on host CSR arrays.  Returns (rowPtrC, colIndC, valC, info)."""
-    bh = _new_handle(value_dtype, device, options)
-    try:
-        Ap, Aj, Ax = (np.ascontiguousarray(Ap, np.int32), np.ascontiguousarray(Aj, np.int32),
-                      np.ascontiguousarray(Ax, value_dtype))
-        Bp, Bj, Bx = (np.ascontiguousarray(Bp, np.int32), np.ascontiguousarray(Bj, np.int32),
-                      np.ascontiguousarray(Bx, value_dtype))
-        Cp = np.zeros(m + 1, np.int32)
-        err = bh.initData(m, k, n, len(Aj), Ax, Ap, Aj, len(Bj), Bx, Bp, Bj, Cp)
-        if err:
-            raise BhsparseError("initData", err)
-        err = bh.spgemm_semiring(semiring)
-        if err:
-            raise BhsparseError("bhs_spgemm_semiring", err)
-        nnzC = bh.get_nnzC()
-        Cj = np.empty(nnzC, np.int32)
-        Cx = np.empty(nnzC, value_dtype)
-        err = bh.get_C(Cj, Cx)
-        if err:
-            raise BhsparseError("get_C", err)
-        info = {"nnzCt": bh.nnzCt, "nnzC": nnzC, "semiring_ms": bh.semiring_ms, "multiply_ms": bh.multiply_ms,
+    with _handle(value_dtype, device, options) as bh:
+        _bind(bh, m, k, n, Ap, Aj, Ax, Bp, Bj, Bx, np.zeros(m + 1, np.int32))
+        _check(bh.spgemm_semiring(semiring), "bhs_spgemm_semiring")
+        Cp, Cj, Cx = _fetch(bh)
+        info = {"nnzCt": bh.nnzCt, "nnzC": len(Cj), "semiring_ms": bh.semiring_ms, "multiply_ms": bh.multiply_ms,
                 "time_ms": bh.time_ms, "kernels": bh.kernel_stats(), "class_state": bh.get_info("class_state")}
-        err = bh.free_mem()
-        if err:
-            raise BhsparseError("free_mem", err)
-    finally:
-        bh.freePlatform()
+        _free(bh)
     return Cp, Cj, Cx, info
 
 
@@ -801,22 +735,11 @@ def spgemm_semiring_masked_csr(m, k, n, Ap, Aj, Ax, Bp, Bj, Bx, Mp, Mj, semiring
                                device=0):
     """Convenience: the masked multiply over a semiring once on host CSR arrays.  Returns (valC value_dtype[nnzM], info);
     the result's pattern is the caller's (Mp, Mj)."""
-    bh = _new_handle(value_dtype, device, options)
-    try:
-        Ap, Aj, Ax = (np.ascontiguousarray(Ap, np.int32), np.ascontiguousarray(Aj, np.int32),
-                      np.ascontiguousarray(Ax, value_dtype))
-        Bp, Bj, Bx = (np.ascontiguousarray(Bp, np.int32), np.ascontiguousarray(Bj, np.int32),
-                      np.ascontiguousarray(Bx, value_dtype))
-        err = bh.initData(m, k, n, len(Aj), Ax, Ap, Aj, len(Bj), Bx, Bp, Bj, None)
-        if err:
-            raise BhsparseError("initData", err)
+    with _handle(value_dtype, device, options) as bh:
+        _bind(bh, m, k, n, Ap, Aj, Ax, Bp, Bj, Bx, None)
         valC = bh.spgemm_semiring_masked(semiring, Mp, Mj)
         info = {"nnzCt": bh.nnzCt, "ms": bh.semiring_ms, "kernels": bh.kernel_stats()}
-        err = bh.free_mem()
-        if err:
-            raise BhsparseError("free_mem", err)
-    finally:
-        bh.freePlatform()
+        _free(bh)
     return valC, info
 
 
@@ -846,73 +769,30 @@ def select_spec(band=None, drop_diag=False, keep_diag=False, abs_tol=None, rel_t
     return s
 
 
-def _new_handle(value_dtype, device, options):
-    plats = [False] * NUM_PLATFORMS
-    plats[BHSPARSE_HIP] = True
-    bh = bhsparse(value_dtype=value_dtype)
-    err = bh.initPlatform(plats, device=device)
-    if err:
-        raise BhsparseError("initPlatform", err)
-    for key, val in (options or {}).items():
-        err = bh.set_option(key, val)
-        if err:
-            bh.freePlatform()
-            raise BhsparseError("set_option(%s)" % key, err)
-    return bh
-
-
 def csr_add(m, n, alpha, Xp, Xj, Xx, beta, Yp, Yj, Yx, value_dtype=np.float64, device=0):
     """Convenience: Z = alpha X + beta Y once on host CSR arrays (m x n, rows strictly ascending), staged as torch tensors
     on the handle's device -- the stand-alone add takes device arrays only.  Returns (Zp int32[m+1], Zj int32[nnzZ],
     Zx value_dtype[nnzZ], info) with info["kernels"], info["y_inside_x"], info["ms"].  Needs no multiply data."""
     import torch
-    dev = torch.device("cuda", device)
-    tdt = torch.float32 if np.dtype(value_dtype) == np.dtype(np.float32) else torch.float64
-
-    def up(a, dt):
-        return torch.from_numpy(np.ascontiguousarray(a, dt).copy()).to(dev)
-    X = (up(Xp, np.int32), up(Xj, np.int32), up(Xx, value_dtype))
-    Y = (up(Yp, np.int32), up(Yj, np.int32), up(Yx, value_dtype))
-    assert X[2].dtype == tdt
-    bh = _new_handle(value_dtype, device, None)
-    try:
+    X = _device_csr(Xp, Xj, Xx, value_dtype, device)
+    Y = _device_csr(Yp, Yj, Yx, value_dtype, device)
+    assert X[2].dtype == (torch.float32 if np.dtype(value_dtype) == np.dtype(np.float32) else torch.float64)
+    with _handle(value_dtype, device, None) as bh:
         Zp, Zj, Zx, inside = bh.csr_add_device(m, n, alpha, X, beta, Y)
         info = {"kernels": bh.kernel_stats(), "y_inside_x": inside, "ms": bh.add_ms}
-        out = (Zp.cpu().numpy(), Zj.cpu().numpy(), Zx.cpu().numpy(), info)
-    finally:
-        bh.freePlatform()
-    return out
+        return _host(Zp, Zj, Zx) + (info,)
 
 
 def spgemm_add_csr(m, k, n, Ap, Aj, Ax, Bp, Bj, Bx, Dp, Dj, Dx, alpha=1.0, beta=1.0, options=None, value_dtype=np.float64,
                    device=0):
     """Convenience: C = alpha A·B + beta D once on host CSR arrays.  Returns (rowPtrC, colIndC, valC, info)."""
-    bh = _new_handle(value_dtype, device, options)
-    try:
-        Ap, Aj, Ax = (np.ascontiguousarray(Ap, np.int32), np.ascontiguousarray(Aj, np.int32),
-                      np.ascontiguousarray(Ax, value_dtype))
-        Bp, Bj, Bx = (np.ascontiguousarray(Bp, np.int32), np.ascontiguousarray(Bj, np.int32),
-                      np.ascontiguousarray(Bx, value_dtype))
-        Cp = np.zeros(m + 1, np.int32)
-        err = bh.initData(m, k, n, len(Aj), Ax, Ap, Aj, len(Bj), Bx, Bp, Bj, Cp)
-        if err:
-            raise BhsparseError("initData", err)
-        err = bh.spgemm_add(alpha, beta, Dp, Dj, Dx)
-        if err:
-            raise BhsparseError("bhs_spgemm_add", err)
-        nnzC = bh.get_nnzC()
-        Cj = np.empty(nnzC, np.int32)
-        Cx = np.empty(nnzC, value_dtype)
-        err = bh.get_C(Cj, Cx)
-        if err:
-            raise BhsparseError("get_C", err)
-        info = {"nnzCt": bh.nnzCt, "nnzC": nnzC, "add_ms": bh.add_ms, "time_ms": bh.time_ms, "kernels": bh.kernel_stats(),
+    with _handle(value_dtype, device, options) as bh:
+        _bind(bh, m, k, n, Ap, Aj, Ax, Bp, Bj, Bx, np.zeros(m + 1, np.int32))
+        _check(bh.spgemm_add(alpha, beta, Dp, Dj, Dx), "bhs_spgemm_add")
+        Cp, Cj, Cx = _fetch(bh)
+        info = {"nnzCt": bh.nnzCt, "nnzC": len(Cj), "add_ms": bh.add_ms, "time_ms": bh.time_ms, "kernels": bh.kernel_stats(),
                 "add_inplace_used": bh.get_info("add_inplace_used"), "class_state": bh.get_info("class_state")}
-        err = bh.free_mem()
-        if err:
-            raise BhsparseError("free_mem", err)
-    finally:
-        bh.freePlatform()
+        _free(bh)
     return Cp, Cj, Cx, info
 
 
@@ -920,50 +800,21 @@ def csr_select(m, n, Xp, Xj, Xx, spec, value_dtype=np.float64, device=0):
     """Convenience: Z = select(X) once on host CSR arrays (m x n), staged as torch tensors on the handle's device -- the
     stand-alone selection takes device arrays only.  Returns (Zp int32[m+1], Zj int32[nnzZ], Zx value_dtype[nnzZ], info)
     with info["kernels"], info["ms"].  Needs no multiply data."""
-    import torch
-    dev = torch.device("cuda", device)
-
-    def up(a, dt):
-        return torch.from_numpy(np.ascontiguousarray(a, dt).copy()).to(dev)
-    X = (up(Xp, np.int32), up(Xj, np.int32), up(Xx, value_dtype))
-    bh = _new_handle(value_dtype, device, None)
-    try:
-        Zp, Zj, Zx = bh.csr_select_device(m, n, X, spec)
-        info = {"kernels": bh.kernel_stats(), "ms": bh.select_ms}
-        out = (Zp.cpu().numpy(), Zj.cpu().numpy(), Zx.cpu().numpy(), info)
-    finally:
-        bh.freePlatform()
-    return out
+    X = _device_csr(Xp, Xj, Xx, value_dtype, device)
+    with _handle(value_dtype, device, None) as bh:
+        Z = bh.csr_select_device(m, n, X, spec)
+        return _host(*Z) + ({"kernels": bh.kernel_stats(), "ms": bh.select_ms},)
 
 
 def spgemm_select_csr(m, k, n, Ap, Aj, Ax, Bp, Bj, Bx, spec, options=None, value_dtype=np.float64, device=0):
     """Convenience: C = select(A·B) once on host CSR arrays.  Returns (rowPtrC, colIndC, valC, info)."""
-    bh = _new_handle(value_dtype, device, options)
-    try:
-        Ap, Aj, Ax = (np.ascontiguousarray(Ap, np.int32), np.ascontiguousarray(Aj, np.int32),
-                      np.ascontiguousarray(Ax, value_dtype))
-        Bp, Bj, Bx = (np.ascontiguousarray(Bp, np.int32), np.ascontiguousarray(Bj, np.int32),
-                      np.ascontiguousarray(Bx, value_dtype))
-        Cp = np.zeros(m + 1, np.int32)
-        err = bh.initData(m, k, n, len(Aj), Ax, Ap, Aj, len(Bj), Bx, Bp, Bj, Cp)
-        if err:
-            raise BhsparseError("initData", err)
-        err = bh.spgemm_select(spec)
-        if err:
-            raise BhsparseError("bhs_spgemm_select", err)
-        nnzC = bh.get_nnzC()
-        Cj = np.empty(nnzC, np.int32)
-        Cx = np.empty(nnzC, value_dtype)
-        err = bh.get_C(Cj, Cx)
-        if err:
-            raise BhsparseError("get_C", err)
-        info = {"nnzCt": bh.nnzCt, "nnzC": nnzC, "select_ms": bh.select_ms, "time_ms": bh.time_ms, "kernels": bh.kernel_stats(),
+    with _handle(value_dtype, device, options) as bh:
+        _bind(bh, m, k, n, Ap, Aj, Ax, Bp, Bj, Bx, np.zeros(m + 1, np.int32))
+        _check(bh.spgemm_select(spec), "bhs_spgemm_select")
+        Cp, Cj, Cx = _fetch(bh)
+        info = {"nnzCt": bh.nnzCt, "nnzC": len(Cj), "select_ms": bh.select_ms, "time_ms": bh.time_ms, "kernels": bh.kernel_stats(),
                 "select_dropped": bh.get_info("select_dropped"), "class_state": bh.get_info("class_state")}
-        err = bh.free_mem()
-        if err:
-            raise BhsparseError("free_mem", err)
-    finally:
-        bh.freePlatform()
+        _free(bh)
     return Cp, Cj, Cx, info
 
 
@@ -972,20 +823,11 @@ def csr_transpose(m, n, Xp, Xj, Xx, value_dtype=np.float64, device=0):
     tensors on the handle's device -- the transpose takes device arrays only.  Returns (Tp int32[n+1], Tj int32[nnz],
     Tx value_dtype[nnz], info) with info["kernels"], info["ms"], info["perm"] (int32[nnz]: the position in X of every entry
     of T).  Needs no multiply data."""
-    import torch
-    dev = torch.device("cuda", device)
-
-    def up(a, dt):
-        return torch.from_numpy(np.ascontiguousarray(a, dt).copy()).to(dev)
-    X = (up(Xp, np.int32), up(Xj, np.int32), up(Xx, value_dtype))
-    bh = _new_handle(value_dtype, device, None)
-    try:
+    X = _device_csr(Xp, Xj, Xx, value_dtype, device)
+    with _handle(value_dtype, device, None) as bh:
         Tp, Tj, Tx, pm = bh.csr_transpose_device(m, n, X, values=True, perm=True)
         info = {"kernels": bh.kernel_stats(), "ms": bh.transpose_ms, "perm": pm.cpu().numpy()}
-        out = (Tp.cpu().numpy(), Tj.cpu().numpy(), Tx.cpu().numpy(), info)
-    finally:
-        bh.freePlatform()
-    return out
+        return _host(Tp, Tj, Tx) + (info,)
 
 
 def extract_csr(m, n, Xp, Xj, Xx, rows=None, cols=None, value_dtype=np.float64, device=0):
@@ -994,23 +836,14 @@ def extract_csr(m, n, Xp, Xj, Xx, rows=None, cols=None, value_dtype=np.float64, 
     device arrays only.  Returns (Zp int32[mI+1], Zj int32[nnzZ], Zx value_dtype[nnzZ], info) with info["kernels"],
     info["ms"], info["reordered_rows"], info["perm"] (int32[nnzZ]: the position in X of every entry of Z).  Needs no
     multiply data."""
-    import torch
-    dev = torch.device("cuda", device)
-
-    def up(a, dt):
-        return torch.from_numpy(np.ascontiguousarray(a, dt).copy()).to(dev)
-    X = (up(Xp, np.int32), up(Xj, np.int32), up(Xx, value_dtype))
-    r = None if rows is None else up(rows, np.int32)
-    c = None if cols is None else up(cols, np.int32)
-    bh = _new_handle(value_dtype, device, None)
-    try:
+    X = _device_csr(Xp, Xj, Xx, value_dtype, device)
+    r = None if rows is None else _upload(rows, np.int32, device)
+    c = None if cols is None else _upload(cols, np.int32, device)
+    with _handle(value_dtype, device, None) as bh:
         Zp, Zj, Zx, pm = bh.csr_extract_device(m, n, X, rows=r, cols=c, values=True, perm=True)
         info = {"kernels": bh.kernel_stats(), "ms": bh.extract_ms, "reordered_rows": bh.get_info("extract_reordered_rows"),
                 "perm": pm.cpu().numpy()}
-        out = (Zp.cpu().numpy(), Zj.cpu().numpy(), Zx.cpu().numpy(), info)
-    finally:
-        bh.freePlatform()
-    return out
+        return _host(Zp, Zj, Zx) + (info,)
 
 
 def permute_csr(n, Xp, Xj, Xx, p, value_dtype=np.float64, device=0):
@@ -1018,27 +851,14 @@ def permute_csr(n, Xp, Xj, Xx, p, value_dtype=np.float64, device=0):
     return extract_csr(n, n, Xp, Xj, Xx, rows=p, cols=p, value_dtype=value_dtype, device=device)
 
 
-def _device_csr(Xp, Xj, Xx, value_dtype, device):
-    import torch
-    dev = torch.device("cuda", device)
-
-    def up(a, dt):
-        return torch.from_numpy(np.ascontiguousarray(a, dt).copy()).to(dev)
-    return up(Xp, np.int32), up(Xj, np.int32), (None if Xx is None else up(Xx, value_dtype)), up
-
-
 def reduce_csr(m, n, Xp, Xj, Xx, axis, op, offdiag=False, value_dtype=np.float64, device=0):
     """Convenience: reduce(X) once on host CSR arrays (X is m x n; Xx may be None: every entry counts as 1), staged as
     torch tensors on the handle's device.  axis: _lib.BHS_AXIS_*, op: _lib.BHS_RED_*.  Returns (out value_dtype[...],
     info) with info["kernels"], info["ms"].  Needs no multiply data."""
-    dXp, dXj, dXx, _ = _device_csr(Xp, Xj, Xx, value_dtype, device)
-    bh = _new_handle(value_dtype, device, None)
-    try:
-        out = bh.csr_reduce_device(m, n, (dXp, dXj, dXx), axis, op, offdiag=offdiag)
-        res = (out.cpu().numpy(), {"kernels": bh.kernel_stats(), "ms": bh.reduce_ms})
-    finally:
-        bh.freePlatform()
-    return res
+    X = _device_csr(Xp, Xj, Xx, value_dtype, device)
+    with _handle(value_dtype, device, None) as bh:
+        out = bh.csr_reduce_device(m, n, X, axis, op, offdiag=offdiag)
+        return out.cpu().numpy(), {"kernels": bh.kernel_stats(), "ms": bh.reduce_ms}
 
 
 def diagonal_csr(m, n, Xp, Xj, Xx, value_dtype=np.float64, device=0):
@@ -1050,16 +870,12 @@ def scale_csr(m, n, Xp, Xj, Xx, alpha=1.0, left=None, right=None, left_div=False
               device=0):
     """Convenience: the values of Z = alpha diag(left) X diag(right) once on host CSR arrays (Z has X's pattern).  Returns
     (Zx value_dtype[nnzX], info) with info["kernels"], info["ms"]."""
-    dXp, dXj, dXx, up = _device_csr(Xp, Xj, Xx, value_dtype, device)
-    l = None if left is None else up(left, value_dtype)
-    r = None if right is None else up(right, value_dtype)
-    bh = _new_handle(value_dtype, device, None)
-    try:
-        Zx = bh.csr_scale_device(m, n, (dXp, dXj, dXx), alpha, l, r, left_div, right_div)
-        res = (Zx.cpu().numpy(), {"kernels": bh.kernel_stats(), "ms": bh.scale_ms})
-    finally:
-        bh.freePlatform()
-    return res
+    X = _device_csr(Xp, Xj, Xx, value_dtype, device)
+    l = None if left is None else _upload(left, value_dtype, device)
+    r = None if right is None else _upload(right, value_dtype, device)
+    with _handle(value_dtype, device, None) as bh:
+        Zx = bh.csr_scale_device(m, n, X, alpha, l, r, left_div, right_div)
+        return Zx.cpu().numpy(), {"kernels": bh.kernel_stats(), "ms": bh.scale_ms}
 
 
 def normalize_csr(m, n, Xp, Xj, Xx, axis, norm=1, value_dtype=np.float64, device=0):
@@ -1069,20 +885,16 @@ def normalize_csr(m, n, Xp, Xj, Xx, axis, norm=1, value_dtype=np.float64, device
     import torch
     if axis not in (_lib.BHS_AXIS_ROWS, _lib.BHS_AXIS_COLS) or norm not in (1, 2, "inf"):
         raise ValueError("axis is BHS_AXIS_ROWS or BHS_AXIS_COLS, norm 1, 2 or \"inf\"")
-    dXp, dXj, dXx, _ = _device_csr(Xp, Xj, Xx, value_dtype, device)
+    X = _device_csr(Xp, Xj, Xx, value_dtype, device)
     op = {1: _lib.BHS_RED_ABS_PLUS, "inf": _lib.BHS_RED_ABS_MAX, 2: _lib.BHS_RED_SQ_PLUS}[norm]
-    bh = _new_handle(value_dtype, device, None)
-    try:
-        nrm = bh.csr_reduce_device(m, n, (dXp, dXj, dXx), axis, op)
+    with _handle(value_dtype, device, None) as bh:
+        nrm = bh.csr_reduce_device(m, n, X, axis, op)
         if norm == 2:
             nrm = torch.sqrt(nrm)
         div = torch.where(nrm == 0, torch.ones_like(nrm), nrm)
         rows = axis == _lib.BHS_AXIS_ROWS
-        Zx = bh.csr_scale_device(m, n, (dXp, dXj, dXx), 1.0, div if rows else None, None if rows else div, rows, not rows)
-        res = (Zx.cpu().numpy(), nrm.cpu().numpy())
-    finally:
-        bh.freePlatform()
-    return res
+        Zx = bh.csr_scale_device(m, n, X, 1.0, div if rows else None, None if rows else div, rows, not rows)
+        return _host(Zx, nrm)
 
 
 def smoothed_prolongator_csr(n, nc, Ap, Aj, Ax, Tp, Tj, Tx, omega, options=None, value_dtype=np.float64, device=0):
@@ -1091,31 +903,18 @@ def smoothed_prolongator_csr(n, nc, Ap, Aj, Ax, Tp, Tj, Tx, omega, options=None,
     get_C: diag(A) (bhs_csr_reduce_device), -omega D^-1 A (bhs_csr_scale_device with LEFT_DIV), then the multiply with T
     plus T (bhs_spgemm_add, alpha = beta = 1).  Returns (Pp int32[n+1], Pj, Px, info); info: "nnzCt", "nnzC",
     "reduce_ms", "scale_ms", "add_ms", "kernels"."""
-    dAp, dAj, dAx, up = _device_csr(Ap, Aj, Ax, value_dtype, device)
-    T = (up(Tp, np.int32), up(Tj, np.int32), up(Tx, value_dtype))
-    bh = _new_handle(value_dtype, device, options)
-    try:
-        d = bh.csr_reduce_device(n, n, (dAp, dAj, dAx), _lib.BHS_AXIS_DIAG, _lib.BHS_RED_PLUS)
-        Sx = bh.csr_scale_device(n, n, (dAp, dAj, dAx), -float(omega), left=d, left_div=True)
-        nnzA, nnzT = dAj.numel(), T[1].numel()
-        err = bh.initData_device(n, n, nc, nnzA, Sx, dAp, dAj, nnzT, T[2], T[0], T[1])
-        if err:
-            raise BhsparseError("initData_device(-omega D^-1 A, T)", err)
-        err = bh.spgemm_add_device(1.0, 1.0, nnzT, T[2], T[0], T[1])
-        if err:
-            raise BhsparseError("bhs_spgemm_add_device", err)
-        nnzC = bh.get_nnzC()
-        Pp = bh.get_rowptrC()
-        Pj = np.empty(nnzC, np.int32)
-        Px = np.empty(nnzC, value_dtype)
-        err = bh.get_C(Pj, Px)
-        if err:
-            raise BhsparseError("get_C", err)
-        info = {"nnzCt": bh.nnzCt, "nnzC": nnzC, "reduce_ms": bh.reduce_ms, "scale_ms": bh.scale_ms, "add_ms": bh.add_ms,
+    A = _device_csr(Ap, Aj, Ax, value_dtype, device)
+    T = _device_csr(Tp, Tj, Tx, value_dtype, device)
+    with _handle(value_dtype, device, options) as bh:
+        d = bh.csr_reduce_device(n, n, A, _lib.BHS_AXIS_DIAG, _lib.BHS_RED_PLUS)
+        Sx = bh.csr_scale_device(n, n, A, -float(omega), left=d, left_div=True)
+        nnzA, nnzT = A[1].numel(), T[1].numel()
+        _check(bh.initData_device(n, n, nc, nnzA, Sx, A[0], A[1], nnzT, T[2], T[0], T[1]), "initData_device(-omega D^-1 A, T)")
+        _check(bh.spgemm_add_device(1.0, 1.0, nnzT, T[2], T[0], T[1]), "bhs_spgemm_add_device")
+        Pp, Pj, Px = _fetch(bh)
+        info = {"nnzCt": bh.nnzCt, "nnzC": len(Pj), "reduce_ms": bh.reduce_ms, "scale_ms": bh.scale_ms, "add_ms": bh.add_ms,
                 "kernels": bh.kernel_stats()}
         bh.free_mem()
-    finally:
-        bh.freePlatform()
     return Pp, Pj, Px, info
 
 
@@ -1125,49 +924,23 @@ def galerkin_csr(m, nc, Pp, Pj, Px, Ap, Aj, Ax, options=None, value_dtype=np.flo
     second one multiplies P^T with the first one's device-resident result (bhs_get_C_device).  Public calls only.
     Returns (Cp int32[nc+1], Cj, Cx, info); info: "nnzCt_AP", "nnzCt" (products of the two multiplies), "nnzC_AP", "nnzC",
     "transpose_ms", "ap_ms", "ptap_ms" (device times), "class_state_AP", "class_state", "kernels_AP", "kernels"."""
-    import torch
-    dev = torch.device("cuda", device)
-
-    def up(a, dt):
-        return torch.from_numpy(np.ascontiguousarray(a, dt).copy()).to(dev)
-    P = (up(Pp, np.int32), up(Pj, np.int32), up(Px, value_dtype))
-    A = (up(Ap, np.int32), up(Aj, np.int32), up(Ax, value_dtype))
+    P = _device_csr(Pp, Pj, Px, value_dtype, device)
+    A = _device_csr(Ap, Aj, Ax, value_dtype, device)
     nnzP, nnzA = P[1].numel(), A[1].numel()
-    h1 = _new_handle(value_dtype, device, options)
-    h2 = None
-    try:
-        h2 = _new_handle(value_dtype, device, options)
+    with _handle(value_dtype, device, options) as h1, _handle(value_dtype, device, options) as h2:
         Tp, Tj, Tx, _ = h2.csr_transpose_device(m, nc, P)
         info = {"transpose_ms": h2.transpose_ms}
-        err = h1.initData_device(m, m, nc, nnzA, A[2], A[0], A[1], nnzP, P[2], P[0], P[1])
-        if err:
-            raise BhsparseError("initData_device(A, P)", err)
-        err = h1.spgemm()
-        if err:
-            raise BhsparseError("spgemm(A·P)", err)
+        _check(h1.initData_device(m, m, nc, nnzA, A[2], A[0], A[1], nnzP, P[2], P[0], P[1]), "initData_device(A, P)")
+        _check(h1.spgemm(), "spgemm(A·P)")
         nnzAP = h1.get_nnzC()
         dAPp, dAPj, dAPx = h1.get_C_device()
         info.update({"nnzCt_AP": h1.nnzCt, "nnzC_AP": nnzAP, "ap_ms": float(sum(h1.stage_ms)), "kernels_AP": h1.kernel_stats(),
                      "class_state_AP": h1.get_info("class_state")})
-        err = h2.initData_device(nc, m, nc, nnzP, Tx, Tp, Tj, nnzAP, dAPx, dAPp, dAPj)
-        if err:
-            raise BhsparseError("initData_device(P^T, A·P)", err)
-        err = h2.spgemm()
-        if err:
-            raise BhsparseError("spgemm(P^T·AP)", err)
-        nnzC = h2.get_nnzC()
-        Cp = h2.get_rowptrC()
-        Cj = np.empty(nnzC, np.int32)
-        Cx = np.empty(nnzC, value_dtype)
-        err = h2.get_C(Cj, Cx)
-        if err:
-            raise BhsparseError("get_C", err)
-        info.update({"nnzCt": h2.nnzCt, "nnzC": nnzC, "ptap_ms": float(sum(h2.stage_ms)), "kernels": h2.kernel_stats(),
+        _check(h2.initData_device(nc, m, nc, nnzP, Tx, Tp, Tj, nnzAP, dAPx, dAPp, dAPj), "initData_device(P^T, A·P)")
+        _check(h2.spgemm(), "spgemm(P^T·AP)")
+        Cp, Cj, Cx = _fetch(h2)
+        info.update({"nnzCt": h2.nnzCt, "nnzC": len(Cj), "ptap_ms": float(sum(h2.stage_ms)), "kernels": h2.kernel_stats(),
                      "class_state": h2.get_info("class_state")})
         h2.free_mem()
         h1.free_mem()
-    finally:
-        if h2 is not None:
-            h2.freePlatform()
-        h1.freePlatform()
     return Cp, Cj, Cx, info

@@ -113,3 +113,42 @@ def test_measurement_tools_still_build(tmp_path):
             assert rc == 0, (src, err)
     for f in sorted(glob.glob(os.path.join(tools, "*.py"))):
         py_compile.compile(f, cfile=str(tmp_path / (os.path.basename(f) + "c")), doraise=True)
+
+
+def test_every_included_file_is_a_listed_source(monkeypatch):
+    """_lib.SOURCES (what build() checks for staleness and source_digest() hashes) names every file the translation unit
+    can include: quoted includes are followed through csrc/ whatever #if they sit under; the Makefile's prerequisite list is
+    the same list.  The public header, which lives outside csrc/, is among build()'s staleness inputs too; the only other include that leaves csrc/ is the lab build's copy
+    of the ring kernel under tools/lab/, which is no source of the product."""
+    assert isinstance(_lib.SOURCES, tuple) and _lib.SOURCES[0] == "bhsparse_hip.hip"
+    assert list(_lib.SOURCES[1:]) == sorted(_lib.SOURCES[1:]) and len(set(_lib.SOURCES)) == len(_lib.SOURCES)
+    seen, todo, outside = set(), ["bhsparse_hip.hip"], set()
+    while todo:
+        f = todo.pop()
+        if f in seen:
+            continue
+        seen.add(f)
+        for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', open(os.path.join(_lib.CSRC, f)).read(), re.M):
+            if "/" in inc:
+                outside.add(inc)
+            else:
+                todo.append(inc)                   # a missing file fails the open() above
+    assert len(seen) > 30 and "bhs_host_side.inc.h" in seen
+    assert sorted(seen - set(_lib.SOURCES)) == []
+    assert outside == {"../../include/bhsparse_hip.h", "../../tools/lab/bhs_class_ring_lab.hip.h"}
+    assert os.path.samefile(os.path.join(_lib.CSRC, "../../include/bhsparse_hip.h"), _lib.HEADER)
+    # the Makefile's prerequisites are the same list: both libraries depend on $(HDRS), which names every header of csrc/
+    mk = open(os.path.join(_lib.CSRC, "Makefile")).read()
+    hdrs = re.search(r"^HDRS\s*:?=((?:.*\\\n)*.*)$", mk, re.M).group(1).replace("\\\n", " ").split()
+    assert tuple(hdrs) == _lib.SOURCES[1:]
+    for lib in ("libbhsparse_hip.so", "libbhsparse_hip_f32.so"):
+        assert re.search(r"^%s: bhsparse_hip\.hip \$\(HDRS\) \.\./\.\./include/bhsparse_hip\.h$" % re.escape(lib), mk, re.M)
+    # build() looks at the modification time of every input it weighs against the libraries: record which
+    asked = []
+    real = os.path.getmtime
+    monkeypatch.setattr(_lib.os.path, "getmtime", lambda p: asked.append(os.path.abspath(p)) or real(p))
+    monkeypatch.setattr(_lib.subprocess, "check_call", lambda *a, **k: 0)
+    _lib.build()
+    assert os.path.abspath(_lib.HEADER) in asked
+    for f in seen:
+        assert os.path.join(_lib.CSRC, f) in asked
