@@ -102,6 +102,9 @@ SYMBOLS = {
                                             C.POINTER(C.c_double)]),
     "bhs_csr_reduce_device": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _vp, C.POINTER(C.c_double)]),
     "bhs_csr_scale_device": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, C.c_double, _vp, _vp, _i, _vp, C.POINTER(C.c_double)]),
+    "bhs_csr_spmv_device": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, C.c_double, _vp, C.c_double, _vp, C.POINTER(C.c_double)]),
+    "bhs_csr_spmm_device": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _i, C.c_double, _vp, C.c_longlong, C.c_double, _vp, C.c_longlong,
+                                 C.POINTER(C.c_double)]),
     "bhs_strerror": (C.c_char_p, [_i]),
     "bhs_version": (C.c_char_p, []),
 }

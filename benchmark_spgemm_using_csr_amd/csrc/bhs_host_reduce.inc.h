@@ -173,14 +173,6 @@ int sc_run(bhs_handle* h, const ScArgs& s, double* ms_out)
     return h->rdWs.host[RD_ERR] ? (int)BHS_ERR_INVALID_ARG : (int)BHS_SUCCESS;
 }
 
-// do [a, a + na) and [b, b + nb) share a byte
-bool rd_overlap(const void* a, size_t na, const void* b, size_t nb)
-{
-    if (!a || !b || !na || !nb) return false;
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a0 < b0 + nb && b0 < a0 + na;
-}
-
 }  // namespace
 
 extern "C" {

@@ -121,6 +121,14 @@ int side_scan(bhs_handle* h, SideWs& ws, const char* name, const SideScanWords& 
     return BHS_SUCCESS;
 }
 
+// do [a, a + na) and [b, b + nb) share a byte (an output array against an input: the reductions, the scaling, CSR x dense)
+bool rd_overlap(const void* a, size_t na, const void* b, size_t nb)
+{
+    if (!a || !b || !na || !nb) return false;
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a0 < b0 + nb && b0 < a0 + na;
+}
+
 // after a failed call: nothing of it stays queued (the pipeline's own state is not touched)
 void settle(bhs_handle* h)
 {

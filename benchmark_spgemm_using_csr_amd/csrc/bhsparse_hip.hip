@@ -1,8 +1,8 @@
 // bhsparse_hip.hip — libbhsparse_hip.so (see include/bhsparse_hip.h): the handle and its helpers here; the launch helpers,
 // the pipeline, the hand-over of a data set and the C-ABI in bhs_host_{launch,pipeline,setdata,cabi}.inc.h, the masked multiply
-// the sparse add, the entry selection, the transpose, the reductions and the scaling, the semiring multiply and the extraction in
-// bhs_host_{masked,add,select,transpose,reduce,semiring,extract}.inc.h on the shared plumbing of bhs_host_side.inc.h (one
-// translation unit).
+// the sparse add, the entry selection, the transpose, the reductions and the scaling, the semiring multiply, the extraction and
+// CSR x dense in bhs_host_{masked,add,select,spmv,transpose,reduce,semiring,extract}.inc.h on the shared plumbing of
+// bhs_host_side.inc.h (one translation unit).
 //
 // Pipeline of one bhs_spgemm() (replaces bhsparse::spgemm_cuda, bhsparse.h:297-339):
 //   stage 1  k_upper_bound (ub per row, nnzCt, symbolic-bin histogram)          <- compute_nnzCt + statistics()
@@ -391,6 +391,8 @@ struct bhs_handle {
     // the reductions and the scaling (bhs_host_reduce.inc.h): the queues of the rows beyond the short bin (2 x m ints), no counts
     SideWs rdWs;
     DevBuf rdAcc, rdPart;                // the accumulators, 8 bytes an output; the partials of a total
+    // CSR x dense (bhs_host_spmv.inc.h): the queues of the rows beyond the short bin (2 x m ints), no counts
+    SideWs mvWs;
 };
 
 namespace {
@@ -554,6 +556,7 @@ inline int one_launch(int rc) { return rc != BHS_SUCCESS ? rc : 1; }
 #include "bhs_host_masked.inc.h"
 #include "bhs_host_add.inc.h"
 #include "bhs_host_select.inc.h"
+#include "bhs_host_spmv.inc.h"
 #include "bhs_host_transpose.inc.h"
 #include "bhs_host_reduce.inc.h"
 #include "bhs_host_semiring.inc.h"

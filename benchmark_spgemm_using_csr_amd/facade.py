@@ -91,6 +91,7 @@ class bhsparse(object):
         self.extract_ms = 0.0
         self.reduce_ms = 0.0
         self.scale_ms = 0.0
+        self.spmv_ms = 0.0
         self.semiring_ms = 0.0
         self.multiply_ms = 0.0
         self.quiet = True

@@ -85,6 +85,16 @@ public:
                          const index_type *d_colIndX, double alpha, const value_type *d_left, const value_type *d_right,
                          int flags, value_type *d_valZ);
 
+    // EXTENSION, not part of the reference's API: CSR x dense (bhs_csr_spmv_device, bhs_csr_spmm_device,
+    // include/bhsparse_hip.h, "CSR x dense") on DEVICE arrays: y = alpha A x + beta y and Y = alpha A X + beta Y; A is m x n
+    // (d_valA may be 0: every entry counts as 1), X n x k and Y m x k row-major with leading dimensions ldX, ldY >= k.  Needs
+    // initPlatform only; does not disturb the data of initData or get_C's result.
+    int csr_spmv_device(int m, int n, int nnzA, const value_type *d_valA, const index_type *d_rowPtrA,
+                        const index_type *d_colIndA, double alpha, const value_type *d_x, double beta, value_type *d_y);
+    int csr_spmm_device(int m, int n, int nnzA, const value_type *d_valA, const index_type *d_rowPtrA,
+                        const index_type *d_colIndA, int k, double alpha, const value_type *d_X, long long ldX, double beta,
+                        value_type *d_Y, long long ldY);
+
     // EXTENSION, not part of the reference's API: the multiply over a semiring (bhs_spgemm_semiring*, include/bhsparse_hip.h,
     // "semiring multiply"; semiring: a BHS_SR_* constant) on the data of initData.  spgemm_semiring is the full product: it
     // fills the csrRowPtrC of initData, and get_nnzC / get_C then return A (+).(x) B on the pattern of A·B.
@@ -229,6 +239,22 @@ inline int bhsparse::csr_scale_device(int m, int n, int nnzX, const value_type *
 {
     if (!_h) return BHS_ERR_NOT_READY;
     return bhs_csr_scale_device(_h, m, n, nnzX, d_valX, d_rowPtrX, d_colIndX, alpha, d_left, d_right, flags, d_valZ, 0);
+}
+
+inline int bhsparse::csr_spmv_device(int m, int n, int nnzA, const value_type *d_valA, const index_type *d_rowPtrA,
+                                     const index_type *d_colIndA, double alpha, const value_type *d_x, double beta,
+                                     value_type *d_y)
+{
+    if (!_h) return BHS_ERR_NOT_READY;
+    return bhs_csr_spmv_device(_h, m, n, nnzA, d_valA, d_rowPtrA, d_colIndA, alpha, d_x, beta, d_y, 0);
+}
+
+inline int bhsparse::csr_spmm_device(int m, int n, int nnzA, const value_type *d_valA, const index_type *d_rowPtrA,
+                                     const index_type *d_colIndA, int k, double alpha, const value_type *d_X, long long ldX,
+                                     double beta, value_type *d_Y, long long ldY)
+{
+    if (!_h) return BHS_ERR_NOT_READY;
+    return bhs_csr_spmm_device(_h, m, n, nnzA, d_valA, d_rowPtrA, d_colIndA, k, alpha, d_X, ldX, beta, d_Y, ldY, 0);
 }
 
 inline int bhsparse::get_nnzC()

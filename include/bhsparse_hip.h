@@ -561,6 +561,51 @@ BHS_API int bhs_csr_scale_device(bhs_handle *h, int m, int n, int nnzX,
         const bhs_value_t *d_right /* n values or NULL */, int flags,
         bhs_value_t *d_valZ /* nnzX; may equal d_valX */, double *ms_out /* may be NULL */);
 
+/* ---- CSR x dense ----------------------------------------------------------
+ * A CSR matrix applied to a dense vector or to k dense vectors at once: y = alpha A x + beta y (the residual b - A x, a
+ * smoother sweep, P^T r and P e of a multigrid cycle, a power-iteration step) and Y = alpha A X + beta Y; no reference
+ * counterpart; bhs_spmv.hip.h.  Plus-times only; for A^T transpose first (bhs_csr_transpose_device).
+ * A: m x n, 0-based int32 CSR; rows need NOT be ascending, duplicate (row, column) pairs are legal and add up (as for
+ * the reductions).  m, n and nnzA may be 0.  d_valA may be NULL: every entry then counts as the value 1.
+ * X is n x k, Y is m x k, both row-major with leading dimensions ldX, ldY >= k: element (i, c) sits at i * ld + c,
+ * indexed in 64 bits.  bhs_csr_spmv_device is the k = 1, ld = 1 case of the same code.
+ * Both calls are synchronous on the handle's stream, need no bound data (they work on a handle straight after
+ * bhs_create), return BHS_ERR_INVALID_ARG between bhs_spgemm_symbolic and bhs_spgemm_finish, and leave the handle as it
+ * was: counters, queues (2 m ints), events and the pinned mirror are buffers of their own from the grow-only pool; C of
+ * the last multiply (whose device arrays from bhs_get_C_device may be passed straight in as A), a served sum or
+ * selection, "class_state", the speculative-launch figures and every option stay.  ms_out (may be NULL): device time of
+ * the call, validation included.
+ * Arithmetic (worded as for the reductions): every product is double(a) * double(x); the products of a row are summed in
+ *   double from +0 to s; t = alpha * s; if beta != 0, t = t + beta * double(y_old); ONE rounding to bhs_value_t.
+ *   beta == 0 never reads d_y: it may hold NaN or be uninitialised.  alpha == 0 takes no shortcut: Inf and NaN in A or x
+ *   propagate by IEEE.  FMA contraction is allowed; the sign of a zero result is not specified.
+ * Reproducibility: the order of every sum is a function of the input arrays and the build alone -- two calls on the same
+ *   arrays give the same bits.  No atomics on an output, no accumulation across workgroups.
+ * Validation: on the device.  rowPtrA[0] != 0, a decreasing rowPtrA, rowPtrA[m] != nnzA, or a column outside [0, n)
+ *   return BHS_ERR_INVALID_ARG.  The check comes before the dependent read: a refused row pointer is never used to
+ *   address colIndA or valA, a refused column never to address x.  y is an in/out array, so a refused call may leave y
+ *   partly written (as bhs_csr_scale_device in place).  Nothing is ever written outside the m x k elements of Y: not in
+ *   the gaps c in [k, ldY) of a row, not past row m - 1.  X's gap columns are never read.
+ *   On the host: a NULL handle, negative sizes, k < 1, ldX < k, ldY < k, a NULL d_rowPtrA, a NULL d_colIndA or d_x with
+ *   nnzA > 0, a NULL d_y with m > 0, or d_y's footprint ((m - 1) ldY + k values) overlapping an input return
+ *   BHS_ERR_INVALID_ARG with d_y untouched.
+ * Rows are binned by length as the reductions bin them; bhs_get_kernel_stats then reports the families spmv_short (every
+ *   row in order: the row pointer's check, the rows of up to 32 entries, 16 lanes each), spmv_wave (up to 1024 entries, a
+ *   wave each), spmv_long (a workgroup each) for k = 1 and spmm_short, spmm_wave, spmm_long for k >= 2.  One round trip
+ *   for the queues' lengths, and only when nnzA > 32.  For k >= 2 the lanes of a row lie along the columns of X first
+ *   (tiles of 2, 4, .. 64 columns; a wider k loops over tiles of 64): one entry's gather is one contiguous read of X's
+ *   row, and the entry is read once per tile.  Compulsory traffic: 12 bytes an entry (8 without values), 4 (m + 1), and
+ *   the dense arrays.                                                                                                  */
+BHS_API int bhs_csr_spmv_device(bhs_handle *h, int m, int n, int nnzA,
+        const bhs_value_t *d_valA /* may be NULL: every entry counts as 1 */,
+        const int *d_rowPtrA, const int *d_colIndA,
+        double alpha, const bhs_value_t *d_x /* n */,
+        double beta, bhs_value_t *d_y /* m, in/out */, double *ms_out /* may be NULL */);
+BHS_API int bhs_csr_spmm_device(bhs_handle *h, int m, int n, int nnzA,
+        const bhs_value_t *d_valA /* may be NULL */, const int *d_rowPtrA, const int *d_colIndA,
+        int k, double alpha, const bhs_value_t *d_X /* n x k */, long long ldX /* >= k */,
+        double beta, bhs_value_t *d_Y /* m x k, in/out */, long long ldY /* >= k */, double *ms_out /* may be NULL */);
+
 /* replaces bhsparse::get_nnzC (bhsparse.h: get_nnzC -> bhsparse_cuda::get_nnzC). */
 BHS_API int bhs_get_nnzC(bhs_handle *h, int *nnzC_out);
 
