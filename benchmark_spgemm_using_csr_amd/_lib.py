@@ -52,6 +52,9 @@ BHS_AXIS_ROWS, BHS_AXIS_COLS, BHS_AXIS_ALL, BHS_AXIS_DIAG = range(4)
 BHS_RED_OFFDIAG = 1
 BHS_SCALE_LEFT_DIV, BHS_SCALE_RIGHT_DIV = 1, 2
 
+# bhs_csr_spmv_semiring_device / bhs_csr_spmm_semiring_device (include/bhsparse_hip.h, "semiring CSR x dense")
+BHS_MV_ACCUM, BHS_MV_MASK_COMPLEMENT = 1, 2
+
 
 # every symbol include/bhsparse_hip.h declares: (restype, argtypes)
 _vp, _i, _i64 = C.c_void_p, C.c_int, C.c_int64
@@ -105,6 +108,10 @@ SYMBOLS = {
     "bhs_csr_spmv_device": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, C.c_double, _vp, C.c_double, _vp, C.POINTER(C.c_double)]),
     "bhs_csr_spmm_device": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _i, C.c_double, _vp, C.c_longlong, C.c_double, _vp, C.c_longlong,
                                  C.POINTER(C.c_double)]),
+    "bhs_csr_spmv_semiring_device": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, C.POINTER(C.c_longlong),
+                                          C.POINTER(C.c_double)]),
+    "bhs_csr_spmm_semiring_device": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, C.c_longlong, _i, _vp, C.c_longlong, _vp,
+                                          C.c_longlong, C.POINTER(C.c_longlong), C.POINTER(C.c_double)]),
     "bhs_strerror": (C.c_char_p, [_i]),
     "bhs_version": (C.c_char_p, []),
 }

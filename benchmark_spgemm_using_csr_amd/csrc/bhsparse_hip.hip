@@ -1,7 +1,7 @@
 // bhsparse_hip.hip — libbhsparse_hip.so (see include/bhsparse_hip.h): the handle and its helpers here; the launch helpers,
 // the pipeline, the hand-over of a data set and the C-ABI in bhs_host_{launch,pipeline,setdata,cabi}.inc.h, the masked multiply
 // the sparse add, the entry selection, the transpose, the reductions and the scaling, the semiring multiply, the extraction and
-// CSR x dense in bhs_host_{masked,add,select,spmv,transpose,reduce,semiring,extract}.inc.h on the shared plumbing of
+// CSR x dense in bhs_host_{masked,add,select,spmv,spmv_sr,transpose,reduce,semiring,extract}.inc.h on the shared plumbing of
 // bhs_host_side.inc.h (one translation unit).
 //
 // Pipeline of one bhs_spgemm() (replaces bhsparse::spgemm_cuda, bhsparse.h:297-339):
@@ -393,6 +393,8 @@ struct bhs_handle {
     DevBuf rdAcc, rdPart;                // the accumulators, 8 bytes an output; the partials of a total
     // CSR x dense (bhs_host_spmv.inc.h): the queues of the rows beyond the short bin (2 x m ints), no counts
     SideWs mvWs;
+    // semiring CSR x dense (bhs_host_spmv_sr.inc.h): the same queues; its control block also holds the 64-bit count of changed elements
+    SideWs srmvWs;
 };
 
 namespace {
@@ -557,6 +559,7 @@ inline int one_launch(int rc) { return rc != BHS_SUCCESS ? rc : 1; }
 #include "bhs_host_add.inc.h"
 #include "bhs_host_select.inc.h"
 #include "bhs_host_spmv.inc.h"
+#include "bhs_host_spmv_sr.inc.h"
 #include "bhs_host_transpose.inc.h"
 #include "bhs_host_reduce.inc.h"
 #include "bhs_host_semiring.inc.h"

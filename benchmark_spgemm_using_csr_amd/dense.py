@@ -1,10 +1,13 @@
 """CSR x dense through a facade handle: y = alpha A x + beta y and Y = alpha A X + beta Y (bhs_csr_spmv_device,
-bhs_csr_spmm_device; include/bhsparse_hip.h, "CSR x dense").
+bhs_csr_spmm_device; include/bhsparse_hip.h, "CSR x dense"), and the same over a semiring with an output mask and
+accumulation, Y<M> (+)= A (+).(x) X (bhs_csr_spmv_semiring_device, bhs_csr_spmm_semiring_device; "semiring CSR x dense").
 
 Functions of a `facade.bhsparse` handle, not methods of it: the raw calls on caller-given arrays (torch tensors on the
 handle's GPU or raw device addresses), the same on torch tensors with the output made here, and conveniences on host CSR
 arrays that stage everything on the device for one call.  Every call is a thin one into the C-ABI; a missing library
 raises, nothing is computed on the host."""
+import ctypes as C
+
 import numpy as np
 
 from . import _lib
@@ -88,3 +91,93 @@ def spmv_csr(m, n, Ap, Aj, Ax, x, alpha=1.0, beta=0.0, y=None, value_dtype=np.fl
 def residual_csr(m, n, Ap, Aj, Ax, x, b, value_dtype=np.float64, device=0):
     """Convenience: the residual b - A x (alpha = -1, beta = 1 on a copy of b).  Returns (r value_dtype[m], info)."""
     return spmv_csr(m, n, Ap, Aj, Ax, x, alpha=-1.0, beta=1.0, y=b, value_dtype=value_dtype, device=device)
+
+
+# ---------------------------------------------------------------- over a semiring, with mask and accumulate
+def _semiring(semiring):
+    """a BHS_SR_* constant from a name of _lib.SEMIRINGS or from the constant itself"""
+    return _lib.SEMIRINGS[semiring] if isinstance(semiring, str) else int(semiring)
+
+
+def semiring_identity(semiring):
+    """the (+)-identity of a semiring (include/bhsparse_hip.h, "semiring multiply"): what a row without entries gives"""
+    inf = float("inf")
+    return (0.0, inf, -inf, -inf, inf, -inf, 0.0, 0.0)[_semiring(semiring)]
+
+
+def _flags(accumulate, complement):
+    return (_lib.BHS_MV_ACCUM if accumulate else 0) | (_lib.BHS_MV_MASK_COMPLEMENT if complement else 0)
+
+
+def _semiring_call(bh, fn, *args):
+    """fn(handle, *args, changed, ms): the status code; sets bh.spmv_ms and bh.spmv_changed on success"""
+    changed, ms = C.c_longlong(0), C.c_double(0)
+    err = fn(bh._h, *args, C.byref(changed), C.byref(ms))
+    if err == _lib.BHS_SUCCESS:
+        bh.spmv_ms = float(ms.value)
+        bh.spmv_changed = int(changed.value)
+    return err
+
+
+def csr_spmv_semiring_raw_device(bh, semiring, m, n, nnzA, d_valA, d_rowPtrA, d_colIndA, d_x, flags, d_mask, d_y):
+    """bhs_csr_spmv_semiring_device on caller-given arrays (d_valA may be None: every entry counts as 1; d_mask may be None:
+    everything is selected; flags: BHS_MV_ACCUM | BHS_MV_MASK_COMPLEMENT): the status code; sets bh.spmv_ms and
+    bh.spmv_changed."""
+    if bh._h is None:
+        return _lib.BHS_ERR_NOT_READY
+    return _semiring_call(bh, bh._lib.bhs_csr_spmv_semiring_device, _semiring(semiring), int(m), int(n), int(nnzA), _ptr(d_valA),
+                          _ptr(d_rowPtrA), _ptr(d_colIndA), _ptr(d_x), int(flags), _ptr(d_mask), _ptr(d_y))
+
+
+def csr_spmm_semiring_raw_device(bh, semiring, m, n, nnzA, d_valA, d_rowPtrA, d_colIndA, k, d_X, ldX, flags, d_M, ldM, d_Y, ldY):
+    """bhs_csr_spmm_semiring_device on caller-given arrays (X: n x k, M and Y: m x k, row-major with leading dimensions ldX,
+    ldM, ldY): the status code; sets bh.spmv_ms and bh.spmv_changed."""
+    if bh._h is None:
+        return _lib.BHS_ERR_NOT_READY
+    return _semiring_call(bh, bh._lib.bhs_csr_spmm_semiring_device, _semiring(semiring), int(m), int(n), int(nnzA), _ptr(d_valA),
+                          _ptr(d_rowPtrA), _ptr(d_colIndA), int(k), _ptr(d_X), int(ldX), int(flags), _ptr(d_M), int(ldM),
+                          _ptr(d_Y), int(ldY))
+
+
+def csr_spmm_semiring_device(bh, semiring, m, n, A, X, Y=None, mask=None, accumulate=False, complement=False):
+    """Y<mask> (+)= A (+).(x) X on device arrays: A = (rowPtr, colInd, val or None) torch tensors on the handle's GPU; X
+    (n x k), mask (m x k or None) and Y (m x k) torch tensors there whose rows are contiguous (stride(0) is the leading
+    dimension); 1-D tensors are taken as k = 1.  semiring: a name of _lib.SEMIRINGS or a BHS_SR_* constant.  Without
+    `accumulate` Y is never read; a Y made here (None) is filled with nothing, so the elements the mask does not select
+    hold whatever the allocation held.  Returns (Y, changed) -- Y in the shape of X's kind (1-D for a 1-D X); raises
+    BhsparseError on failure."""
+    import torch
+    Ap, Aj, Ax = A
+    flat = X.dim() == 1
+    as2d = lambda T: T if T is None or T.dim() != 1 else T.unsqueeze(1)   # noqa: E731
+    X2, M2, Y2 = as2d(X), as2d(mask), as2d(Y)
+    k = X2.shape[1] if X2.dim() == 2 else 0
+    if Y2 is None and k:
+        Y2 = _alloc(m * k, X.dtype, X.device)[:m * k].view(m, k)
+    for name, T, rows in (("X", X2, n), ("mask", M2, m), ("Y", Y2, m)):
+        if name == "mask" and T is None:
+            continue
+        if not k or T.dim() != 2 or tuple(T.shape) != (rows, k) or (k > 1 and T.stride(1) != 1):
+            raise ValueError("%s is a row-major %d x k tensor, k >= 1" % (name, rows))
+    ld = lambda T: max(int(T.stride(0)), k) if T.shape[0] > 1 else k   # noqa: E731  (one row or none: any ld will do)
+    torch.cuda.synchronize()                           # the library works on its own stream (see facade.initData_device)
+    _check(csr_spmm_semiring_raw_device(bh, semiring, m, n, Aj.numel(), Ax, Ap, Aj, k, X2, ld(X2), _flags(accumulate, complement),
+                                        M2, ld(M2) if M2 is not None else k, Y2, ld(Y2)), "bhs_csr_spmm_semiring_device")
+    out = Y if Y is not None else (Y2[:, 0] if flat else Y2)
+    return out, bh.spmv_changed
+
+
+def spmm_semiring_csr(semiring, m, n, Ap, Aj, Ax, X, Y=None, mask=None, accumulate=False, complement=False,
+                      value_dtype=np.float64, device=0):
+    """Convenience: Y<mask> (+)= A (+).(x) X once on host arrays (A: m x n CSR, Ax may be None; X: n x k or n values; mask
+    and Y: m x k or None -- a Y of None starts from the (+)-identity), staged as torch tensors on the handle's device.
+    Returns (Y value_dtype[m, k], info) with info["kernels"], info["ms"], info["changed"].  Needs no multiply data."""
+    A = _device_csr(Ap, Aj, Ax, value_dtype, device)
+    dX = _upload(np.asarray(X).reshape(n, -1), value_dtype, device)
+    k = dX.shape[1]
+    Y0 = np.full((m, k), semiring_identity(semiring)) if Y is None else np.asarray(Y).reshape(m, k)
+    dY = _upload(Y0, value_dtype, device)
+    dM = None if mask is None else _upload(np.asarray(mask).reshape(m, k), value_dtype, device)
+    with _handle(value_dtype, device, None) as bh:
+        out, changed = csr_spmm_semiring_device(bh, semiring, m, n, A, dX, dY, dM, accumulate, complement)
+        return out.cpu().numpy(), {"kernels": bh.kernel_stats(), "ms": bh.spmv_ms, "changed": changed}

@@ -92,6 +92,7 @@ class bhsparse(object):
         self.reduce_ms = 0.0
         self.scale_ms = 0.0
         self.spmv_ms = 0.0
+        self.spmv_changed = 0
         self.semiring_ms = 0.0
         self.multiply_ms = 0.0
         self.quiet = True

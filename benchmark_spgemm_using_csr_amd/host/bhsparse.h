@@ -95,6 +95,19 @@ public:
                         const index_type *d_colIndA, int k, double alpha, const value_type *d_X, long long ldX, double beta,
                         value_type *d_Y, long long ldY);
 
+    // EXTENSION, not part of the reference's API: semiring CSR x dense with an output mask and accumulation
+    // (bhs_csr_spmv_semiring_device, bhs_csr_spmm_semiring_device, include/bhsparse_hip.h, "semiring CSR x dense") on DEVICE
+    // arrays: Y<M> (+)= A (+).(x) X; semiring: a BHS_SR_* constant, flags: BHS_MV_ACCUM | BHS_MV_MASK_COMPLEMENT, d_mask /
+    // d_M may be 0 (everything is selected), changed_out may be 0.  One step of a BFS (OR_AND under the complement of the
+    // visited set) or of Bellman-Ford (MIN_PLUS with BHS_MV_ACCUM); an entry A(i, j) is an edge j -> i.  Needs initPlatform
+    // only; does not disturb the data of initData or get_C's result.
+    int csr_spmv_semiring_device(int semiring, int m, int n, int nnzA, const value_type *d_valA, const index_type *d_rowPtrA,
+                                 const index_type *d_colIndA, const value_type *d_x, int flags, const value_type *d_mask,
+                                 value_type *d_y, long long *changed_out);
+    int csr_spmm_semiring_device(int semiring, int m, int n, int nnzA, const value_type *d_valA, const index_type *d_rowPtrA,
+                                 const index_type *d_colIndA, int k, const value_type *d_X, long long ldX, int flags,
+                                 const value_type *d_M, long long ldM, value_type *d_Y, long long ldY, long long *changed_out);
+
     // EXTENSION, not part of the reference's API: the multiply over a semiring (bhs_spgemm_semiring*, include/bhsparse_hip.h,
     // "semiring multiply"; semiring: a BHS_SR_* constant) on the data of initData.  spgemm_semiring is the full product: it
     // fills the csrRowPtrC of initData, and get_nnzC / get_C then return A (+).(x) B on the pattern of A·B.
@@ -255,6 +268,25 @@ inline int bhsparse::csr_spmm_device(int m, int n, int nnzA, const value_type *d
 {
     if (!_h) return BHS_ERR_NOT_READY;
     return bhs_csr_spmm_device(_h, m, n, nnzA, d_valA, d_rowPtrA, d_colIndA, k, alpha, d_X, ldX, beta, d_Y, ldY, 0);
+}
+
+inline int bhsparse::csr_spmv_semiring_device(int semiring, int m, int n, int nnzA, const value_type *d_valA,
+                                              const index_type *d_rowPtrA, const index_type *d_colIndA, const value_type *d_x,
+                                              int flags, const value_type *d_mask, value_type *d_y, long long *changed_out)
+{
+    if (!_h) return BHS_ERR_NOT_READY;
+    return bhs_csr_spmv_semiring_device(_h, semiring, m, n, nnzA, d_valA, d_rowPtrA, d_colIndA, d_x, flags, d_mask, d_y,
+                                        changed_out, 0);
+}
+
+inline int bhsparse::csr_spmm_semiring_device(int semiring, int m, int n, int nnzA, const value_type *d_valA,
+                                              const index_type *d_rowPtrA, const index_type *d_colIndA, int k,
+                                              const value_type *d_X, long long ldX, int flags, const value_type *d_M,
+                                              long long ldM, value_type *d_Y, long long ldY, long long *changed_out)
+{
+    if (!_h) return BHS_ERR_NOT_READY;
+    return bhs_csr_spmm_semiring_device(_h, semiring, m, n, nnzA, d_valA, d_rowPtrA, d_colIndA, k, d_X, ldX, flags, d_M, ldM,
+                                        d_Y, ldY, changed_out, 0);
 }
 
 inline int bhsparse::get_nnzC()

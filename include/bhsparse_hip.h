@@ -606,6 +606,68 @@ BHS_API int bhs_csr_spmm_device(bhs_handle *h, int m, int n, int nnzA,
         int k, double alpha, const bhs_value_t *d_X /* n x k */, long long ldX /* >= k */,
         double beta, bhs_value_t *d_Y /* m x k, in/out */, long long ldY /* >= k */, double *ms_out /* may be NULL */);
 
+/* ---- semiring CSR x dense -------------------------------------------------
+ * One step of a graph traversal with every array on the device: y<mask> (+)= A (+).(x) x and, for k vectors (k sources)
+ * at once, Y<M> (+)= A (+).(x) X over the eight semirings of "semiring multiply" (GraphBLAS mxv / mxm with a dense
+ * operand; no reference counterpart; bhs_spmv_sr.hip.h): a Bellman-Ford relaxation (MIN_PLUS with BHS_MV_ACCUM), a
+ * pull-direction BFS frontier (OR_AND under the complement of the visited set), bottleneck paths (MAX_MIN, MIN_MAX).
+ * Row i pulls from its columns: an entry A(i, j) is an edge j -> i.
+ * A, X, Y: as "CSR x dense" -- A is m x n, 0-based int32 CSR, rows need NOT be ascending, duplicate (row, column) pairs are
+ *   legal and every one of them is an entry; m, n and nnzA may be 0; d_valA may be NULL: every entry then counts as the
+ *   value 1.  X is n x k, M and Y are m x k, row-major with leading dimensions ldX, ldM, ldY >= k, indexed in 64 bits; the
+ *   gaps c in [k, ld) are never read and never written.  bhs_csr_spmv_semiring_device is the k = 1, ld = 1 case of the
+ *   same code.
+ * The rule.  For element (i, c), t = (+) over the entries e of row i of a_e (x) X(col_e, c): product, reduction and
+ *   identity from the table of "semiring multiply", for all eight BHS_SR_*.  Every element of X counts as an entry (a
+ *   dense operand has no pattern); a row without entries gives the (+)-identity.  BHS_SR_PLUS_PAIR reads neither valA nor
+ *   X and gives the number of entries of the row, duplicates counted (its columns are read and checked).  Order of min and
+ *   max, -0 below +0, NaN propagation, OR_AND's notion of non-zero: word for word those of "semiring multiply".
+ *   Arithmetic in double, ONE rounding to bhs_value_t per element.
+ * Accumulate.  Without BHS_MV_ACCUM, Y(i,c) = round(t) and y_old is never read: it may be NaN or uninitialised.  With it,
+ *   Y(i,c) = round(double(y_old) (+) t): min for the MIN_ semirings, max for MAX_, or for OR_AND (y_old != 0 counts as
+ *   1), + for PLUS_.  A NaN y_old gives NaN for min and max.
+ * Mask.  Element (i, c) of M is SET where its value is non-zero: NaN is set, -0 and +0 are not.  With
+ *   BHS_MV_MASK_COMPLEMENT an element is selected where it is NOT set; a NULL mask selects everything; COMPLEMENT with a
+ *   NULL mask is refused.  An element the mask does not select is neither read nor written, with or without ACCUM.  A row
+ *   none of whose k elements is selected is not walked at all -- its columns and values are not read --, which is what
+ *   makes a pull-direction BFS cheaper as the visited set grows.  Columns are therefore checked where they are read.
+ * changed_out (may be NULL): the number of selected elements whose stored value differs, as a number, from what it was
+ *   accumulated into: y_old with ACCUM ("has the relaxation converged"), the (+)-identity without ("how large is the next
+ *   frontier").  +0 equals -0; NaN over NaN counts as unchanged, NaN against a number as changed.  The count is an exact
+ *   integer: summed per workgroup, added once per workgroup to a 64-bit control word and read in the round trip the call
+ *   makes anyway for its error word -- y is never copied to the host.  Integer adds commute: the same count from run to
+ *   run.  Written on success only.  With a NULL changed_out the count is not taken at all (the kernels skip it).
+ * Reproducibility: min, max, or and pair are bit-for-bit functions of the input.  The PLUS_TIMES sum has the guarantee of
+ *   "CSR x dense": its order is a function of the input arrays and the build alone.  No atomics touch Y, nothing
+ *   accumulates across workgroups into Y.  PLUS_TIMES runs the kernels of this section like the others (with a mask it
+ *   could not forward to bhs_csr_spmm_device, and one path is easier to reason about than two).
+ * Validation: on the device, as "CSR x dense": rowPtrA[0] != 0, a decreasing rowPtrA, rowPtrA[m] != nnzA, or a column
+ *   outside [0, n) in a row that is read return BHS_ERR_INVALID_ARG.  The row pointer is checked in every row, selected
+ *   or not; the check comes before the dependent read.  Y is an in/out array, so a call refused on the device may leave Y
+ *   partly written (never outside its selected m x k elements).
+ *   On the host, each BHS_ERR_INVALID_ARG with Y untouched: the list of "CSR x dense" (a NULL handle, negative sizes,
+ *   k < 1, ldX < k, ldY < k, a NULL d_rowPtrA, a NULL d_colIndA or d_X with nnzA > 0, a NULL d_Y with m > 0), an unknown
+ *   semiring, an unknown flag bit, ldM < k with a mask, COMPLEMENT without a mask, or Y's footprint overlapping A, X or M
+ *   (M may overlap X: the levels of a BFS are mask and never operand, but nothing forbids it).
+ * Both calls are synchronous on the handle's stream, need no bound data, return BHS_ERR_INVALID_ARG between
+ *   bhs_spgemm_symbolic and bhs_spgemm_finish, and leave the handle as it was: C of the last multiply, a served sum or
+ *   selection, "class_state", the speculative-launch figures and every option stay (the workspace is a buffer set of its
+ *   own).  ms_out (may be NULL): device time of the call, validation included.
+ * bhs_get_kernel_stats then reports srmv_short, srmv_wave, srmv_long -- the same three for every k: the bins of "CSR x
+ *   dense" (up to 32 entries, up to 1024, beyond), one round trip for the queues' lengths and only when nnzA > 32; a row
+ *   beyond the short bin is queued only where one of its k elements is selected.                                        */
+enum { BHS_MV_ACCUM = 1, BHS_MV_MASK_COMPLEMENT = 2 };
+BHS_API int bhs_csr_spmv_semiring_device(bhs_handle *h, int semiring, int m, int n, int nnzA,
+        const bhs_value_t *d_valA /* may be NULL: ones */, const int *d_rowPtrA, const int *d_colIndA,
+        const bhs_value_t *d_x /* n */, int flags, const bhs_value_t *d_mask /* m, or NULL */,
+        bhs_value_t *d_y /* m, in/out */, long long *changed_out /* may be NULL */, double *ms_out /* may be NULL */);
+BHS_API int bhs_csr_spmm_semiring_device(bhs_handle *h, int semiring, int m, int n, int nnzA,
+        const bhs_value_t *d_valA /* may be NULL */, const int *d_rowPtrA, const int *d_colIndA,
+        int k, const bhs_value_t *d_X /* n x k */, long long ldX /* >= k */, int flags,
+        const bhs_value_t *d_M /* m x k, or NULL */, long long ldM /* >= k with a mask */,
+        bhs_value_t *d_Y /* m x k, in/out */, long long ldY /* >= k */, long long *changed_out /* may be NULL */,
+        double *ms_out /* may be NULL */);
+
 /* replaces bhsparse::get_nnzC (bhsparse.h: get_nnzC -> bhsparse_cuda::get_nnzC). */
 BHS_API int bhs_get_nnzC(bhs_handle *h, int *nnzC_out);
 
