@@ -395,6 +395,10 @@ struct bhs_handle {
     SideWs mvWs;
     // semiring CSR x dense (bhs_host_spmv_sr.inc.h): the same queues; its control block also holds the 64-bit count of changed elements
     SideWs srmvWs;
+    // sparse frontier x CSR (bhs_host_push_sr.inc.h): the row map and the changed elements' bits in its queue buffer, the
+    // frontier's degrees and then the row map's counts in its count buffer
+    SideWs pushWs;
+    DevBuf pushOff;                      // the scanned counts: the frontier's offsets, then the places in d_next
 };
 
 namespace {
@@ -560,6 +564,7 @@ inline int one_launch(int rc) { return rc != BHS_SUCCESS ? rc : 1; }
 #include "bhs_host_select.inc.h"
 #include "bhs_host_spmv.inc.h"
 #include "bhs_host_spmv_sr.inc.h"
+#include "bhs_host_push_sr.inc.h"
 #include "bhs_host_transpose.inc.h"
 #include "bhs_host_reduce.inc.h"
 #include "bhs_host_semiring.inc.h"

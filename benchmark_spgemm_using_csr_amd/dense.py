@@ -1,6 +1,7 @@
 """CSR x dense through a facade handle: y = alpha A x + beta y and Y = alpha A X + beta Y (bhs_csr_spmv_device,
 bhs_csr_spmm_device; include/bhsparse_hip.h, "CSR x dense"), and the same over a semiring with an output mask and
-accumulation, Y<M> (+)= A (+).(x) X (bhs_csr_spmv_semiring_device, bhs_csr_spmm_semiring_device; "semiring CSR x dense").
+accumulation, Y<M> (+)= A (+).(x) X (bhs_csr_spmv_semiring_device, bhs_csr_spmm_semiring_device; "semiring CSR x dense"),
+and in the push direction from a list of rows (bhs_csr_push_semiring_device; "sparse frontier x CSR").
 
 Functions of a `facade.bhsparse` handle, not methods of it: the raw calls on caller-given arrays (torch tensors on the
 handle's GPU or raw device addresses), the same on torch tensors with the output made here, and conveniences on host CSR
@@ -165,6 +166,56 @@ def csr_spmm_semiring_device(bh, semiring, m, n, A, X, Y=None, mask=None, accumu
                                         M2, ld(M2) if M2 is not None else k, Y2, ld(Y2)), "bhs_csr_spmm_semiring_device")
     out = Y if Y is not None else (Y2[:, 0] if flat else Y2)
     return out, bh.spmv_changed
+
+
+# ---------------------------------------------------------------- the push direction: a sparse frontier
+def csr_push_semiring_raw_device(bh, semiring, m, n, nnzG, d_valG, d_rowPtrG, d_colIndG, nf, d_fidx, k, d_F, ldF, flags, d_M, ldM,
+                                 d_Y, ldY, d_next, want_changed=True):
+    """bhs_csr_push_semiring_device on caller-given arrays, the C arguments in order (d_valG, d_M and d_next may be None;
+    flags: BHS_MV_MASK_COMPLEMENT or 0): the status code; sets bh.spmv_ms, bh.spmv_changed and bh.push_next (the length of
+    the list in d_next) on success.  want_changed False passes a NULL changed_out (bh.spmv_changed is then 0)."""
+    if bh._h is None:
+        return _lib.BHS_ERR_NOT_READY
+    changed, count, ms = C.c_longlong(0), C.c_int(0), C.c_double(0)
+    err = bh._lib.bhs_csr_push_semiring_device(bh._h, _semiring(semiring), int(m), int(n), int(nnzG), _ptr(d_valG), _ptr(d_rowPtrG),
+                                               _ptr(d_colIndG), int(nf), _ptr(d_fidx), int(k), _ptr(d_F), int(ldF), int(flags),
+                                               _ptr(d_M), int(ldM), _ptr(d_Y), int(ldY), _ptr(d_next), C.byref(count),
+                                               C.byref(changed) if want_changed else None, C.byref(ms))
+    if err == _lib.BHS_SUCCESS:
+        bh.spmv_ms = float(ms.value)
+        bh.spmv_changed = int(changed.value)
+        bh.push_next = int(count.value)
+    return err
+
+
+def csr_push_semiring_device(bh, semiring, m, n, G, fidx, F, Y, mask=None, complement=False, want_list=True):
+    """Y<mask> (+)= F (+).(x) G(fidx, :) on device arrays, the push direction: G = (rowPtr, colInd, val or None), the m x n
+    CSR of OUT-edges (row j lists the vertices j pushes to: the transpose of the pull calls' A) as torch tensors on the
+    handle's GPU; fidx an int32 tensor of nf rows of G; F (nf x k), mask (n x k or None) and Y (n x k, updated in place: the
+    call always accumulates) tensors there whose rows are contiguous (stride(0) is the leading dimension); 1-D tensors are
+    taken as k = 1.  semiring: any but plus_times.  Returns (Y, changed, next_idx): the number of elements of Y that
+    changed, and the rows of Y that hold one -- ascending, an int32 view (of the count's length) of a buffer made here; None
+    without want_list.  Raises BhsparseError on failure."""
+    import torch
+    Gp, Gj, Gx = G
+    as2d = lambda T: T if T is None or T.dim() != 1 else T.unsqueeze(1)   # noqa: E731
+    F2, M2, Y2 = as2d(F), as2d(mask), as2d(Y)
+    nf = int(fidx.numel())
+    k = Y2.shape[1] if Y2.dim() == 2 else 0
+    for name, T, rows in (("F", F2, nf), ("mask", M2, n), ("Y", Y2, n)):
+        if name == "mask" and T is None:
+            continue
+        if not k or T.dim() != 2 or tuple(T.shape) != (rows, k) or (k > 1 and T.stride(1) != 1):
+            raise ValueError("%s is a row-major %d x k tensor, k >= 1" % (name, rows))
+    if fidx.dtype != torch.int32 or fidx.dim() != 1 or not fidx.is_contiguous():
+        raise ValueError("fidx is a contiguous int32 vector")
+    ld = lambda T: max(int(T.stride(0)), k) if T.shape[0] > 1 else k   # noqa: E731  (one row or none: any ld will do)
+    nxt = torch.empty(max(n, 1), dtype=torch.int32, device=Y.device) if want_list else None
+    torch.cuda.synchronize()                           # the library works on its own stream (see facade.initData_device)
+    _check(csr_push_semiring_raw_device(bh, semiring, m, n, Gj.numel(), Gx, Gp, Gj, nf, fidx, k, F2, ld(F2),
+                                        _flags(False, complement), M2, ld(M2) if M2 is not None else k, Y2, ld(Y2), nxt),
+           "bhs_csr_push_semiring_device")
+    return Y, bh.spmv_changed, (nxt[:bh.push_next] if want_list else None)
 
 
 def spmm_semiring_csr(semiring, m, n, Ap, Aj, Ax, X, Y=None, mask=None, accumulate=False, complement=False,

@@ -93,6 +93,7 @@ class bhsparse(object):
         self.scale_ms = 0.0
         self.spmv_ms = 0.0
         self.spmv_changed = 0
+        self.push_next = 0
         self.semiring_ms = 0.0
         self.multiply_ms = 0.0
         self.quiet = True

@@ -4,11 +4,16 @@ a step is one call of the library, and what ends the loop is the call's count of
 
 Functions of a `facade.bhsparse` handle, as in dense.py.  The direction: row i pulls from its columns, so an entry A(i, j)
 is an edge j -> i (of weight A(i, j)).  A symmetric matrix is an undirected graph; for a matrix of out-edge lists --
-A(i, j) an edge i -> j -- transpose first (facade.csr_transpose, bhsparse.csr_transpose_device)."""
+A(i, j) an edge i -> j -- transpose first (facade.csr_transpose, bhsparse.csr_transpose_device).
+
+The *_frontier_* functions give the same results and choose a direction per step: a step whose frontier is small goes by
+push (dense.csr_push_semiring_device; "sparse frontier x CSR"), which reads the out-edges of the frontier's vertices and
+nothing else, a step whose frontier is large by the pull call above.  On a graph of high diameter -- a road network, a mesh,
+a banded matrix -- that is the difference between touching every edge once and touching every edge once per level."""
 import numpy as np
 
 from . import _lib
-from .dense import csr_spmm_semiring_device
+from .dense import csr_push_semiring_device, csr_spmm_semiring_device
 from .facade import BhsparseError, _device_csr, _handle
 
 
@@ -97,6 +102,143 @@ def _sssp(bh, n, A, sources, max_sweeps):
     raise BhsparseError("sssp_device: still changing after %d sweeps (%s)" % (sweeps, why), _lib.BHS_ERR_INVALID_ARG)
 
 
+# ---------------------------------------------------------------- a direction per step
+# The frontier size at which one OR_AND push call stops being cheaper than the pull call under the matching complement
+# mask, as n / frontier vertices (tools/push_case.py, profiles/push_case.md).
+PUSH_BELOW = 10
+
+
+def _by_push(nf, n, push_below):
+    """does a frontier of nf vertices go by push: at most n / push_below of them (0: never, inf: always)"""
+    return push_below > 0 and (push_below == float("inf") or nf * push_below <= n)
+
+
+def _out_edges(bh, n, A, At):
+    """the out-edge CSR: given, or A's transpose by the handle (once)"""
+    if At is not None:
+        return At
+    Tp, Tj, Tx, _ = bh.csr_transpose_device(n, n, A, values=A[2] is not None)
+    return Tp, Tj, Tx
+
+
+def _rows_with(T):
+    """the rows of the n x k tensor T that hold a non-zero (a True), ascending: int32"""
+    import torch
+    return torch.nonzero(T.any(dim=1)).flatten().to(torch.int32)
+
+
+def bfs_levels_frontier_device(bh, n, A, sources, At=None, push_below=None):
+    """bfs_levels_device with a direction per level: the same n x k tensor of levels (A(i, j) is an edge j -> i; At =
+    (rowPtr, colInd, val or None) is the CSR of out-edges, A's transpose, computed once with the handle's transpose when
+    None; for a symmetric A pass At=A).  A level whose frontier has at most n / push_below vertices goes by push
+    (push_below None: PUSH_BELOW, the measured crossover; 0: never push; inf: always), the others by the pull call of
+    bfs_levels_device.  A push level is one library call and no pass over all n vertices: the call returns the rows it
+    changed, and the levels and the next frontier's values are read and written at those rows only."""
+    return _bfs_frontier(bh, n, A, sources, At, push_below)[0]
+
+
+def _bfs_frontier(bh, n, A, sources, At=None, push_below=None):
+    """(levels, steps, total device ms of the steps, steps that went by push)"""
+    import torch
+    push_below = PUSH_BELOW if push_below is None else push_below
+    src = _sources(sources, n)
+    k = len(src)
+    dev = A[0].device
+    dt = _value_type(bh, A)
+    levels = torch.zeros((n, k), dtype=dt, device=dev)
+    levels[torch.as_tensor(src, device=dev), torch.arange(k, device=dev)] = 1.0
+    # the frontier: a list of vertices, ascending, with their nf x k rows of 0 / 1 -- or, idx None, the dense n x k tensor
+    idx = torch.as_tensor(np.unique(src), device=dev).to(torch.int32)
+    F = levels.index_select(0, idx.to(torch.int64))
+    G = None
+    reach = None                                                        # push levels' Y: all zero between the levels
+    steps, ms, pushes = 0, 0.0, 0
+    for depth in range(1, n + 1):
+        if idx is not None and _by_push(idx.numel(), n, push_below):
+            if G is None:
+                G = _out_edges(bh, n, A, At)
+            if reach is None:
+                reach = torch.zeros((n, k), dtype=dt, device=dev)
+            _, changed, nxt = csr_push_semiring_device(bh, "or_and", n, n, G, idx, F, reach, mask=levels, complement=True)
+            steps, ms, pushes = steps + 1, ms + bh.spmv_ms, pushes + 1
+            if changed == 0:
+                break
+            at = nxt.to(torch.int64)
+            F = reach.index_select(0, at)
+            levels.index_add_(0, at, F * float(depth + 1))              # (the mask let through unvisited elements only: 0 + level)
+            reach.index_fill_(0, at, 0.0)
+            idx = nxt
+        else:
+            frontier = F if idx is None else torch.zeros((n, k), dtype=dt, device=dev).index_copy_(0, idx.to(torch.int64), F)
+            nxt = torch.zeros_like(frontier)
+            nxt, changed = csr_spmm_semiring_device(bh, "or_and", n, n, A, frontier, nxt, mask=levels, accumulate=False,
+                                                    complement=True)
+            steps, ms = steps + 1, ms + bh.spmv_ms
+            if changed == 0:
+                break
+            levels += nxt * float(depth + 1)
+            idx, F = None, nxt                                          # a dense frontier ...
+            if _by_push((changed + k - 1) // k, n, push_below):         # ... unless it may be small enough: then its list
+                rows = _rows_with(nxt)
+                if _by_push(rows.numel(), n, push_below):
+                    idx, F = rows, nxt.index_select(0, rows.to(torch.int64))
+    return levels, steps, ms, pushes
+
+
+def sssp_frontier_device(bh, n, A, sources, At=None, max_rounds=None, push_below=None):
+    """sssp_device with a direction per round: the same n x k tensor of distances (At, push_below: as
+    bfs_levels_frontier_device).  Round-synchronous Bellman-Ford on a frontier: the vertices whose distance changed in the
+    last round -- the sources at first -- relax their out-edges.  A push round gathers F, a snapshot of D at the frontier,
+    and one MIN_PLUS push call takes the minima into D in place and returns the rows it changed: the next frontier.  A pull
+    round is sssp_device's Jacobi sweep, and its frontier the rows the sweep changed.
+
+    The distances equal sssp_device's bit for bit.  Floating add is monotone (a <= b gives a + w <= b + w after rounding)
+    and min is exact, so a vertex's distance only ever takes values that are the left-to-right sum of the weights along
+    some path from the source, and relaxing an edge from a vertex whose distance has not changed since it last relaxed
+    changes nothing.  Both loops therefore stop at the same point: the least fixed point of D = min(D, D (min.+) A), the
+    minimum over the paths of their left-to-right sums -- whatever the order of the relaxations, and with the frontier's
+    rounds even after the same number of steps as the sweeps.
+
+    Raises BhsparseError when a round still changes something after max_rounds (default n, at least 1) of them: with n
+    rounds that is a cycle of negative weight.  ValueError for a source that is no vertex."""
+    return _sssp_frontier(bh, n, A, sources, At, max_rounds, push_below)[0]
+
+
+def _sssp_frontier(bh, n, A, sources, At=None, max_rounds=None, push_below=None):
+    """(distances, rounds, total device ms of the rounds, rounds that went by push)"""
+    import torch
+    push_below = PUSH_BELOW if push_below is None else push_below
+    src = _sources(sources, n)
+    k = len(src)
+    dev = A[0].device
+    dt = _value_type(bh, A)
+    D = torch.full((n, k), float("inf"), dtype=dt, device=dev)
+    D[torch.as_tensor(src, device=dev), torch.arange(k, device=dev)] = 0.0
+    limit = n if max_rounds is None else int(max_rounds)
+    if limit < 1:
+        raise ValueError("max_rounds: at least one round")
+    idx = torch.as_tensor(np.unique(src), device=dev).to(torch.int32)   # None: everything relaxes (a pull round)
+    G = None
+    rounds, ms, pushes = 0, 0.0, 0
+    for _ in range(limit):
+        if idx is not None and _by_push(idx.numel(), n, push_below):
+            if G is None:
+                G = _out_edges(bh, n, A, At)
+            F = D.index_select(0, idx.to(torch.int64))                  # the snapshot: a round reads last round's distances
+            _, changed, idx = csr_push_semiring_device(bh, "min_plus", n, n, G, idx, F, D)
+            rounds, ms, pushes = rounds + 1, ms + bh.spmv_ms, pushes + 1
+        else:
+            D2 = D.clone()
+            D2, changed = csr_spmm_semiring_device(bh, "min_plus", n, n, A, D, D2, accumulate=True)
+            rounds, ms = rounds + 1, ms + bh.spmv_ms
+            idx = _rows_with(D2 != D) if changed and _by_push((changed + k - 1) // k, n, push_below) else None
+            D = D2
+        if changed == 0:
+            return D, rounds, ms, pushes
+    why = "a cycle of negative weight" if rounds >= n else "max_rounds is below the number of vertices: no verdict on a negative cycle"
+    raise BhsparseError("sssp_frontier_device: still changing after %d rounds (%s)" % (rounds, why), _lib.BHS_ERR_INVALID_ARG)
+
+
 def bfs_levels_csr(n, Ap, Aj, Ax, sources, value_dtype=np.float64, device=0):
     """Convenience: bfs_levels_device once on host CSR arrays.  Returns (levels value_dtype[n, k], info) with
     info["kernels"] (of the last step), info["steps"], info["ms"] (total device time of the steps)."""
@@ -114,3 +256,21 @@ def sssp_csr(n, Ap, Aj, Ax, sources, max_sweeps=None, value_dtype=np.float64, de
         out, steps, ms = _sssp(bh, n, A, sources, max_sweeps)
         return out.cpu().numpy(), {"kernels": bh.kernel_stats(), "steps": steps, "ms": ms}
 
+
+
+def bfs_levels_frontier_csr(n, Ap, Aj, Ax, sources, push_below=None, value_dtype=np.float64, device=0):
+    """Convenience: bfs_levels_frontier_device once on host CSR arrays (the out-edges by the handle's transpose).  Returns
+    (levels value_dtype[n, k], info) with info["kernels"] (of the last step), info["steps"], info["push_steps"], info["ms"]."""
+    A = _device_csr(Ap, Aj, Ax, value_dtype, device)
+    with _handle(value_dtype, device, None) as bh:
+        out, steps, ms, pushes = _bfs_frontier(bh, n, A, sources, None, push_below)
+        return out.cpu().numpy(), {"kernels": bh.kernel_stats(), "steps": steps, "push_steps": pushes, "ms": ms}
+
+
+def sssp_frontier_csr(n, Ap, Aj, Ax, sources, max_rounds=None, push_below=None, value_dtype=np.float64, device=0):
+    """Convenience: sssp_frontier_device once on host CSR arrays.  Returns (distances value_dtype[n, k], info) with
+    info["kernels"] (of the last round), info["steps"], info["push_steps"], info["ms"]."""
+    A = _device_csr(Ap, Aj, Ax, value_dtype, device)
+    with _handle(value_dtype, device, None) as bh:
+        out, steps, ms, pushes = _sssp_frontier(bh, n, A, sources, None, max_rounds, push_below)
+        return out.cpu().numpy(), {"kernels": bh.kernel_stats(), "steps": steps, "push_steps": pushes, "ms": ms}

@@ -108,6 +108,17 @@ public:
                                  const index_type *d_colIndA, int k, const value_type *d_X, long long ldX, int flags,
                                  const value_type *d_M, long long ldM, value_type *d_Y, long long ldY, long long *changed_out);
 
+    // EXTENSION, not part of the reference's API: the push direction of the same step (bhs_csr_push_semiring_device,
+    // include/bhsparse_hip.h, "sparse frontier x CSR") on DEVICE arrays: Y<M> (+)= F (+).(x) G(fidx, :), where G holds
+    // OUT-edges (row j lists the vertices j pushes to: the transpose of the pull calls' A) and d_fidx lists the nf rows of
+    // the frontier; only those rows of G are read.  Any semiring but BHS_SR_PLUS_TIMES; flags: BHS_MV_MASK_COMPLEMENT or 0;
+    // d_valG, d_M, d_next, next_count_out and changed_out may be 0.  d_next (n ints) receives the rows of Y that changed,
+    // ascending: the next frontier.  Needs initPlatform only.
+    int csr_push_semiring_device(int semiring, int m, int n, int nnzG, const value_type *d_valG, const index_type *d_rowPtrG,
+                                 const index_type *d_colIndG, int nf, const index_type *d_fidx, int k, const value_type *d_F,
+                                 long long ldF, int flags, const value_type *d_M, long long ldM, value_type *d_Y, long long ldY,
+                                 index_type *d_next, int *next_count_out, long long *changed_out);
+
     // EXTENSION, not part of the reference's API: the multiply over a semiring (bhs_spgemm_semiring*, include/bhsparse_hip.h,
     // "semiring multiply"; semiring: a BHS_SR_* constant) on the data of initData.  spgemm_semiring is the full product: it
     // fills the csrRowPtrC of initData, and get_nnzC / get_C then return A (+).(x) B on the pattern of A·B.
@@ -287,6 +298,17 @@ inline int bhsparse::csr_spmm_semiring_device(int semiring, int m, int n, int nn
     if (!_h) return BHS_ERR_NOT_READY;
     return bhs_csr_spmm_semiring_device(_h, semiring, m, n, nnzA, d_valA, d_rowPtrA, d_colIndA, k, d_X, ldX, flags, d_M, ldM,
                                         d_Y, ldY, changed_out, 0);
+}
+
+inline int bhsparse::csr_push_semiring_device(int semiring, int m, int n, int nnzG, const value_type *d_valG,
+                                              const index_type *d_rowPtrG, const index_type *d_colIndG, int nf,
+                                              const index_type *d_fidx, int k, const value_type *d_F, long long ldF, int flags,
+                                              const value_type *d_M, long long ldM, value_type *d_Y, long long ldY,
+                                              index_type *d_next, int *next_count_out, long long *changed_out)
+{
+    if (!_h) return BHS_ERR_NOT_READY;
+    return bhs_csr_push_semiring_device(_h, semiring, m, n, nnzG, d_valG, d_rowPtrG, d_colIndG, nf, d_fidx, k, d_F, ldF, flags,
+                                        d_M, ldM, d_Y, ldY, d_next, next_count_out, changed_out, 0);
 }
 
 inline int bhsparse::get_nnzC()

@@ -668,6 +668,74 @@ BHS_API int bhs_csr_spmm_semiring_device(bhs_handle *h, int semiring, int m, int
         bhs_value_t *d_Y /* m x k, in/out */, long long ldY /* >= k */, long long *changed_out /* may be NULL */,
         double *ms_out /* may be NULL */);
 
+/* ---- sparse frontier x CSR ------------------------------------------------
+ * The push direction of the same traversal step: Y (+)= F (+).(x) G restricted to a LIST of rows of G (GraphBLAS vxm with a
+ * sparse vector operand; no reference counterpart; bhs_push_sr.hip.h).  The pull calls above visit all m rows of A every
+ * step; this call reads the listed rows of G and nothing else, so a BFS level or a Bellman-Ford round costs what its
+ * frontier's out-edges cost.  What it is for: graphs of high diameter (road networks, meshes, banded matrices), whose
+ * traversals are thousands of steps with small frontiers.
+ * G holds OUT-edges: row j of G lists the vertices that j pushes to, an entry G(j, v) is an edge j -> v.  G is the transpose
+ *   of the pull calls' A (bhs_csr_transpose_device), or A itself for a symmetric matrix.  G is m x n, 0-based int32 CSR, rows
+ *   need NOT be ascending, duplicate (row, column) pairs are legal and every one of them is an entry; d_valG may be NULL:
+ *   every entry then counts as the value 1.
+ * d_fidx: nf rows of G, the frontier, in any order; a vertex may be listed more than once, and each listing is an operand of
+ *   its own.  F is nf x k, row p belongs to d_fidx[p]; M and Y are n x k; all row-major with leading dimensions ldF, ldM,
+ *   ldY >= k, indexed in 64 bits; the gaps c in [k, ld) are never read and never written.  nf, m, n and nnzG may be 0.
+ * The rule.  For every list position p < nf, every entry e of row d_fidx[p] of G and every column c < k, the selected
+ *   element Y(col_e, c) becomes round(double(Y(col_e, c)) (+) (g_e (x) F(p, c))).  Products, reductions, identities, the NaN
+ *   rule, -0 below +0 and OR_AND's notion of non-zero (a Y that is reached counts as 1 where it is not zero, as y_old does
+ *   under BHS_MV_ACCUM) are word for word those of "semiring multiply".  Every element of F counts as an entry, as X does in
+ *   the pull call.  The call ALWAYS accumulates: there is no form that overwrites, and an element that no product reaches is
+ *   neither read nor written.  The frontier's entries, repeats counted, number below 2^31 (else BHS_ERR_INVALID_ARG).
+ * Semirings.  The seven whose (+) gives the same bits in any order: BHS_SR_MIN_PLUS, MAX_PLUS, MAX_TIMES, MIN_MAX, MAX_MIN,
+ *   OR_AND and PLUS_PAIR (every PLUS_PAIR product is 1 and neither valG nor F is read, so the order of its adds cannot
+ *   matter).  BHS_SR_PLUS_TIMES is refused on the host with BHS_ERR_INVALID_ARG: products that meet in an element of Y
+ *   arrive through atomics in whatever order the hardware runs them, and a floating sum scattered that way would break this
+ *   library's promise that a result is a bit-for-bit function of its input.  (It needs a store-then-sum-by-destination pass.)
+ *   In the float build each update rounds to float; rounding is monotone, so that equals one rounding at the end for min,
+ *   max and or.  PLUS_PAIR adds 1 per entry with a rounding each: exact while the count stays below 2^24 (2^53 in double).
+ * The update is a compare-and-swap loop on the element's bits over the order-preserving keys of the reductions: the element
+ *   is read first and nothing is written where the combined value has the same bits.  A retry happens only because another
+ *   update of the same element went in; nothing waits.  The hardware's floating min / max atomics are not used (their NaN
+ *   and zero ordering is not this contract's).
+ * Mask.  Over Y's elements, with the set / complement rules of the pull call: M(v, c) is SET where non-zero (NaN is set, -0
+ *   and +0 are not); BHS_MV_MASK_COMPLEMENT selects what is NOT set; NULL selects everything; COMPLEMENT with a NULL mask is
+ *   refused.  An unselected element is neither read nor written.  BHS_MV_MASK_COMPLEMENT is the only flag.
+ * changed_out (may be NULL): the number of selected elements of Y whose final value differs, as a number, from their value
+ *   on entry (+0 equals -0, NaN over NaN is unchanged).  All seven (+) move an element one way only, so this is the number
+ *   of elements that received at least one effective update; it is taken through a test-and-set on a workspace bit per
+ *   element: an exact integer, the same from run to run.
+ * d_next (may be NULL; capacity n ints) / next_count_out (may be NULL): the rows of Y with at least one changed element,
+ *   ascending, each once, *next_count_out <= n of them: the next frontier.  Built by compacting a bit-per-row map with the
+ *   library's scan, never appended in arrival order: the list is identical from run to run.  With d_next NULL no list is
+ *   made and *next_count_out is 0; with d_next and changed_out both NULL no bitmap is touched.  Counts and the error word
+ *   come back in the ONE round trip the call makes, at its end; Y is never copied to the host.
+ * Validation, on the device, each check before the dependent read: a d_fidx[p] outside [0, m); for a row that is pushed,
+ *   rowPtrG[j] > rowPtrG[j+1] or either of the two outside [0, nnzG]; a column outside [0, n) in a pushed row.  Each
+ *   returns BHS_ERR_INVALID_ARG, and Y may be partly written, never outside its selected elements.  Rows of G that are not
+ *   in the frontier are NOT READ AT ALL -- neither their row pointer nor their columns, so nothing in them is validated
+ *   (rowPtrG[0] and rowPtrG[m] neither): that is the point of the call.
+ *   On the host, each BHS_ERR_INVALID_ARG with Y untouched: a NULL handle, negative sizes (m, n, nnzG, nf), k < 1, ldF or
+ *   ldY below k, ldM below k with a mask, NULL arrays where sizes are positive (d_rowPtrG with m > 0, d_colIndG with
+ *   nnzG > 0, d_fidx or d_F with nf > 0, d_Y with n > 0), an unknown semiring or BHS_SR_PLUS_TIMES, any flag other than
+ *   BHS_MV_MASK_COMPLEMENT, COMPLEMENT without a mask, the footprint of Y or of d_next overlapping G, d_fidx, F or M (or
+ *   each other), and a call between bhs_spgemm_symbolic and bhs_spgemm_finish.
+ * Synchronous on the handle's stream, needs no bound data, leaves the handle as it was (a workspace of its own).  ms_out
+ *   (may be NULL): device time of the call.  bhs_get_kernel_stats then reports push_degrees (validation and the listed rows'
+ *   lengths), push_scan (the library's one-pass scan: lengths to offsets, and the row map's counts to places), push_edges
+ *   (runs of 256 consecutive (entry x column) pairs of the frontier a wave, whichever vertices they belong to: at k = 1 a
+ *   hub of 10^5 entries is spread over 400 waves) and push_compact (the row map to d_next).                       */
+BHS_API int bhs_csr_push_semiring_device(bhs_handle *h, int semiring,
+        int m /* rows of G = vertices pushed from */, int n /* columns of G = rows of Y */, int nnzG,
+        const bhs_value_t *d_valG /* may be NULL: ones */, const int *d_rowPtrG, const int *d_colIndG,
+        int nf, const int *d_fidx /* nf rows of G */,
+        int k, const bhs_value_t *d_F /* nf x k */, long long ldF,
+        int flags /* BHS_MV_MASK_COMPLEMENT only */,
+        const bhs_value_t *d_M /* n x k or NULL */, long long ldM,
+        bhs_value_t *d_Y /* n x k, in/out */, long long ldY,
+        int *d_next /* may be NULL; capacity n */, int *next_count_out /* may be NULL */,
+        long long *changed_out /* may be NULL */, double *ms_out /* may be NULL */);
+
 /* replaces bhsparse::get_nnzC (bhsparse.h: get_nnzC -> bhsparse_cuda::get_nnzC). */
 BHS_API int bhs_get_nnzC(bhs_handle *h, int *nnzC_out);
 
