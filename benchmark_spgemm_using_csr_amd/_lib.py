@@ -114,6 +114,8 @@ SYMBOLS = {
                                           C.c_longlong, C.POINTER(C.c_longlong), C.POINTER(C.c_double)]),
     "bhs_csr_push_semiring_device": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, C.c_longlong, _i, _vp, C.c_longlong,
                                           _vp, C.c_longlong, _vp, C.POINTER(_i), C.POINTER(C.c_longlong), C.POINTER(C.c_double)]),
+    "bhs_csr_aggregate_device": (_i, [_vp, _i, _i, _vp, _vp, _vp, C.c_uint, _i, _vp, _vp, C.POINTER(_i), C.POINTER(_i),
+                                      C.POINTER(C.c_double)]),
     "bhs_strerror": (C.c_char_p, [_i]),
     "bhs_version": (C.c_char_p, []),
 }

@@ -1,0 +1,251 @@
+"""A smoothed-aggregation multigrid setup that never leaves the device: MIS(2) aggregation (bhs_csr_aggregate_device;
+include/bhsparse_hip.h, "aggregation") and, built from it and the existing device calls of a `facade.bhsparse` handle, the
+strength pattern, the tentative and the smoothed prolongator, the Galerkin product, a V-cycle and a solver.
+
+Everything is a torch tensor on the handle's GPU: a matrix is (rowPtr int32, colInd int32, val), a pattern the first two.
+Functions of handles, not methods.  Every step is a thin call into the C-ABI; a missing library raises, nothing is computed
+on the host but the handful of scalars a call returns."""
+import ctypes as C
+import time
+
+import numpy as np
+
+from . import _lib
+from .dense import csr_spmv_device
+from .facade import BhsparseError, _alloc, _check, _device_csr, _handle, _host, _ptr, select_spec  # noqa: F401
+
+
+def _tdt(bh):
+    import torch
+    return torch.float32 if bh._vdt == np.dtype(np.float32) else torch.float64
+
+
+# ---------------------------------------------------------------- aggregation
+def aggregate_raw_device(bh, n, nnzS, d_rowPtrS, d_colIndS, d_prio, seed, flags, d_agg, d_roots):
+    """bhs_csr_aggregate_device on caller-given arrays, the C arguments in order (d_prio and d_roots may be None): the status
+    code; sets bh.aggregate_ms, bh.aggregate_nagg and bh.aggregate_rounds on success."""
+    if bh._h is None:
+        return _lib.BHS_ERR_NOT_READY
+    nagg, rounds, ms = C.c_int(0), C.c_int(0), C.c_double(0)
+    err = bh._lib.bhs_csr_aggregate_device(bh._h, int(n), int(nnzS), _ptr(d_rowPtrS), _ptr(d_colIndS), _ptr(d_prio),
+                                           int(seed) & 0xFFFFFFFF, int(flags), _ptr(d_agg), _ptr(d_roots), C.byref(nagg),
+                                           C.byref(rounds), C.byref(ms))
+    if err == _lib.BHS_SUCCESS:
+        bh.aggregate_ms, bh.aggregate_nagg, bh.aggregate_rounds = float(ms.value), int(nagg.value), int(rounds.value)
+    return err
+
+
+def aggregate_device(bh, n, S, seed=0, prio=None):
+    """MIS(2) aggregates of the n x n pattern S = (rowPtr, colInd[, anything]) of strong connections, torch tensors on the
+    handle's GPU; prio: n priorities as an int32 / uint32 tensor's bits, or None for the hash of (vertex, seed).  Returns
+    (agg int32[n], nagg, roots int32[nagg]): the aggregate of every vertex and the roots, ascending, agg[roots[a]] == a.
+    bh.aggregate_rounds and bh.aggregate_ms hold the rounds and the device time.  Raises BhsparseError on failure."""
+    import torch
+    Sp, Sj = S[0], S[1]
+    agg = _alloc(n, torch.int32, Sp.device)
+    roots = _alloc(n, torch.int32, Sp.device)
+    torch.cuda.synchronize()                           # the library works on its own stream (see facade.initData_device)
+    _check(aggregate_raw_device(bh, n, Sj.numel(), Sp, Sj, prio, seed, 0, agg, roots), "bhs_csr_aggregate_device")
+    return agg[:n], bh.aggregate_nagg, roots[:bh.aggregate_nagg]
+
+
+# ---------------------------------------------------------------- the pieces of a level
+def strength_device(bh, n, A, theta):
+    """The symmetric pattern of strong connections of the n x n matrix A (rows strictly ascending): the selection keeps the
+    diagonal and every a_ij unless |a_ij| < theta * max_{k != i} |a_ik| (csr_select_device, rel_tol, keep_diag), its
+    transpose (csr_transpose_device) is united with it (csr_add_device).  theta == 0 is pattern(A) U pattern(A^T).
+    Returns (rowPtr, colInd); bh.strength_ms is the three calls' device time."""
+    import torch
+    Zp, Zj, _ = bh.csr_select_device(n, n, A, select_spec(rel_tol=float(theta), keep_diag=True), values=False)
+    ms = bh.select_ms
+    Tp, Tj, _, _ = bh.csr_transpose_device(n, n, (Zp, Zj, None), values=False)
+    ms += bh.transpose_ms
+    one = lambda j: torch.ones(max(j.numel(), 1), dtype=_tdt(bh), device=j.device)[:j.numel()]   # noqa: E731
+    Sp, Sj, _, _ = bh.csr_add_device(n, n, 1.0, (Zp, Zj, one(Zj)), 1.0, (Tp, Tj, one(Tj)))
+    bh.strength_ms = ms + bh.add_ms
+    return Sp, Sj
+
+
+def tentative_device(bh, n, agg, nagg, cand=None):
+    """The tentative prolongator T (n x nagg) of the aggregates `agg` and one candidate vector (ones when None):
+    T(i, agg[i]) = cand[i] / ||cand over the aggregate||_2.  The column norms come from the stable transpose of T with its
+    values (csr_transpose_device), a SQ_PLUS reduction along its rows (csr_reduce_device) and a square root; T's values from
+    csr_scale_device with right_div: no scattered sum, so they repeat bit for bit.  Returns ((rowPtr, colInd, val),
+    coarse_cand): the norms are the candidate on the coarse level."""
+    import torch
+    dev = agg.device
+    Tp = torch.arange(n + 1, dtype=torch.int32, device=dev)
+    Tj = agg.to(torch.int32).contiguous()
+    x = torch.ones(n, dtype=_tdt(bh), device=dev) if cand is None else cand.to(_tdt(bh)).contiguous()
+    Rp, Rj, Rx, _ = bh.csr_transpose_device(n, nagg, (Tp, Tj, x), values=True)
+    nrm = torch.sqrt(bh.csr_reduce_device(nagg, n, (Rp, Rj, Rx), _lib.BHS_AXIS_ROWS, _lib.BHS_RED_SQ_PLUS))
+    Tx = bh.csr_scale_device(n, nagg, (Tp, Tj, x), 1.0, right=nrm, right_div=True)
+    return (Tp, Tj, Tx), nrm
+
+
+def _result_device(bh, rows, dev):
+    """(rowPtrC, colIndC, valC) of the handle's last multiply as torch tensors of their own: cloned out of bhs_get_C_device
+    before the handle is used again"""
+    import torch
+    nnz = bh.get_nnzC()
+    ptrs = bh.get_C_device()
+    vstr, tdt = ("<f4", torch.float32) if bh._vdt == np.dtype(np.float32) else ("<f8", torch.float64)
+
+    class _View(object):
+        def __init__(self, ptr, count, typestr):
+            self.__cuda_array_interface__ = {"shape": (int(count),), "typestr": typestr, "data": (int(ptr), False), "version": 2,
+                                             "strides": None}
+
+    def take(ptr, count, typestr, dtype):
+        if count == 0 or not ptr:
+            return torch.empty(0, dtype=dtype, device=dev)
+        return torch.as_tensor(_View(ptr, count, typestr), device=dev).clone()
+    out = take(ptrs[0], rows + 1, "<i4", torch.int32), take(ptrs[1], nnz, "<i4", torch.int32), take(ptrs[2], nnz, vstr, tdt)
+    torch.cuda.synchronize()
+    return out
+
+
+def smoothed_prolongator_device(bh, n, nc, A, T, omega):
+    """P = T - omega D^-1 A T on device tensors, the steps of facade.smoothed_prolongator_csr: diag(A), -omega D^-1 A, the
+    multiply with T plus T.  Returns (rowPtr, colInd, val) of its own; bh.prolongator_ms is the device time."""
+    d = bh.csr_reduce_device(n, n, A, _lib.BHS_AXIS_DIAG, _lib.BHS_RED_PLUS)
+    ms = bh.reduce_ms
+    Sx = bh.csr_scale_device(n, n, A, -float(omega), left=d, left_div=True)
+    ms += bh.scale_ms
+    nnzA, nnzT = A[1].numel(), T[1].numel()
+    _check(bh.initData_device(n, n, nc, nnzA, Sx, A[0], A[1], nnzT, T[2], T[0], T[1]), "initData_device(-omega D^-1 A, T)")
+    t0 = time.perf_counter()
+    _check(bh.spgemm_add_device(1.0, 1.0, nnzT, T[2], T[0], T[1]), "bhs_spgemm_add_device")
+    ms += (time.perf_counter() - t0) * 1e3               # (the call is synchronous: the multiply and the add)
+    P = _result_device(bh, n, A[0].device)
+    _check(bh.free_mem(), "free_mem")
+    bh.prolongator_ms = ms
+    return P
+
+
+def galerkin_device(h1, h2, n, nc, A, P):
+    """(A_c = P^T (A P), R = P^T) on device tensors, the steps of facade.galerkin_csr: h2 transposes P, h1 multiplies A P, h2
+    multiplies P^T with h1's device-resident result.  h1.galerkin_ms is the device time of the three."""
+    Rp, Rj, Rx, _ = h2.csr_transpose_device(n, nc, P)
+    ms = h2.transpose_ms
+    nnzA, nnzP = A[1].numel(), P[1].numel()
+    _check(h1.initData_device(n, n, nc, nnzA, A[2], A[0], A[1], nnzP, P[2], P[0], P[1]), "initData_device(A, P)")
+    _check(h1.spgemm(), "spgemm(A P)")
+    ms += float(sum(h1.stage_ms))
+    nnzAP = h1.get_nnzC()
+    dAPp, dAPj, dAPx = h1.get_C_device()
+    _check(h2.initData_device(nc, n, nc, nnzP, Rx, Rp, Rj, nnzAP, dAPx, dAPp, dAPj), "initData_device(P^T, A P)")
+    _check(h2.spgemm(), "spgemm(P^T AP)")
+    ms += float(sum(h2.stage_ms))
+    Ac = _result_device(h2, nc, A[0].device)
+    _check(h2.free_mem(), "free_mem")
+    _check(h1.free_mem(), "free_mem")
+    h1.galerkin_ms = ms
+    return Ac, (Rp, Rj, Rx)
+
+
+# ---------------------------------------------------------------- the setup
+def sa_setup_device(handles, n, A, theta=0.0, omega=2.0 / 3.0, max_levels=10, min_coarse=40, seed=0):
+    """The smoothed-aggregation hierarchy of the n x n matrix A = (rowPtr, colInd, val), torch tensors on the GPU, rows
+    strictly ascending.  handles: two initialised facade.bhsparse handles (h1, h2) of A's value type, or a callable that
+    makes one (called twice; those are destroyed here).  Per level: strength -> aggregate -> tentative -> P = T - omega
+    D^-1 A T -> A_c = P^T (A P); coarsening stops at max_levels, at min_coarse rows or fewer, or where nothing is merged.
+    Returns (levels, info): levels a list of (A_l, P_l, R_l = P_l^T) with P = R = None on the last; info a list with one
+    entry per level: n, nnz and, where the level was coarsened, nagg, rounds and the device ms of strength / aggregate /
+    prolongator / galerkin."""
+    own = callable(handles)
+    h1, h2 = (handles(), handles()) if own else handles
+    try:
+        levels, info = [], []
+        while True:
+            rec = {"n": n, "nnz": int(A[1].numel())}
+            info.append(rec)
+            if len(levels) + 1 >= max_levels or n <= min_coarse:
+                break
+            S = strength_device(h1, n, A, theta)
+            agg, nagg, _ = aggregate_device(h1, n, S, seed)
+            if nagg >= n:
+                break
+            T, _ = tentative_device(h1, n, agg, nagg)
+            P = smoothed_prolongator_device(h1, n, nagg, A, T, omega)
+            Ac, R = galerkin_device(h1, h2, n, nagg, A, P)
+            rec.update({"nagg": nagg, "rounds": h1.aggregate_rounds, "strength_ms": h1.strength_ms,
+                        "aggregate_ms": h1.aggregate_ms, "prolongator_ms": h1.prolongator_ms, "galerkin_ms": h1.galerkin_ms})
+            levels.append((A, P, R))
+            A, n = Ac, nagg
+        levels.append((A, None, None))
+        return levels, info
+    finally:
+        if own:
+            h1.freePlatform()
+            h2.freePlatform()
+
+
+def sa_setup_csr(n, Ap, Aj, Ax, theta=0.0, omega=2.0 / 3.0, max_levels=10, min_coarse=40, seed=0, value_dtype=np.float64,
+                 device=0):
+    """Convenience: the hierarchy of a host CSR matrix (rows strictly ascending), built on the device and copied back.
+    Returns (levels, info): levels a list of (A_l, P_l, R_l) with every matrix a (rowPtr, colInd, val) triple of numpy
+    arrays, None for P and R on the last; info as sa_setup_device."""
+    A = _device_csr(Ap, Aj, Ax, value_dtype, device)
+    with _handle(value_dtype, device, None) as h1, _handle(value_dtype, device, None) as h2:
+        levels, info = sa_setup_device((h1, h2), n, A, theta, omega, max_levels, min_coarse, seed)
+    host = lambda M: None if M is None else _host(*M)   # noqa: E731
+    return [(host(a), host(p), host(r)) for a, p, r in levels], info
+
+
+# ---------------------------------------------------------------- the cycle
+def _rows(M):
+    return int(M[0].numel()) - 1
+
+
+def _diagonals(bh, levels):
+    """diag(A_l) of every level but the last, kept on the hierarchy's first entry between cycles"""
+    return [bh.csr_reduce_device(_rows(A), _rows(A), A, _lib.BHS_AXIS_DIAG, _lib.BHS_RED_PLUS) for A, P, _ in levels if P is not None]
+
+
+def _jacobi(bh, A, d, b, x, omega_jacobi, sweeps):
+    n = _rows(A)
+    for _ in range(sweeps):
+        r = csr_spmv_device(bh, n, n, A, x, alpha=-1.0, beta=1.0, y=b.clone())      # b - A x
+        x = x + omega_jacobi * r / d
+    return x
+
+
+def vcycle_device(bh, levels, b, x, omega_jacobi=2.0 / 3.0, pre=1, post=1, diagonals=None, lvl=0):
+    """One V(pre, post) cycle for A_0 x = b on the hierarchy of sa_setup_device: weighted Jacobi from csr_spmv_device
+    (y = alpha A x + beta y) and the diagonal, restriction and prolongation by R_l and P_l through csr_spmv_device, the
+    coarsest level by a dense torch.linalg.solve.  Returns the new x."""
+    import torch
+    A, P, R = levels[lvl]
+    n = _rows(A)
+    if P is None:
+        dense = torch.zeros((n, n), dtype=b.dtype, device=b.device)
+        rows = torch.repeat_interleave(torch.arange(n, device=b.device), (A[0][1:] - A[0][:-1]).long())
+        dense.index_put_((rows, A[1].long()), A[2], accumulate=True)
+        return torch.linalg.solve(dense, b)
+    if diagonals is None:
+        diagonals = _diagonals(bh, levels)
+    d, nc = diagonals[lvl], _rows(R)
+    x = _jacobi(bh, A, d, b, x, omega_jacobi, pre)
+    r = csr_spmv_device(bh, n, n, A, x, alpha=-1.0, beta=1.0, y=b.clone())
+    rc = csr_spmv_device(bh, nc, n, R, r)
+    xc = vcycle_device(bh, levels, rc, torch.zeros_like(rc), omega_jacobi, pre, post, diagonals, lvl + 1)
+    x = csr_spmv_device(bh, n, nc, P, xc, alpha=1.0, beta=1.0, y=x.clone())
+    return _jacobi(bh, A, d, b, x, omega_jacobi, post)
+
+
+def solve_device(bh, levels, b, tol=1e-8, maxiter=100):
+    """V(1,1) cycles from x = 0 until ||b - A x|| <= tol ||b|| or maxiter cycles.  Returns (x, cycles, residual norms)."""
+    import torch
+    A = levels[0][0]
+    n = _rows(A)
+    diagonals = _diagonals(bh, levels)
+    x = torch.zeros_like(b)
+    res = [float(torch.linalg.norm(b))]
+    cycles = 0
+    while res[-1] > tol * res[0] and cycles < maxiter:
+        x = vcycle_device(bh, levels, b, x, diagonals=diagonals)
+        r = csr_spmv_device(bh, n, n, A, x, alpha=-1.0, beta=1.0, y=b.clone())
+        res.append(float(torch.linalg.norm(r)))
+        cycles += 1
+    return x, cycles, res

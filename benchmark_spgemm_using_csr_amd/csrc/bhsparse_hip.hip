@@ -399,6 +399,10 @@ struct bhs_handle {
     // frontier's degrees and then the row map's counts in its count buffer
     SideWs pushWs;
     DevBuf pushOff;                      // the scanned counts: the frontier's offsets, then the places in d_next
+    // the aggregation (bhs_host_aggregate.inc.h): the vertices' words, the first gather's result, the root bitmap and pass 1's
+    // aggregates in its queue buffer, the roots per bitmap word in its count buffer
+    SideWs aggWs;
+    DevBuf aggOff;                       // the scanned counts: every bitmap word's first root number
 };
 
 namespace {
@@ -565,6 +569,7 @@ inline int one_launch(int rc) { return rc != BHS_SUCCESS ? rc : 1; }
 #include "bhs_host_spmv.inc.h"
 #include "bhs_host_spmv_sr.inc.h"
 #include "bhs_host_push_sr.inc.h"
+#include "bhs_host_aggregate.inc.h"
 #include "bhs_host_transpose.inc.h"
 #include "bhs_host_reduce.inc.h"
 #include "bhs_host_semiring.inc.h"

@@ -119,6 +119,13 @@ public:
                                  long long ldF, int flags, const value_type *d_M, long long ldM, value_type *d_Y, long long ldY,
                                  index_type *d_next, int *next_count_out, long long *changed_out);
 
+    // EXTENSION, not part of the reference's API: MIS(2) aggregation of an n x n pattern of strong connections on DEVICE
+    // arrays (bhs_csr_aggregate_device, include/bhsparse_hip.h, "aggregation"): d_agg (n ints) receives the aggregate of
+    // every vertex, d_roots (room for n ints, may be 0) the roots, ascending, *nagg_out their number and *rounds_out the
+    // rounds taken.  d_prio (n priorities) may be 0: the hash of (vertex, seed); flags must be 0.  Needs initPlatform only.
+    int csr_aggregate_device(int n, int nnzS, const index_type *d_rowPtrS, const index_type *d_colIndS, const unsigned *d_prio,
+                             unsigned seed, int flags, index_type *d_agg, index_type *d_roots, int *nagg_out, int *rounds_out);
+
     // EXTENSION, not part of the reference's API: the multiply over a semiring (bhs_spgemm_semiring*, include/bhsparse_hip.h,
     // "semiring multiply"; semiring: a BHS_SR_* constant) on the data of initData.  spgemm_semiring is the full product: it
     // fills the csrRowPtrC of initData, and get_nnzC / get_C then return A (+).(x) B on the pattern of A·B.
@@ -309,6 +316,14 @@ inline int bhsparse::csr_push_semiring_device(int semiring, int m, int n, int nn
     if (!_h) return BHS_ERR_NOT_READY;
     return bhs_csr_push_semiring_device(_h, semiring, m, n, nnzG, d_valG, d_rowPtrG, d_colIndG, nf, d_fidx, k, d_F, ldF, flags,
                                         d_M, ldM, d_Y, ldY, d_next, next_count_out, changed_out, 0);
+}
+
+inline int bhsparse::csr_aggregate_device(int n, int nnzS, const index_type *d_rowPtrS, const index_type *d_colIndS,
+                                          const unsigned *d_prio, unsigned seed, int flags, index_type *d_agg,
+                                          index_type *d_roots, int *nagg_out, int *rounds_out)
+{
+    if (!_h) return BHS_ERR_NOT_READY;
+    return bhs_csr_aggregate_device(_h, n, nnzS, d_rowPtrS, d_colIndS, d_prio, seed, flags, d_agg, d_roots, nagg_out, rounds_out, 0);
 }
 
 inline int bhsparse::get_nnzC()

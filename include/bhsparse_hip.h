@@ -736,6 +736,55 @@ BHS_API int bhs_csr_push_semiring_device(bhs_handle *h, int semiring,
         int *d_next /* may be NULL; capacity n */, int *next_count_out /* may be NULL */,
         long long *changed_out /* may be NULL */, double *ms_out /* may be NULL */);
 
+/* ---- aggregation -----------------------------------------------------------
+ * MIS(2) aggregation of the vertices of an n x n pattern S of strong connections: the coarsening step of a smoothed-
+ * aggregation multigrid setup, the one that produces the tentative prolongator's pattern (no reference counterpart;
+ * bhs_aggregate.hip.h).  S is 0-based int32 CSR; values are NOT TAKEN, so the double and the float library run the same code.
+ * Neighbours.  N(i) is the set of columns of row i of S.  The diagonal, repeated columns and the order inside a row make no
+ *   difference; rows need not be sorted.
+ * Keys.  Vertex i has the 64-bit key prio31(i) << 31 | i: prio31(i) = d_prio[i] >> 1 where d_prio is given, else h >> 1 of
+ *   the 32-bit hash (all arithmetic mod 2^32)
+ *       h = (i ^ seed) + 0x9e3779b9;  h ^= h >> 16;  h *= 0x85ebca6b;  h ^= h >> 13;  h *= 0xc2b2ae35;  h ^= h >> 16.
+ *   Keys are distinct: every tie of priorities is broken by index.
+ * Roots.  For a structurally symmetric S the roots are THE greedy distance-2 independent set in descending key order: a
+ *   vertex is a root exactly when no vertex of greater key within two steps of it is a root.  That set is unique, so the
+ *   result does not depend on how the work is scheduled.
+ * Numbering.  Roots are numbered in ascending vertex order: d_agg[d_roots[a]] == a, d_roots ascending, *nagg_out of them.
+ * Pass 1.  A vertex that is no root and has a root in N(i) joins the aggregate of the root of greatest key in N(i) (on a
+ *   symmetric S there is at most one such root).
+ * Pass 2.  Every remaining vertex joins the pass-1 aggregate of the member of N(i) of greatest key among those that pass 1
+ *   or the root numbering placed.  Pass 2 reads pass 1's result and never its own: the two live in separate arrays.
+ * Isolated vertices.  A vertex without off-diagonal neighbours is a root and a singleton aggregate.
+ * Non-symmetric S.  The call still ends, every vertex gets an aggregate in [0, nagg) and d_agg[d_roots[a]] == a; which
+ *   aggregates, is unspecified.
+ * Reproducibility.  The result is a function of (pattern, priorities or seed) alone: the same bits from run to run, from
+ *   handle to handle, and in the double and the float library.  No atomic touches a result.
+ * The algorithm is synchronous rounds over one word a vertex, state << 62 | key (undecided 1, in 2, out 0).  A round:
+ *   t1[i] = max of the words over i and N(i); then, for undecided i only, t2 = max of t1 over i and N(i) -- t2 is i's own word:
+ *   i is in; t2's state is in: i is out; else i stays undecided.  The undecided vertex of greatest key is decided in every
+ *   round, so the call ends within n rounds (hashed priorities: 4 to 14 at n <= 3000).  The host reads the count of
+ *   undecided vertices once a round, one round trip; *rounds_out is the number of rounds.  The call returns
+ *   BHS_ERR_INTERNAL when a round decides nothing or after n + 1 rounds; nothing spins on the device, nothing waits for
+ *   another workgroup.
+ * Validation, on the device, each check ahead of the dependent read: rowPtrS[i] > rowPtrS[i+1] or either outside
+ *   [0, nnzS]; a column outside [0, n).  On the host: a NULL handle, negative n or nnzS, flags != 0, NULL d_rowPtrS or
+ *   d_agg with n > 0, NULL d_colIndS with nnzS > 0, the footprint of d_agg or d_roots (n ints each) overlapping S, d_prio or
+ *   each other, and a call between bhs_spgemm_symbolic and bhs_spgemm_finish.  Each returns BHS_ERR_INVALID_ARG; on refusal
+ *   nothing is read or written out of bounds, the outputs' contents are unspecified, nothing stays queued.
+ * n == 0 succeeds with *nagg_out = 0 and *rounds_out = 0 and launches nothing.
+ * Synchronous on the handle's stream, needs no bound data, leaves the handle as it was (a workspace of its own).  ms_out
+ *   (may be NULL): device time of the call, the rounds' round trips included.  bhs_get_kernel_stats then reports agg_init
+ *   (keys, the row pointer's validation), agg_near and agg_decide (the two gathers of a round, a row spread over 1, 4, 16 or
+ *   64 lanes by the pattern's mean row length), agg_scan (the roots counted per 64 vertices, the library's one-pass scan,
+ *   the numbering) and agg_join (the two passes).                                                                   */
+BHS_API int bhs_csr_aggregate_device(bhs_handle *h, int n, int nnzS,
+        const int *d_rowPtrS, const int *d_colIndS /* n x n pattern of strong connections; values are not taken */,
+        const unsigned *d_prio /* n caller priorities, or NULL: the hash */,
+        unsigned seed, int flags /* must be 0 */,
+        int *d_agg /* out: n ints, the aggregate of every vertex, in [0, nagg) */,
+        int *d_roots /* out, may be NULL: the roots, ascending; room for n ints */,
+        int *nagg_out /* may be NULL */, int *rounds_out /* may be NULL */, double *ms_out /* may be NULL */);
+
 /* replaces bhsparse::get_nnzC (bhsparse.h: get_nnzC -> bhsparse_cuda::get_nnzC). */
 BHS_API int bhs_get_nnzC(bhs_handle *h, int *nnzC_out);
 

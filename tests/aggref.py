@@ -1,0 +1,317 @@
+"""bhs_csr_aggregate_device of include/bhsparse_hip.h ("aggregation") restated in numpy: the reference of its tests, and
+the scipy restatement of the smoothed-aggregation hierarchy that benchmark_spgemm_using_csr_amd/amg.py builds on top of it.
+
+S is an n x n CSR pattern; N(i) is the set of columns of row i -- the diagonal, repeats and the order inside a row make no
+difference.  Vertex i has the key prio31(i) << 31 | i with prio31 = prio[i] >> 1 or hash(i, seed) >> 1.  Three things are
+restated independently of each other: the synchronous rounds the library runs (`rounds`), the greedy distance-2
+independent set in descending key order by its definition (`greedy`), and the two join passes (`join`)."""
+import numpy as np
+
+M32 = 0xFFFFFFFF
+UNDECIDED, IN = np.uint64(1 << 62), np.uint64(2 << 62)
+
+
+def hash32(i, seed):
+    """the header's hash of a vertex number, all arithmetic mod 2^32 (i: an array or a number)"""
+    h = ((np.asarray(i, np.uint64) ^ np.uint64(seed & M32)) + np.uint64(0x9e3779b9)) & np.uint64(M32)
+    h ^= h >> np.uint64(16)
+    h = (h * np.uint64(0x85ebca6b)) & np.uint64(M32)
+    h ^= h >> np.uint64(13)
+    h = (h * np.uint64(0xc2b2ae35)) & np.uint64(M32)
+    h ^= h >> np.uint64(16)
+    return h
+
+
+def keys(n, seed=0, prio=None):
+    """the n distinct 62-bit keys as uint64"""
+    i = np.arange(n, dtype=np.uint64)
+    p = hash32(i, seed) if prio is None else np.asarray(prio, np.uint64) & np.uint64(M32)
+    return ((p >> np.uint64(1)) << np.uint64(31)) | i
+
+
+def edges(n, Sp, Sj):
+    """(row, column) of every entry of S"""
+    Sp = np.asarray(Sp, np.int64)
+    return np.repeat(np.arange(n, dtype=np.int64), np.diff(Sp[:n + 1])), np.asarray(Sj, np.int64)[Sp[0]:Sp[n]]
+
+
+def _near_max(n, r, c, w):
+    """max of w over i and N(i)"""
+    out = w.copy()
+    np.maximum.at(out, r, w[c])
+    return out
+
+
+def rounds(n, Sp, Sj, key):
+    """The library's algorithm: (is_root bool[n], number of rounds).  State undecided 1, in 2, out 0 in bits 62..63 of a
+    word a vertex; a round is two max passes over the closed neighbourhoods."""
+    r, c = edges(n, Sp, Sj)
+    w = UNDECIDED | key
+    nrounds = 0
+    while np.any((w >> np.uint64(62)) == 1):
+        assert nrounds <= n, "a round decides at least one vertex"
+        t1 = _near_max(n, r, c, w)
+        t2 = _near_max(n, r, c, t1)
+        und = (w >> np.uint64(62)) == 1
+        goes_in = und & (t2 == w)
+        goes_out = und & ~goes_in & ((t2 >> np.uint64(62)) == 2)
+        assert goes_in.any() or goes_out.any()
+        w = np.where(goes_in, IN | key, np.where(goes_out, key, w))
+        nrounds += 1
+    return (w >> np.uint64(62)) == 2, nrounds
+
+
+def greedy(n, Sp, Sj, key):
+    """The definition, for a structurally symmetric S: vertices in descending key order, a vertex is a root unless a root
+    chosen earlier lies within two steps of it.  is_root bool[n]."""
+    Sp = np.asarray(Sp, np.int64)
+    Sj = np.asarray(Sj, np.int64)
+    blocked = np.zeros(n, bool)
+    root = np.zeros(n, bool)
+    for v in np.argsort(key)[::-1]:
+        if blocked[v]:
+            continue
+        root[v] = True
+        blocked[v] = True
+        for u in Sj[Sp[v]:Sp[v + 1]]:
+            blocked[u] = True
+            blocked[Sj[Sp[u]:Sp[u + 1]]] = True
+    return root
+
+
+def join(n, Sp, Sj, key, root):
+    """(agg int32[n], roots int32[nagg]) from the root set: the numbering and the two passes"""
+    r, c = edges(n, Sp, Sj)
+    roots = np.flatnonzero(root).astype(np.int32)
+    agg1 = np.full(n, -1, np.int64)
+    agg1[roots] = np.arange(len(roots))
+    valid = np.uint64(1 << 63)
+
+    def best(placed):
+        """per vertex the placed member of N(i) of greatest key as (found, vertex)"""
+        cand = np.zeros(n, np.uint64)
+        sel = placed[c]
+        np.maximum.at(cand, r[sel], valid | key[c[sel]])
+        return cand != 0, (cand & np.uint64(0x7FFFFFFF)).astype(np.int64)
+
+    found, who = best(root)                                          # pass 1
+    take = ~root & found
+    agg1[take] = agg1[who[take]]
+    placed = agg1 >= 0
+    found, who = best(placed)                                        # pass 2 reads pass 1's result only
+    agg = agg1.copy()
+    take = ~placed & found
+    agg[take] = agg1[who[take]]
+    agg[agg < 0] = 0                                                  # (cannot happen: every vertex has a placed neighbour)
+    return agg.astype(np.int32), roots
+
+
+def aggregate(n, Sp, Sj, seed=0, prio=None):
+    """(agg int32[n], nagg, roots int32[nagg], rounds): what bhs_csr_aggregate_device returns"""
+    if n == 0:
+        return np.zeros(0, np.int32), 0, np.zeros(0, np.int32), 0
+    key = keys(n, seed, prio)
+    root, nrounds = rounds(n, Sp, Sj, key)
+    agg, roots = join(n, Sp, Sj, key, root)
+    return agg, len(roots), roots, nrounds
+
+
+def invalid(n, nnzS, Sp, Sj, flags=0, has_agg=True, overlap=False):
+    """the reason the call refuses its arguments with BHS_ERR_INVALID_ARG, or None"""
+    if n < 0 or nnzS < 0:
+        return "negative size"
+    if flags != 0:
+        return "unknown flag"
+    if n > 0 and (Sp is None or not has_agg):
+        return "NULL array"
+    if nnzS > 0 and Sj is None:
+        return "NULL array"
+    if overlap:
+        return "an output overlaps an input"
+    Sp = np.asarray(Sp, np.int64)[:n + 1] if n > 0 else np.zeros(1, np.int64)
+    if n > 0 and (np.any(Sp < 0) or np.any(Sp > nnzS) or np.any(np.diff(Sp) < 0)):
+        return "bad row pointer"
+    if n > 0:
+        cols = np.asarray(Sj, np.int64)[Sp[0]:Sp[n]]
+        if np.any(cols < 0) or np.any(cols >= n):
+            return "column out of range"
+    return None
+
+
+# ---------------------------------------------------------------- structural properties of a result on a symmetric S
+def check_structure(n, Sp, Sj, agg, nagg, roots):
+    import scipy.sparse as sp
+    from scipy.sparse import csgraph
+    r, c = edges(n, Sp, Sj)
+    G = sp.csr_matrix((np.ones(len(r)), (r, c)), shape=(n, n))
+    G = ((G + sp.identity(n)) > 0).astype(np.float64).tocsr()
+    G2 = ((G @ G) > 0).tocsr()
+    roots = np.asarray(roots, np.int64)
+    assert len(roots) == nagg and np.all(np.diff(roots) > 0)
+    assert np.array_equal(agg[roots], np.arange(nagg))
+    assert agg.min() >= 0 and agg.max() < nagg
+    sub = G2[roots][:, roots]
+    assert sub.nnz == nagg, "two roots within two steps"             # only the diagonal
+    assert np.all(G2[np.arange(n), roots[agg]]), "a vertex beyond two steps of its root"
+    same = agg[r] == agg[c]
+    inside = sp.csr_matrix((np.ones(int(same.sum())), (r[same], c[same])), shape=(n, n))
+    ncomp, _ = csgraph.connected_components(inside, directed=False)
+    assert ncomp == nagg, "an aggregate is not connected"
+
+
+# ---------------------------------------------------------------- the hierarchy, in scipy
+def strength(A, theta):
+    """pattern of strong connections, symmetrised: the diagonal and every a_ij unless |a_ij| < theta * max_{k != i} |a_ik|, united with its transpose"""
+    import scipy.sparse as sp
+    A = sp.csr_matrix(A)
+    n = A.shape[0]
+    r = np.repeat(np.arange(n), np.diff(A.indptr))
+    diag = r == A.indices
+    rowmax = np.zeros(n)                                             # over the off-diagonal entries, as the selection takes it
+    np.maximum.at(rowmax, r[~diag], np.abs(A.data[~diag]))
+    keep = ~(np.abs(A.data) < theta * rowmax[r]) | diag
+    S = sp.csr_matrix((np.ones(int(keep.sum())), (r[keep], A.indices[keep])), shape=(n, n))
+    S = ((S + S.T) > 0).astype(np.float64).tocsr()
+    S.sort_indices()
+    return S
+
+
+def tentative(n, agg, nagg, cand=None):
+    """(T n x nagg, coarse candidate)"""
+    import scipy.sparse as sp
+    cand = np.ones(n) if cand is None else np.asarray(cand, np.float64)
+    nrm = np.sqrt(np.bincount(agg, weights=cand * cand, minlength=nagg))
+    T = sp.csr_matrix((cand / nrm[agg], agg, np.arange(n + 1)), shape=(n, nagg))
+    return T, nrm
+
+
+def _ones(M):
+    import scipy.sparse as sp
+    M = sp.csr_matrix(M)
+    return sp.csr_matrix((np.ones(M.nnz), M.indices, M.indptr), shape=M.shape)
+
+
+def on_pattern(M, pattern):
+    """M's values on the structural pattern of the operation that made it: scipy stores no sum that is exactly zero, the
+    library keeps every entry a product lands on (pattern: a matrix of positive entries with that structure)"""
+    import scipy.sparse as sp
+    M, pattern = sp.csr_matrix(M), sp.csr_matrix(pattern)
+    pattern.sort_indices()
+    r = np.repeat(np.arange(pattern.shape[0]), np.diff(pattern.indptr))
+    data = np.asarray(M[r, pattern.indices]).ravel() if pattern.nnz else np.zeros(0)
+    return sp.csr_matrix((data, pattern.indices, pattern.indptr), shape=M.shape)
+
+
+def sa_setup(A, theta=0.0, omega=2.0 / 3.0, max_levels=10, min_coarse=40, seed=0, aggregates=None):
+    """levels [(A_l, P_l, R_l)], the last with P = R = None, and the aggregate counts; aggregates: a list of (agg, nagg) a
+    level to use instead of this module's"""
+    import scipy.sparse as sp
+    A = sp.csr_matrix(A, dtype=np.float64)
+    levels, sizes = [], []
+    while len(levels) + 1 < max_levels and A.shape[0] > min_coarse:
+        n = A.shape[0]
+        if aggregates is not None:
+            agg, nagg = aggregates[len(levels)]
+        else:
+            S = strength(A, theta)
+            agg, nagg, _, _ = aggregate(n, S.indptr, S.indices, seed)
+        if nagg >= n:
+            break
+        T, _ = tentative(n, np.asarray(agg, np.int64), nagg)
+        Dinv = sp.diags(1.0 / A.diagonal())
+        P = on_pattern(T - omega * (Dinv @ A @ T), _ones(T) + _ones(A) @ _ones(T))
+        R = P.T.tocsr()
+        R.sort_indices()
+        levels.append((A, P, R))
+        sizes.append(nagg)
+        A = on_pattern(R @ (A @ P), _ones(R) @ (_ones(A) @ _ones(P)))
+    levels.append((A, None, None))
+    return levels, sizes
+
+
+def vcycle(levels, b, x, omega_jacobi=2.0 / 3.0, pre=1, post=1, lvl=0):
+    A, P, R = levels[lvl]
+    if P is None:
+        return np.linalg.solve(A.toarray(), b)
+    d = A.diagonal()
+    for _ in range(pre):
+        x = x + omega_jacobi * (b - A @ x) / d
+    xc = vcycle(levels, R @ (b - A @ x), np.zeros(P.shape[1]), omega_jacobi, pre, post, lvl + 1)
+    x = x + P @ xc
+    for _ in range(post):
+        x = x + omega_jacobi * (b - A @ x) / d
+    return x
+
+
+def solve(levels, b, tol=1e-8, maxiter=100):
+    """(x, cycles, residual norms)"""
+    A = levels[0][0]
+    x = np.zeros_like(b)
+    res = [np.linalg.norm(b - A @ x)]
+    cycles = 0
+    while res[-1] > tol * res[0] and cycles < maxiter:
+        x = vcycle(levels, b, x)
+        res.append(np.linalg.norm(b - A @ x))
+        cycles += 1
+    return x, cycles, res
+
+
+# ---------------------------------------------------------------- the test inputs (patterns with their symmetrisation)
+def symmetrise(n, Ap, Aj):
+    import scipy.sparse as sp
+    X = sp.csr_matrix((np.ones(len(Aj)), np.asarray(Aj), np.asarray(Ap)), shape=(n, n))
+    X = ((X + X.T) > 0).astype(np.float64).tocsr()
+    X.sort_indices()
+    return X.indptr.astype(np.int32), X.indices.astype(np.int32)
+
+
+def star(leaves):
+    """vertex 0 joined to every other; with the diagonal"""
+    import scipy.sparse as sp
+    n = leaves + 1
+    r = np.concatenate([np.zeros(leaves, np.int64), np.arange(1, n), np.arange(n)])
+    c = np.concatenate([np.arange(1, n), np.zeros(leaves, np.int64), np.arange(n)])
+    X = sp.csr_matrix((np.ones(len(r)), (r, c)), shape=(n, n))
+    X.sort_indices()
+    return n, X.indptr.astype(np.int32), X.indices.astype(np.int32)
+
+
+def two_cliques(k=70):
+    import scipy.sparse as sp
+    X = sp.block_diag([np.ones((k, k)), np.ones((k, k))]).tocsr()
+    X.sort_indices()
+    return 2 * k, X.indptr.astype(np.int32), X.indices.astype(np.int32)
+
+
+def poisson(name, nx, ny, nz=1):
+    """(n, Ap, Aj, Ax) with Poisson values: -1 off the diagonal, stencil size - 1 on it"""
+    from benchmark_spgemm_using_csr_amd import gallery
+    Ap, Aj = gallery.poisson_csr(name, nx, ny, nz)
+    n = len(Ap) - 1
+    r = np.repeat(np.arange(n), np.diff(Ap))
+    full = len(gallery.stencil_offsets(name))
+    Ax = np.where(r == Aj, float(full - 1), -1.0)
+    return n, np.asarray(Ap, np.int32), np.asarray(Aj, np.int32), Ax
+
+
+def gpu_cases():
+    """name -> (n, Sp, Sj): the symmetric patterns of tests/test_aggregate_gpu.py; the CPU test compares the two root sets
+    and checks the structure on the same list"""
+    from benchmark_spgemm_using_csr_amd import gallery
+    cases = {}
+    cases["one_with_diag"] = (1, np.array([0, 1], np.int32), np.array([0], np.int32))
+    cases["one_without_diag"] = (1, np.array([0, 0], np.int32), np.zeros(0, np.int32))
+    cases["two_one_edge"] = (2, np.array([0, 1, 2], np.int32), np.array([1, 0], np.int32))
+    for name, args in (("path300", ("poisson5pt", 300, 1)), ("poisson5pt_33", ("poisson5pt", 33, 33)),
+                       ("poisson9pt_20", ("poisson9pt", 20, 20)), ("poisson27pt_9", ("poisson27pt", 9, 9, 9))):
+        Ap, Aj = gallery.poisson_csr(*args)
+        cases[name] = (len(Ap) - 1, np.asarray(Ap, np.int32), np.asarray(Aj, np.int32))
+    Ap, Aj = gallery.uniform_csr(2048, 4, seed=7)
+    cases["uniform2048"] = (2048,) + symmetrise(2048, Ap, Aj)
+    Ap, Aj = gallery.powerlaw_csr(3000, 3000, 12000, 600, seed=11)
+    cases["powerlaw3000"] = (3000,) + symmetrise(3000, Ap, Aj)
+    Ap, Aj = gallery.roadlike_csr(40, 40)
+    cases["roadlike40"] = (1600, np.asarray(Ap, np.int32), np.asarray(Aj, np.int32))
+    cases["star1024"] = star(1024)
+    cases["two_k70"] = two_cliques(70)
+    return cases
