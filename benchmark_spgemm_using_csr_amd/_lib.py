@@ -55,6 +55,9 @@ BHS_SCALE_LEFT_DIV, BHS_SCALE_RIGHT_DIV = 1, 2
 # bhs_csr_spmv_semiring_device / bhs_csr_spmm_semiring_device (include/bhsparse_hip.h, "semiring CSR x dense")
 BHS_MV_ACCUM, BHS_MV_MASK_COMPLEMENT = 1, 2
 
+# bhs_csr_gs_device (include/bhsparse_hip.h, "colouring and relaxation")
+BHS_GS_FORWARD, BHS_GS_BACKWARD, BHS_GS_SYMMETRIC, BHS_GS_VERIFY = 1, 2, 3, 4
+
 
 # every symbol include/bhsparse_hip.h declares: (restype, argtypes)
 _vp, _i, _i64 = C.c_void_p, C.c_int, C.c_int64
@@ -116,6 +119,10 @@ SYMBOLS = {
                                           _vp, C.c_longlong, _vp, C.POINTER(_i), C.POINTER(C.c_longlong), C.POINTER(C.c_double)]),
     "bhs_csr_aggregate_device": (_i, [_vp, _i, _i, _vp, _vp, _vp, C.c_uint, _i, _vp, _vp, C.POINTER(_i), C.POINTER(_i),
                                       C.POINTER(C.c_double)]),
+    "bhs_csr_color_device": (_i, [_vp, _i, _i, _vp, _vp, _vp, C.c_uint, _i, _vp, _vp, _vp, C.POINTER(_i), C.POINTER(_i),
+                                  C.POINTER(C.c_double)]),
+    "bhs_csr_gs_device": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, C.c_double, _i, _i,
+                               C.POINTER(C.c_double)]),
     "bhs_strerror": (C.c_char_p, [_i]),
     "bhs_version": (C.c_char_p, []),
 }

@@ -1,6 +1,9 @@
 """A smoothed-aggregation multigrid setup that never leaves the device: MIS(2) aggregation (bhs_csr_aggregate_device;
 include/bhsparse_hip.h, "aggregation") and, built from it and the existing device calls of a `facade.bhsparse` handle, the
-strength pattern, the tentative and the smoothed prolongator, the Galerkin product, a V-cycle and a solver.
+strength pattern, the tentative and the smoothed prolongator, the Galerkin product, a V-cycle and a solver.  The cycle's
+smoother is weighted Jacobi or multicolour Gauss-Seidel on a device colouring (bhs_csr_color_device, bhs_csr_gs_device;
+"colouring and relaxation"); with forward sweeps before and backward sweeps after the coarse correction the cycle is
+symmetric and preconditions CG (pcg_device).
 
 Everything is a torch tensor on the handle's GPU: a matrix is (rowPtr int32, colInd int32, val), a pattern the first two.
 Functions of handles, not methods.  Every step is a thin call into the C-ABI; a missing library raises, nothing is computed
@@ -47,6 +50,72 @@ def aggregate_device(bh, n, S, seed=0, prio=None):
     torch.cuda.synchronize()                           # the library works on its own stream (see facade.initData_device)
     _check(aggregate_raw_device(bh, n, Sj.numel(), Sp, Sj, prio, seed, 0, agg, roots), "bhs_csr_aggregate_device")
     return agg[:n], bh.aggregate_nagg, roots[:bh.aggregate_nagg]
+
+
+# ---------------------------------------------------------------- colouring and relaxation
+def color_raw_device(bh, n, nnzS, d_rowPtrS, d_colIndS, d_prio, seed, flags, d_color, d_order, d_colorPtr):
+    """bhs_csr_color_device on caller-given arrays, the C arguments in order (d_prio may be None): the status code; sets
+    bh.color_ms, bh.color_ncolors and bh.color_rounds on success."""
+    if bh._h is None:
+        return _lib.BHS_ERR_NOT_READY
+    ncolors, rounds, ms = C.c_int(0), C.c_int(0), C.c_double(0)
+    err = bh._lib.bhs_csr_color_device(bh._h, int(n), int(nnzS), _ptr(d_rowPtrS), _ptr(d_colIndS), _ptr(d_prio),
+                                       int(seed) & 0xFFFFFFFF, int(flags), _ptr(d_color), _ptr(d_order), _ptr(d_colorPtr),
+                                       C.byref(ncolors), C.byref(rounds), C.byref(ms))
+    if err == _lib.BHS_SUCCESS:
+        bh.color_ms, bh.color_ncolors, bh.color_rounds = float(ms.value), int(ncolors.value), int(rounds.value)
+    return err
+
+
+def color_device(bh, n, S, seed=0, prio=None):
+    """The first-fit greedy colouring in descending key order of the n x n pattern S = (rowPtr, colInd[, anything]), torch
+    tensors on the handle's GPU; prio as in aggregate_device.  Returns (color int32[n], ncolors, order int32[n],
+    colorPtr_host): order holds the vertices by (colour, index), colorPtr_host is a numpy int32 array of ncolors + 1 offsets
+    into it, on the host, where bhs_csr_gs_device wants it.  bh.color_rounds and bh.color_ms hold the rounds and the device
+    time.  Raises BhsparseError on failure."""
+    import torch
+    Sp, Sj = S[0], S[1]
+    color = _alloc(n, torch.int32, Sp.device)
+    order = _alloc(n, torch.int32, Sp.device)
+    cptr = _alloc(n + 1, torch.int32, Sp.device)
+    torch.cuda.synchronize()                           # the library works on its own stream (see facade.initData_device)
+    _check(color_raw_device(bh, n, Sj.numel(), Sp, Sj, prio, seed, 0, color, order, cptr), "bhs_csr_color_device")
+    ncolors = bh.color_ncolors
+    cptr_host = cptr[:ncolors + 1].cpu().numpy().astype(np.int32) if n else np.zeros(1, np.int32)
+    return color[:n], ncolors, order[:n], cptr_host
+
+
+_GS_DIRECTIONS = {"forward": _lib.BHS_GS_FORWARD, "backward": _lib.BHS_GS_BACKWARD, "symmetric": _lib.BHS_GS_SYMMETRIC}
+
+
+def gs_raw_device(bh, n, nnzA, d_rowPtrA, d_colIndA, d_valA, d_diag, ncolors, h_colorPtr, d_order, d_color, d_b, d_x, omega,
+                  sweeps, flags):
+    """bhs_csr_gs_device on caller-given arrays, the C arguments in order (h_colorPtr: a numpy int32 array on the host;
+    d_color may be None without BHS_GS_VERIFY): the status code; sets bh.gs_ms on success."""
+    if bh._h is None:
+        return _lib.BHS_ERR_NOT_READY
+    ms = C.c_double(0)
+    hptr = None if h_colorPtr is None else np.ascontiguousarray(h_colorPtr, np.int32)
+    err = bh._lib.bhs_csr_gs_device(bh._h, int(n), int(nnzA), _ptr(d_rowPtrA), _ptr(d_colIndA), _ptr(d_valA), _ptr(d_diag),
+                                    int(ncolors), _ptr(hptr), _ptr(d_order), _ptr(d_color), _ptr(d_b), _ptr(d_x), float(omega),
+                                    int(sweeps), int(flags), C.byref(ms))
+    if err == _lib.BHS_SUCCESS:
+        bh.gs_ms = float(ms.value)
+    return err
+
+
+def gs_device(bh, A, diag, coloring, b, x, omega=1.0, sweeps=1, direction="symmetric", verify=False):
+    """`sweeps` multicolour Gauss-Seidel (omega == 1) or SOR sweeps on A x = b, IN PLACE on x: A = (rowPtr, colInd, val),
+    diag its diagonal, coloring what color_device returned, all torch tensors on the handle's GPU.  direction: "forward"
+    (colours ascending), "backward" or "symmetric" (forward then backward in each sweep); verify: the kernels check the
+    colouring against A as they go.  Returns x; bh.gs_ms holds the device time.  Raises BhsparseError on failure."""
+    import torch
+    color, ncolors, order, cptr = coloring
+    flags = _GS_DIRECTIONS[direction] | (_lib.BHS_GS_VERIFY if verify else 0)
+    torch.cuda.synchronize()                           # the library works on its own stream (see facade.initData_device)
+    _check(gs_raw_device(bh, _rows(A), A[1].numel(), A[0], A[1], A[2], diag, ncolors, cptr, order, color, b, x, omega, sweeps,
+                         flags), "bhs_csr_gs_device")
+    return x
 
 
 # ---------------------------------------------------------------- the pieces of a level
@@ -211,11 +280,30 @@ def _jacobi(bh, A, d, b, x, omega_jacobi, sweeps):
     return x
 
 
-def vcycle_device(bh, levels, b, x, omega_jacobi=2.0 / 3.0, pre=1, post=1, diagonals=None, lvl=0):
-    """One V(pre, post) cycle for A_0 x = b on the hierarchy of sa_setup_device: weighted Jacobi from csr_spmv_device
-    (y = alpha A x + beta y) and the diagonal, restriction and prolongation by R_l and P_l through csr_spmv_device, the
-    coarsest level by a dense torch.linalg.solve.  Returns the new x."""
+def smoother_setup_device(bh, levels, seed=0):
+    """What the Gauss-Seidel smoother needs of every level but the last: (diag(A_l), colouring of pattern(A_l) U
+    pattern(A_l^T)) -- the diagonal from csr_reduce_device, the pattern from strength_device(theta = 0), the colouring from
+    color_device with the hash of (vertex, seed).  A list to pass to vcycle_device / pcg_device as `smoothers`."""
+    out = []
+    for A, P, _ in levels:
+        if P is None:
+            continue
+        n = _rows(A)
+        d = bh.csr_reduce_device(n, n, A, _lib.BHS_AXIS_DIAG, _lib.BHS_RED_PLUS)
+        out.append((d, color_device(bh, n, strength_device(bh, n, A, 0.0), seed)))
+    return out
+
+
+def vcycle_device(bh, levels, b, x, omega_jacobi=2.0 / 3.0, pre=1, post=1, diagonals=None, lvl=0, smoother="jacobi",
+                  smoothers=None):
+    """One V(pre, post) cycle for A_0 x = b on the hierarchy of sa_setup_device: restriction and prolongation by R_l and P_l
+    through csr_spmv_device, the coarsest level by a dense torch.linalg.solve.  smoother "jacobi": weighted Jacobi from
+    csr_spmv_device (y = alpha A x + beta y) and the diagonal.  smoother "gs": `pre` forward multicolour Gauss-Seidel
+    sweeps before the coarse correction and `post` backward sweeps after it (gs_device; smoothers: what
+    smoother_setup_device returned, made here when None) -- a symmetric cycle where pre == post.  Returns the new x."""
     import torch
+    if smoother not in ("jacobi", "gs"):
+        raise ValueError("smoother is 'jacobi' or 'gs'")
     A, P, R = levels[lvl]
     n = _rows(A)
     if P is None:
@@ -223,14 +311,24 @@ def vcycle_device(bh, levels, b, x, omega_jacobi=2.0 / 3.0, pre=1, post=1, diago
         rows = torch.repeat_interleave(torch.arange(n, device=b.device), (A[0][1:] - A[0][:-1]).long())
         dense.index_put_((rows, A[1].long()), A[2], accumulate=True)
         return torch.linalg.solve(dense, b)
-    if diagonals is None:
+    gs = smoother == "gs"
+    if gs and smoothers is None:
+        smoothers = smoother_setup_device(bh, levels)
+    if not gs and diagonals is None:
         diagonals = _diagonals(bh, levels)
-    d, nc = diagonals[lvl], _rows(R)
-    x = _jacobi(bh, A, d, b, x, omega_jacobi, pre)
+    nc = _rows(R)
+    if gs:
+        d, coloring = smoothers[lvl]
+        x = gs_device(bh, A, d, coloring, b, x.clone(), 1.0, pre, "forward")
+    else:
+        d = diagonals[lvl]
+        x = _jacobi(bh, A, d, b, x, omega_jacobi, pre)
     r = csr_spmv_device(bh, n, n, A, x, alpha=-1.0, beta=1.0, y=b.clone())
     rc = csr_spmv_device(bh, nc, n, R, r)
-    xc = vcycle_device(bh, levels, rc, torch.zeros_like(rc), omega_jacobi, pre, post, diagonals, lvl + 1)
+    xc = vcycle_device(bh, levels, rc, torch.zeros_like(rc), omega_jacobi, pre, post, diagonals, lvl + 1, smoother, smoothers)
     x = csr_spmv_device(bh, n, nc, P, xc, alpha=1.0, beta=1.0, y=x.clone())
+    if gs:
+        return gs_device(bh, A, d, coloring, b, x, 1.0, post, "backward")
     return _jacobi(bh, A, d, b, x, omega_jacobi, post)
 
 
@@ -249,3 +347,31 @@ def solve_device(bh, levels, b, tol=1e-8, maxiter=100):
         res.append(float(torch.linalg.norm(r)))
         cycles += 1
     return x, cycles, res
+
+
+def pcg_device(bh, levels, b, tol=1e-8, maxiter=100, smoother="gs"):
+    """Conjugate gradients for A_0 x = b from x = 0, preconditioned with one V(1,1) cycle from zero (smoother "gs": forward
+    before and backward after, a symmetric operator; "jacobi" is symmetric too), until ||r|| <= tol ||b|| or maxiter
+    iterations.  The products with A_0 are csr_spmv_device, the dot products and updates torch's.  Returns (x, iterations,
+    residual norms): the norms of the recurrence's residual, the first ||b||."""
+    import torch
+    A = levels[0][0]
+    n = _rows(A)
+    smoothers = smoother_setup_device(bh, levels) if smoother == "gs" else None
+    diagonals = _diagonals(bh, levels) if smoother == "jacobi" else None
+    x = torch.zeros_like(b)
+    r = b.clone()
+    res = [float(torch.linalg.norm(r))]
+    p, rz, its = None, 0.0, 0
+    while res[-1] > tol * res[0] and its < maxiter:
+        z = vcycle_device(bh, levels, r, torch.zeros_like(r), diagonals=diagonals, smoother=smoother, smoothers=smoothers)
+        rz_new = float(torch.dot(r, z))
+        p = z if p is None else z + (rz_new / rz) * p
+        rz = rz_new
+        q = csr_spmv_device(bh, n, n, A, p)
+        alpha = rz / float(torch.dot(p, q))
+        x = x + alpha * p
+        r = r - alpha * q
+        res.append(float(torch.linalg.norm(r)))
+        its += 1
+    return x, its, res

@@ -403,6 +403,10 @@ struct bhs_handle {
     // aggregates in its queue buffer, the roots per bitmap word in its count buffer
     SideWs aggWs;
     DevBuf aggOff;                       // the scanned counts: every bitmap word's first root number
+    // the colouring and the Gauss-Seidel sweeps on it (bhs_host_color.inc.h): the rounds' second colour array in its queue
+    // buffer, the vertices per (colour, 64 vertices) in its count buffer
+    SideWs colWs;
+    DevBuf colOff;                       // the scanned counts: every (colour, 64 vertices)' first place in the order
 };
 
 namespace {
@@ -570,6 +574,7 @@ inline int one_launch(int rc) { return rc != BHS_SUCCESS ? rc : 1; }
 #include "bhs_host_spmv_sr.inc.h"
 #include "bhs_host_push_sr.inc.h"
 #include "bhs_host_aggregate.inc.h"
+#include "bhs_host_color.inc.h"
 #include "bhs_host_transpose.inc.h"
 #include "bhs_host_reduce.inc.h"
 #include "bhs_host_semiring.inc.h"

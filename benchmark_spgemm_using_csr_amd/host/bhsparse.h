@@ -126,6 +126,20 @@ public:
     int csr_aggregate_device(int n, int nnzS, const index_type *d_rowPtrS, const index_type *d_colIndS, const unsigned *d_prio,
                              unsigned seed, int flags, index_type *d_agg, index_type *d_roots, int *nagg_out, int *rounds_out);
 
+    // EXTENSION, not part of the reference's API: the first-fit greedy colouring in descending key order of an n x n pattern
+    // on DEVICE arrays (bhs_csr_color_device, include/bhsparse_hip.h, "colouring and relaxation"): d_color (n ints) receives
+    // every vertex's colour, d_order (n ints) the vertices by (colour, index), d_colorPtr (room for n + 1 ints) the
+    // *ncolors_out + 1 offsets of the colours into d_order.  d_prio may be 0: the hash of (vertex, seed); flags must be 0.
+    // csr_gs_device relaxes d_x in place with multicolour Gauss-Seidel / SOR sweeps on such a colouring (bhs_csr_gs_device):
+    // h_colorPtr is a HOST array of ncolors + 1 ints, d_diag the diagonal of A, flags BHS_GS_FORWARD, BHS_GS_BACKWARD or
+    // BHS_GS_SYMMETRIC, with BHS_GS_VERIFY (needs d_color, else it may be 0) to check the colouring.  Both need initPlatform only.
+    int csr_color_device(int n, int nnzS, const index_type *d_rowPtrS, const index_type *d_colIndS, const unsigned *d_prio,
+                         unsigned seed, int flags, index_type *d_color, index_type *d_order, index_type *d_colorPtr,
+                         int *ncolors_out, int *rounds_out);
+    int csr_gs_device(int n, int nnzA, const index_type *d_rowPtrA, const index_type *d_colIndA, const value_type *d_valA,
+                      const value_type *d_diag, int ncolors, const index_type *h_colorPtr, const index_type *d_order,
+                      const index_type *d_color, const value_type *d_b, value_type *d_x, double omega, int sweeps, int flags);
+
     // EXTENSION, not part of the reference's API: the multiply over a semiring (bhs_spgemm_semiring*, include/bhsparse_hip.h,
     // "semiring multiply"; semiring: a BHS_SR_* constant) on the data of initData.  spgemm_semiring is the full product: it
     // fills the csrRowPtrC of initData, and get_nnzC / get_C then return A (+).(x) B on the pattern of A·B.
@@ -324,6 +338,25 @@ inline int bhsparse::csr_aggregate_device(int n, int nnzS, const index_type *d_r
 {
     if (!_h) return BHS_ERR_NOT_READY;
     return bhs_csr_aggregate_device(_h, n, nnzS, d_rowPtrS, d_colIndS, d_prio, seed, flags, d_agg, d_roots, nagg_out, rounds_out, 0);
+}
+
+inline int bhsparse::csr_color_device(int n, int nnzS, const index_type *d_rowPtrS, const index_type *d_colIndS,
+                                      const unsigned *d_prio, unsigned seed, int flags, index_type *d_color,
+                                      index_type *d_order, index_type *d_colorPtr, int *ncolors_out, int *rounds_out)
+{
+    if (!_h) return BHS_ERR_NOT_READY;
+    return bhs_csr_color_device(_h, n, nnzS, d_rowPtrS, d_colIndS, d_prio, seed, flags, d_color, d_order, d_colorPtr, ncolors_out,
+                                rounds_out, 0);
+}
+
+inline int bhsparse::csr_gs_device(int n, int nnzA, const index_type *d_rowPtrA, const index_type *d_colIndA,
+                                   const value_type *d_valA, const value_type *d_diag, int ncolors, const index_type *h_colorPtr,
+                                   const index_type *d_order, const index_type *d_color, const value_type *d_b, value_type *d_x,
+                                   double omega, int sweeps, int flags)
+{
+    if (!_h) return BHS_ERR_NOT_READY;
+    return bhs_csr_gs_device(_h, n, nnzA, d_rowPtrA, d_colIndA, d_valA, d_diag, ncolors, h_colorPtr, d_order, d_color, d_b, d_x,
+                             omega, sweeps, flags, 0);
 }
 
 inline int bhsparse::get_nnzC()

@@ -811,6 +811,81 @@ BHS_API int bhs_get_C_device(bhs_handle *h, const int **d_rowPtrC, const int **d
 BHS_API int bhs_csr_sort_indices_device(bhs_handle *h, int n_row, const int *d_rowPtr, int *d_colInd,
                                         bhs_value_t *d_val);
 
+/* ---- colouring and relaxation ----------------------------------------------
+ * A greedy colouring of the vertices of an n x n pattern S, and multicolour Gauss-Seidel / SOR sweeps on a vector that use
+ * it: the smoother of a multigrid cycle, and a colouring for its own sake (no reference counterpart; bhs_color.hip.h,
+ * bhs_gs.hip.h).
+ *
+ * bhs_csr_color_device.  S is 0-based int32 CSR; values are NOT TAKEN, so the double and the float library run the same
+ *   code and give the same bits.
+ * Keys.  The aggregation's: prio31(i) << 31 | i, prio31(i) = d_prio[i] >> 1 where d_prio is given (the lowest bit of a
+ *   priority is dropped), else h >> 1 of the aggregation's hash of (i, seed).  Ties go by index.
+ * Result, as a definition: THE first-fit greedy colouring in descending key order.  Going through the vertices from the
+ *   greatest key down, vertex i gets the smallest colour >= 0 that no off-diagonal neighbour coloured before it holds.
+ *   Diagonal entries are ignored, repeated columns and the order inside a row make no difference; an isolated vertex gets
+ *   colour 0.  For a structurally symmetric S no two neighbours share a colour.
+ * Rounds.  Synchronous rounds, as the aggregation's: an uncoloured vertex whose key exceeds that of every uncoloured
+ *   off-diagonal neighbour takes its colour this round.  A round reads one colour array and writes another, never the one
+ *   it reads, so *rounds_out is a function of the input alone.  The host reads the error word, the count of uncoloured
+ *   vertices and the colours in use once a round, one round trip.  BHS_ERR_INTERNAL when a round colours nothing or after
+ *   n + 1 rounds; nothing spins on the device, nothing waits for another workgroup.
+ * Outputs.  d_color: n ints in [0, ncolors).  d_order: the n vertices sorted by (colour, index).  d_colorPtr: CAPACITY
+ *   n + 1 ints, of which ncolors + 1 are written: colour c is d_order[d_colorPtr[c] .. d_colorPtr[c + 1]).  The order is
+ *   built without atomics on results and in a number of launches that does not grow with n: the vertices per (colour, 64
+ *   vertices) are counted into a colour-major table, the library's one-pass scan turns it into places.  The table holds
+ *   ncolors * ceil(n / 64) ints; beyond 2^26 of them (256 MiB, and as much for the places) the call returns
+ *   BHS_ERR_ALLOC -- more than 2048 colours at n = 2^21.
+ * Non-symmetric S.  The call still ends and every colour is in [0, ncolors); which colouring results is unspecified.
+ * Validation, on the device, each check ahead of the dependent read: rowPtrS[i] > rowPtrS[i+1] or either outside
+ *   [0, nnzS]; a column outside [0, n).  On the host: a NULL handle, negative n or nnzS, flags != 0, a NULL d_rowPtrS,
+ *   d_color, d_order or d_colorPtr with n > 0, NULL d_colIndS with nnzS > 0, an output's footprint overlapping S, d_prio
+ *   or another output, and a call between bhs_spgemm_symbolic and bhs_spgemm_finish.  Each returns BHS_ERR_INVALID_ARG.
+ * n == 0 succeeds with *ncolors_out = 0 and *rounds_out = 0 and launches nothing.
+ * bhs_get_kernel_stats then reports color_round (the rounds, a row spread over 1, 4, 16 or 64 lanes by the pattern's mean
+ *   row length) and color_order (the count, the scan, the numbering).
+ *
+ * bhs_csr_gs_device.  In place on d_x.  For every colour in turn, one launch per non-empty colour over the rows
+ *   d_order[h_colorPtr[c] .. h_colorPtr[c + 1]):
+ *       s = sum over the entries with j != i of double(a_ij) * double(x_j), summed in double from +0 in an order that
+ *           depends on the row's length and the lanes per row alone (the SpMV's rule),
+ *       t = (double(b_i) - s) / double(d_i),
+ *       x_i = t where omega == 1, else x_i + omega * (t - x_i); one rounding to the value type; IEEE results where d_i is 0.
+ *   d_diag (n values, required) is d_i: the diagonal entries of A are skipped, not read.  h_colorPtr is a HOST array of
+ *   ncolors + 1 ints.  BHS_GS_FORWARD goes through the colours 0 .. ncolors - 1, BHS_GS_BACKWARD through them in reverse,
+ *   BHS_GS_SYMMETRIC forward then backward in each of the `sweeps` sweeps.  The kernel boundary is the only synchronisation.
+ * Listed rows.  Rows that are not listed are untouched; h_colorPtr[ncolors] <= n is allowed, so a caller can relax a subset.
+ * Validation.  On the host: h_colorPtr starts at 0, never falls and ends <= n; ncolors in [0, n]; sweeps >= 0; a direction
+ *   is given and no unknown flag; NULL arrays; d_x overlapping any input (A, d_diag, d_order, d_color, d_b); a call between
+ *   bhs_spgemm_symbolic and bhs_spgemm_finish.  On the device, ahead of the dependent read: every d_order entry, row bounds,
+ *   columns.  Each returns BHS_ERR_INVALID_ARG; after a refusal by the device x is unspecified.
+ * BHS_GS_VERIFY needs d_color (else it may be NULL): the kernels also check color[i] == c for each listed row and
+ *   color[j] != c for every off-diagonal entry read; a violation returns BHS_ERR_INVALID_ARG and leaves x unspecified.  It
+ *   is a template switch: the unverified path pays nothing.  WITHOUT it an improper colouring -- two rows of one colour
+ *   that share an entry -- gives values that depend on timing.
+ * Repeatability.  Given a proper colouring the result is a function of the arguments: the same bits from call to call and
+ *   from handle to handle.  One control round trip per call, at its end.  ms_out (may be NULL): device time of the call.
+ *   bhs_get_kernel_stats then reports gs_forward and gs_backward.                                                  */
+#define BHS_GS_FORWARD   1
+#define BHS_GS_BACKWARD  2
+#define BHS_GS_SYMMETRIC 3   /* forward then backward in each sweep */
+#define BHS_GS_VERIFY    4
+BHS_API int bhs_csr_color_device(bhs_handle *h, int n, int nnzS,
+        const int *d_rowPtrS, const int *d_colIndS /* n x n pattern; values are not taken */,
+        const unsigned *d_prio /* n caller priorities, or NULL: the hash */,
+        unsigned seed, int flags /* must be 0 */,
+        int *d_color /* out: n ints in [0, ncolors) */,
+        int *d_order /* out: the n vertices by (colour, index) */,
+        int *d_colorPtr /* out: capacity n + 1, ncolors + 1 written */,
+        int *ncolors_out /* may be NULL */, int *rounds_out /* may be NULL */, double *ms_out /* may be NULL */);
+BHS_API int bhs_csr_gs_device(bhs_handle *h, int n, int nnzA,
+        const int *d_rowPtrA, const int *d_colIndA, const bhs_value_t *d_valA,
+        const bhs_value_t *d_diag /* n values */,
+        int ncolors, const int *h_colorPtr /* HOST: ncolors + 1 ints */, const int *d_order,
+        const int *d_color /* may be NULL unless BHS_GS_VERIFY */,
+        const bhs_value_t *d_b, bhs_value_t *d_x /* in/out */,
+        double omega, int sweeps, int flags /* BHS_GS_FORWARD, _BACKWARD or _SYMMETRIC, | BHS_GS_VERIFY */,
+        double *ms_out /* may be NULL */);
+
 /* ---- measurement ----------------------------------------------------------
  * Per-kernel-family device times of the LAST bhs_spgemm (option "kernel_stats" = 1), measured with
  * hipEvents on the stream the kernels were launched on (what bench.py reports
