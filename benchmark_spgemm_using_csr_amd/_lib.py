@@ -58,6 +58,9 @@ BHS_MV_ACCUM, BHS_MV_MASK_COMPLEMENT = 1, 2
 # bhs_csr_gs_device (include/bhsparse_hip.h, "colouring and relaxation")
 BHS_GS_FORWARD, BHS_GS_BACKWARD, BHS_GS_SYMMETRIC, BHS_GS_VERIFY = 1, 2, 3, 4
 
+# bhs_csr_levels_device / bhs_csr_trsv_device (include/bhsparse_hip.h, "triangular solve and ILU(0)")
+BHS_TRI_LOWER, BHS_TRI_UPPER, BHS_TRI_UNIT_DIAG = 1, 2, 4
+
 
 # every symbol include/bhsparse_hip.h declares: (restype, argtypes)
 _vp, _i, _i64 = C.c_void_p, C.c_int, C.c_int64
@@ -123,6 +126,9 @@ SYMBOLS = {
                                   C.POINTER(C.c_double)]),
     "bhs_csr_gs_device": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, C.c_double, _i, _i,
                                C.POINTER(C.c_double)]),
+    "bhs_csr_levels_device": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(C.c_double)]),
+    "bhs_csr_trsv_device": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, C.c_double, _vp, _vp, _i, C.POINTER(C.c_double)]),
+    "bhs_csr_ilu0_device": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, C.POINTER(_i), C.POINTER(C.c_double)]),
     "bhs_strerror": (C.c_char_p, [_i]),
     "bhs_version": (C.c_char_p, []),
 }

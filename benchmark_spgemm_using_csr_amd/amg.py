@@ -3,7 +3,9 @@ include/bhsparse_hip.h, "aggregation") and, built from it and the existing devic
 strength pattern, the tentative and the smoothed prolongator, the Galerkin product, a V-cycle and a solver.  The cycle's
 smoother is weighted Jacobi or multicolour Gauss-Seidel on a device colouring (bhs_csr_color_device, bhs_csr_gs_device;
 "colouring and relaxation"); with forward sweeps before and backward sweeps after the coarse correction the cycle is
-symmetric and preconditions CG (pcg_device).
+symmetric and preconditions CG (pcg_device).  Beside it: the level sets of a triangle, the sparse triangular solve and
+ILU(0) in place (bhs_csr_levels_device, bhs_csr_trsv_device, bhs_csr_ilu0_device; "triangular solve and ILU(0)") and CG
+preconditioned with that factorisation in natural or colour order (ilu0_pcg_device).
 
 Everything is a torch tensor on the handle's GPU: a matrix is (rowPtr int32, colInd int32, val), a pattern the first two.
 Functions of handles, not methods.  Every step is a thin call into the C-ABI; a missing library raises, nothing is computed
@@ -365,6 +367,160 @@ def pcg_device(bh, levels, b, tol=1e-8, maxiter=100, smoother="gs"):
     p, rz, its = None, 0.0, 0
     while res[-1] > tol * res[0] and its < maxiter:
         z = vcycle_device(bh, levels, r, torch.zeros_like(r), diagonals=diagonals, smoother=smoother, smoothers=smoothers)
+        rz_new = float(torch.dot(r, z))
+        p = z if p is None else z + (rz_new / rz) * p
+        rz = rz_new
+        q = csr_spmv_device(bh, n, n, A, p)
+        alpha = rz / float(torch.dot(p, q))
+        x = x + alpha * p
+        r = r - alpha * q
+        res.append(float(torch.linalg.norm(r)))
+        its += 1
+    return x, its, res
+
+
+# ---------------------------------------------------------------- triangular solve and ILU(0)
+def levels_raw_device(bh, n, nnzA, d_rowPtrA, d_colIndA, flags, d_level, d_order, d_levelPtr):
+    """bhs_csr_levels_device on caller-given arrays, the C arguments in order: the status code; sets bh.levels_ms,
+    bh.levels_nlevels and bh.levels_passes (the passes depend on timing) on success."""
+    if bh._h is None:
+        return _lib.BHS_ERR_NOT_READY
+    nlevels, passes, ms = C.c_int(0), C.c_int(0), C.c_double(0)
+    err = bh._lib.bhs_csr_levels_device(bh._h, int(n), int(nnzA), _ptr(d_rowPtrA), _ptr(d_colIndA), int(flags), _ptr(d_level),
+                                        _ptr(d_order), _ptr(d_levelPtr), C.byref(nlevels), C.byref(passes), C.byref(ms))
+    if err == _lib.BHS_SUCCESS:
+        bh.levels_ms, bh.levels_nlevels, bh.levels_passes = float(ms.value), int(nlevels.value), int(passes.value)
+    return err
+
+
+def levels_device(bh, n, A, upper=False):
+    """The level sets of the lower (j < i) or upper (j > i) triangle of the n x n pattern A = (rowPtr, colInd[, anything]),
+    torch tensors on the handle's GPU: level(i) = 0 for a row without a counted entry, else 1 + the greatest level among
+    them.  Returns (level int32[n], nlevels, order int32[n], levelPtr_host): order holds the rows by (level, index),
+    levelPtr_host is a numpy int32 array of nlevels + 1 offsets into it, on the host, where bhs_csr_trsv_device and
+    bhs_csr_ilu0_device want it.  bh.levels_ms holds the device time.  Raises BhsparseError on failure."""
+    import torch
+    Ap, Aj = A[0], A[1]
+    level = _alloc(n, torch.int32, Ap.device)
+    order = _alloc(n, torch.int32, Ap.device)
+    lptr = _alloc(n + 1, torch.int32, Ap.device)
+    torch.cuda.synchronize()                           # the library works on its own stream (see facade.initData_device)
+    _check(levels_raw_device(bh, n, Aj.numel(), Ap, Aj, _lib.BHS_TRI_UPPER if upper else _lib.BHS_TRI_LOWER, level, order, lptr),
+           "bhs_csr_levels_device")
+    nlevels = bh.levels_nlevels
+    lptr_host = lptr[:nlevels + 1].cpu().numpy().astype(np.int32) if n else np.zeros(1, np.int32)
+    return level[:n], nlevels, order[:n], lptr_host
+
+
+def trsv_raw_device(bh, n, nnzA, d_rowPtrA, d_colIndA, d_valA, nlevels, h_levelPtr, d_order, alpha, d_b, d_x, flags):
+    """bhs_csr_trsv_device on caller-given arrays, the C arguments in order (h_levelPtr: a numpy int32 array on the host): the
+    status code; sets bh.trsv_ms on success."""
+    if bh._h is None:
+        return _lib.BHS_ERR_NOT_READY
+    ms = C.c_double(0)
+    hptr = None if h_levelPtr is None else np.ascontiguousarray(h_levelPtr, np.int32)
+    err = bh._lib.bhs_csr_trsv_device(bh._h, int(n), int(nnzA), _ptr(d_rowPtrA), _ptr(d_colIndA), _ptr(d_valA), int(nlevels),
+                                      _ptr(hptr), _ptr(d_order), float(alpha), _ptr(d_b), _ptr(d_x), int(flags), C.byref(ms))
+    if err == _lib.BHS_SUCCESS:
+        bh.trsv_ms = float(ms.value)
+    return err
+
+
+def trsv_device(bh, A, levels, b, x, alpha=1.0, upper=False, unit_diag=False):
+    """Solves T x = alpha b for T the lower or the upper triangle of A = (rowPtr, colInd, val) with its diagonal, read in
+    place; levels: what levels_device returned for that triangle; b and x torch tensors on the handle's GPU, x may be b
+    itself.  unit_diag: the diagonal is taken as 1 and diagonal entries are ignored.  Returns x; bh.trsv_ms holds the device
+    time.  Raises BhsparseError on failure."""
+    import torch
+    _, nlevels, order, lptr = levels
+    flags = (_lib.BHS_TRI_UPPER if upper else _lib.BHS_TRI_LOWER) | (_lib.BHS_TRI_UNIT_DIAG if unit_diag else 0)
+    torch.cuda.synchronize()                           # the library works on its own stream (see facade.initData_device)
+    _check(trsv_raw_device(bh, _rows(A), A[1].numel(), A[0], A[1], A[2], nlevels, lptr, order, alpha, b, x, flags),
+           "bhs_csr_trsv_device")
+    return x
+
+
+def ilu0_raw_device(bh, n, nnzA, d_rowPtrA, d_colIndA, d_valA, nlevels, h_levelPtr, d_order, flags):
+    """bhs_csr_ilu0_device on caller-given arrays, the C arguments in order (h_levelPtr: a numpy int32 array on the host): the
+    status code; sets bh.ilu0_ms and bh.ilu0_pivot (the smallest row with a zero or non-finite pivot, or -1) on success."""
+    if bh._h is None:
+        return _lib.BHS_ERR_NOT_READY
+    pivot, ms = C.c_int(-1), C.c_double(0)
+    hptr = None if h_levelPtr is None else np.ascontiguousarray(h_levelPtr, np.int32)
+    err = bh._lib.bhs_csr_ilu0_device(bh._h, int(n), int(nnzA), _ptr(d_rowPtrA), _ptr(d_colIndA), _ptr(d_valA), int(nlevels),
+                                      _ptr(hptr), _ptr(d_order), int(flags), C.byref(pivot), C.byref(ms))
+    if err == _lib.BHS_SUCCESS:
+        bh.ilu0_ms, bh.ilu0_pivot = float(ms.value), int(pivot.value)
+    return err
+
+
+def ilu0_device(bh, A, levels):
+    """A = L U on A's own pattern, IN PLACE on the values of A = (rowPtr, colInd, val) (rows strictly ascending, a diagonal
+    entry in every row); levels: what levels_device returned for the lower triangle.  Afterwards the entries with j < i
+    hold L (unit diagonal, not stored), those with j >= i hold U.  Returns A; bh.ilu0_pivot is the smallest row whose pivot
+    is 0 or not finite, or -1; bh.ilu0_ms the device time.  Raises BhsparseError on failure."""
+    import torch
+    _, nlevels, order, lptr = levels
+    torch.cuda.synchronize()                           # the library works on its own stream (see facade.initData_device)
+    _check(ilu0_raw_device(bh, _rows(A), A[1].numel(), A[0], A[1], A[2], nlevels, lptr, order, 0), "bhs_csr_ilu0_device")
+    return A
+
+
+def _permuted_device(bh, n, A, perm):
+    """A(perm, perm), rows ascending (csr_extract_device)"""
+    Zp, Zj, Zx, _ = bh.csr_extract_device(n, n, A, rows=perm, cols=perm)
+    return Zp, Zj, Zx
+
+
+def ilu0_setup_device(bh, A, ordering="natural", seed=0):
+    """The ILU(0) preconditioner of A = (rowPtr, colInd, val), rows strictly ascending.  ordering "natural": A as it is.
+    "colour": A permuted by (colour, index) of the colouring of pattern(A) U pattern(A^T) (strength_device(theta = 0),
+    color_device with the hash of (vertex, seed), csr_extract_device), whose triangles have as many levels as there are
+    colours.  Both triangles are analysed (levels_device), the values copied and factorised (ilu0_device).  Returns what
+    ilu0_apply_device needs: a dict with "LU" (rowPtr, colInd, val), "lower" and "upper" (the levels), "perm" (the
+    permutation as an int64 tensor, None for "natural"), "ncolors" and "pivot"."""
+    if ordering not in ("natural", "colour"):
+        raise ValueError("ordering is 'natural' or 'colour'")
+    n = _rows(A)
+    perm, ncolors = None, 0
+    if ordering == "colour":
+        _, ncolors, order, _ = color_device(bh, n, strength_device(bh, n, A, 0.0), seed)
+        A = _permuted_device(bh, n, A, order)
+        perm = order.long()
+    LU = (A[0], A[1], A[2].clone())
+    lower = levels_device(bh, n, LU)
+    upper = levels_device(bh, n, LU, upper=True)
+    ilu0_device(bh, LU, lower)
+    return {"LU": LU, "lower": lower, "upper": upper, "perm": perm, "ncolors": ncolors, "pivot": getattr(bh, "ilu0_pivot", -1)}
+
+
+def ilu0_apply_device(bh, M, r, z):
+    """z = (L U)^-1 r for M of ilu0_setup_device: r permuted where M has a permutation, the unit lower solve, the upper solve
+    in place, the result scattered back into z.  Returns z."""
+    perm = M["perm"]
+    y = r.clone() if perm is None else r[perm]
+    trsv_device(bh, M["LU"], M["lower"], y, y, unit_diag=True)
+    trsv_device(bh, M["LU"], M["upper"], y, y, upper=True)
+    if perm is None:
+        z.copy_(y)
+    else:
+        z[perm] = y
+    return z
+
+
+def ilu0_pcg_device(bh, A, b, tol=1e-8, maxiter=100, ordering="colour"):
+    """Conjugate gradients for A x = b from x = 0, preconditioned with ILU(0) of A in the given ordering
+    (ilu0_setup_device, ilu0_apply_device), until ||r|| <= tol ||b|| or maxiter iterations.  The products with A are
+    csr_spmv_device, the dot products and updates torch's.  Returns (x, iterations, residual norms) as pcg_device does."""
+    import torch
+    n = _rows(A)
+    M = ilu0_setup_device(bh, A, ordering)
+    x = torch.zeros_like(b)
+    r = b.clone()
+    res = [float(torch.linalg.norm(r))]
+    p, rz, its = None, 0.0, 0
+    while res[-1] > tol * res[0] and its < maxiter:
+        z = ilu0_apply_device(bh, M, r, torch.empty_like(r))
         rz_new = float(torch.dot(r, z))
         p = z if p is None else z + (rz_new / rz) * p
         rz = rz_new

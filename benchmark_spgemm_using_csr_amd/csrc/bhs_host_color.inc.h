@@ -15,7 +15,8 @@
 
 namespace {
 
-// the table of the order (ints): 256 MiB of counts and as much of offsets; beyond it bhs_csr_color_device returns BHS_ERR_ALLOC
+// the table of the order (ints): 256 MiB of counts and as much of offsets; beyond it bhs_csr_color_device and
+// bhs_csr_levels_device return BHS_ERR_ALLOC
 constexpr long long kCoMaxTable = 1ll << 26;
 
 struct CoIn {
@@ -56,11 +57,42 @@ int co_rounds(bhs_handle* h, const CoIn& in, int* first, int* second, int* ctl, 
     }
 }
 
+// The order of n vertices by (label, index) and every label's first place, for labels in [0, nlabels): the vertices per
+// (label, 64 vertices) counted into a label-major table in ws's count buffer, the library's one-pass scan over it, the
+// numbering -- three launches and a scan under the kernel record `name`, whatever n.  The colouring's colours and the level
+// sets' levels (bhs_host_trsv.inc.h) both come through here.  ws is prepared again with its ctlInts and queueBytes and the
+// table; the caller reads the error word and the total (AG_TOTAL == n) with its next round trip.
+int co_order(bhs_handle* h, SideWs& ws, const char* name, int ctlInts, size_t queueBytes, int n, long long nlabels, const int* label,
+             int* order, int* labelPtr)
+{
+    const size_t nWords = ((size_t)n + 63) / 64;
+    const long long table = nlabels * (long long)nWords;
+    if (table > kCoMaxTable) return BHS_ERR_ALLOC;
+    BHS_TRY(side_prepare(h, ws, ctlInts, queueBytes, (size_t)table + 1));
+    BHS_TRY(ensure(h, h->colOff, sizeof(int) * ((size_t)table + 1)));
+    int* ctl = (int*)ws.ctl.p;
+    int* cnt = (int*)ws.cnt.p;
+    int* off = (int*)h->colOff.p;
+    BHS_HIP(hipMemsetAsync(cnt, 0, sizeof(int) * (size_t)table, h->stream));
+    BHS_TRY(timed(h, name, n, [&] {
+        hipLaunchKernelGGL(k_col_count, dim3((unsigned)(((size_t)n + 255) / 256)), dim3(256), 0, h->stream, n, (int)nWords, (int)nlabels,
+                           label, cnt, ctl);
+        return 1;
+    }));
+    BHS_TRY(side_scan(h, ws, name, kAgScan, (int)table, off, off));
+    BHS_TRY(timed(h, name, 0, [&] {
+        hipLaunchKernelGGL(k_col_number, dim3((unsigned)(((size_t)n + 1 + 255) / 256)), dim3(256), 0, h->stream, n, (int)nWords, (int)nlabels,
+                           label, (const int*)off, order, labelPtr, ctl);
+        return 1;
+    }));
+    return BHS_SUCCESS;
+}
+
 int co_run(bhs_handle* h, const CoIn& in, int* ncolors_out, int* rounds_out, double* ms_out)
 {
     const AgDims& d = in.d;
     SideWs& ws = h->colWs;
-    const size_t n = (size_t)d.n, nWords = (n + 63) / 64;
+    const size_t n = (size_t)d.n;
     BHS_TRY(side_prepare(h, ws, CO_INTS, sizeof(int) * n, 0));
     int* ctl = (int*)ws.ctl.p;
     BHS_HIP(hipMemsetAsync(ctl, 0, sizeof(int) * CO_INTS, h->stream));
@@ -76,24 +108,7 @@ int co_run(bhs_handle* h, const CoIn& in, int* ncolors_out, int* rounds_out, dou
     if (last != in.color) BHS_HIP(hipMemcpyAsync(in.color, last, sizeof(int) * n, hipMemcpyDeviceToDevice, h->stream));
     const long long ncolors = ws.host[CO_NCOL];
     if (ncolors < 1 || ncolors > (long long)d.n) return BHS_ERR_INTERNAL;
-    const long long table = ncolors * (long long)nWords;
-    if (table > kCoMaxTable) return BHS_ERR_ALLOC;
-    BHS_TRY(side_prepare(h, ws, CO_INTS, sizeof(int) * n, (size_t)table + 1));
-    BHS_TRY(ensure(h, h->colOff, sizeof(int) * ((size_t)table + 1)));
-    int* cnt = (int*)ws.cnt.p;
-    int* off = (int*)h->colOff.p;
-    BHS_HIP(hipMemsetAsync(cnt, 0, sizeof(int) * (size_t)table, h->stream));
-    BHS_TRY(timed(h, "color_order", d.n, [&] {
-        hipLaunchKernelGGL(k_col_count, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, d.n, (int)nWords, (int)ncolors,
-                           (const int*)in.color, cnt, ctl);
-        return 1;
-    }));
-    BHS_TRY(side_scan(h, ws, "color_order", kAgScan, (int)table, off, off));
-    BHS_TRY(timed(h, "color_order", 0, [&] {
-        hipLaunchKernelGGL(k_col_number, dim3((unsigned)((n + 1 + 255) / 256)), dim3(256), 0, h->stream, d.n, (int)nWords, (int)ncolors,
-                           (const int*)in.color, (const int*)off, in.order, in.colorPtr, ctl);
-        return 1;
-    }));
+    BHS_TRY(co_order(h, ws, "color_order", CO_INTS, sizeof(int) * n, d.n, ncolors, in.color, in.order, in.colorPtr));
     BHS_TRY(side_end(h, ws));
     BHS_TRY(side_read_ctl(h, ws, CO_INTS));                           // the order's error word and total
     BHS_TRY(side_elapsed(h, ws, ms_out));

@@ -407,6 +407,8 @@ struct bhs_handle {
     // buffer, the vertices per (colour, 64 vertices) in its count buffer
     SideWs colWs;
     DevBuf colOff;                       // the scanned counts: every (colour, 64 vertices)' first place in the order
+    // the level sets, the triangular solve and ILU(0) (bhs_host_trsv.inc.h): the table of the levels' order in its count buffer
+    SideWs trsvWs;
 };
 
 namespace {
@@ -575,6 +577,7 @@ inline int one_launch(int rc) { return rc != BHS_SUCCESS ? rc : 1; }
 #include "bhs_host_push_sr.inc.h"
 #include "bhs_host_aggregate.inc.h"
 #include "bhs_host_color.inc.h"
+#include "bhs_host_trsv.inc.h"
 #include "bhs_host_transpose.inc.h"
 #include "bhs_host_reduce.inc.h"
 #include "bhs_host_semiring.inc.h"

@@ -140,6 +140,22 @@ public:
                       const value_type *d_diag, int ncolors, const index_type *h_colorPtr, const index_type *d_order,
                       const index_type *d_color, const value_type *d_b, value_type *d_x, double omega, int sweeps, int flags);
 
+    // EXTENSION, not part of the reference's API: the level sets of a triangle, the sparse triangular solve on them and ILU(0)
+    // in place, on DEVICE arrays (bhs_csr_levels_device, bhs_csr_trsv_device, bhs_csr_ilu0_device; include/bhsparse_hip.h,
+    // "triangular solve and ILU(0)").  csr_levels_device: flags BHS_TRI_LOWER or BHS_TRI_UPPER; d_level (n ints) receives
+    // every row's level, d_order (n ints) the rows by (level, index), d_levelPtr (room for n + 1 ints) the *nlevels_out + 1
+    // offsets of the levels into d_order; *passes_out depends on timing.  csr_trsv_device solves T x = alpha b for that
+    // triangle of A read in place (h_levelPtr is a HOST array of nlevels + 1 ints; flags the triangle, | BHS_TRI_UNIT_DIAG;
+    // d_x may be d_b).  csr_ilu0_device factorises A = L U on A's pattern in d_valA (the LOWER levels; flags must be 0);
+    // *pivot_out is the smallest row with a zero or non-finite pivot, or -1.  All need initPlatform only.
+    int csr_levels_device(int n, int nnzA, const index_type *d_rowPtrA, const index_type *d_colIndA, int flags,
+                          index_type *d_level, index_type *d_order, index_type *d_levelPtr, int *nlevels_out, int *passes_out);
+    int csr_trsv_device(int n, int nnzA, const index_type *d_rowPtrA, const index_type *d_colIndA, const value_type *d_valA,
+                        int nlevels, const index_type *h_levelPtr, const index_type *d_order, double alpha, const value_type *d_b,
+                        value_type *d_x, int flags);
+    int csr_ilu0_device(int n, int nnzA, const index_type *d_rowPtrA, const index_type *d_colIndA, value_type *d_valA,
+                        int nlevels, const index_type *h_levelPtr, const index_type *d_order, int flags, int *pivot_out);
+
     // EXTENSION, not part of the reference's API: the multiply over a semiring (bhs_spgemm_semiring*, include/bhsparse_hip.h,
     // "semiring multiply"; semiring: a BHS_SR_* constant) on the data of initData.  spgemm_semiring is the full product: it
     // fills the csrRowPtrC of initData, and get_nnzC / get_C then return A (+).(x) B on the pattern of A·B.
@@ -357,6 +373,30 @@ inline int bhsparse::csr_gs_device(int n, int nnzA, const index_type *d_rowPtrA,
     if (!_h) return BHS_ERR_NOT_READY;
     return bhs_csr_gs_device(_h, n, nnzA, d_rowPtrA, d_colIndA, d_valA, d_diag, ncolors, h_colorPtr, d_order, d_color, d_b, d_x,
                              omega, sweeps, flags, 0);
+}
+
+inline int bhsparse::csr_levels_device(int n, int nnzA, const index_type *d_rowPtrA, const index_type *d_colIndA, int flags,
+                                       index_type *d_level, index_type *d_order, index_type *d_levelPtr, int *nlevels_out,
+                                       int *passes_out)
+{
+    if (!_h) return BHS_ERR_NOT_READY;
+    return bhs_csr_levels_device(_h, n, nnzA, d_rowPtrA, d_colIndA, flags, d_level, d_order, d_levelPtr, nlevels_out, passes_out, 0);
+}
+
+inline int bhsparse::csr_trsv_device(int n, int nnzA, const index_type *d_rowPtrA, const index_type *d_colIndA,
+                                     const value_type *d_valA, int nlevels, const index_type *h_levelPtr,
+                                     const index_type *d_order, double alpha, const value_type *d_b, value_type *d_x, int flags)
+{
+    if (!_h) return BHS_ERR_NOT_READY;
+    return bhs_csr_trsv_device(_h, n, nnzA, d_rowPtrA, d_colIndA, d_valA, nlevels, h_levelPtr, d_order, alpha, d_b, d_x, flags, 0);
+}
+
+inline int bhsparse::csr_ilu0_device(int n, int nnzA, const index_type *d_rowPtrA, const index_type *d_colIndA, value_type *d_valA,
+                                     int nlevels, const index_type *h_levelPtr, const index_type *d_order, int flags,
+                                     int *pivot_out)
+{
+    if (!_h) return BHS_ERR_NOT_READY;
+    return bhs_csr_ilu0_device(_h, n, nnzA, d_rowPtrA, d_colIndA, d_valA, nlevels, h_levelPtr, d_order, flags, pivot_out, 0);
 }
 
 inline int bhsparse::get_nnzC()

@@ -1040,6 +1040,90 @@ BHS_API int bhs_expand_class_columns_device(void *stream, int n, int row0, const
 BHS_API const char *bhs_strerror(int status);
 BHS_API const char *bhs_version(void);
 
+/* ---- triangular solve and ILU(0) ---------------------------------------------
+ * The level sets of a triangle of an n x n pattern, the sparse triangular solve on them with the triangle read IN PLACE,
+ * and the incomplete factorisation A = L U on A's own pattern (no reference counterpart; bhs_trsv.hip.h, bhs_ilu0.hip.h).
+ * All three read 0-based int32 CSR on the device.  A triangle is never extracted: the caller passes the whole A, or one
+ * CSR that holds L and U as bhs_csr_ilu0_device leaves them.
+ *
+ * bhs_csr_levels_device.  Values are NOT TAKEN, so the double and the float library run the same code and give the same
+ *   bits.  flags is BHS_TRI_LOWER or BHS_TRI_UPPER, exactly one and nothing else.  LOWER counts the entries with j < i,
+ *   UPPER those with j > i; everything else, the diagonal included, is ignored.
+ * Result, as a definition: level(i) = 0 where row i has no counted entry, else 1 + the greatest level(j) over its counted
+ *   entries.  Repeated columns and the order inside a row make no difference: the result is a function of the pattern.
+ * Passes.  Monotone relaxation in place: levels start at 0, a pass sets level[i] = max(level[i], 1 + max level[j]); values
+ *   only rise and never pass the true level, so the fixed point is the definition however a pass's reads race with its
+ *   writes.  Rows go in ascending block order for LOWER and descending for UPPER, so one pass carries a level across many
+ *   rows.  The host launches 8 passes per control round trip and stops after a batch whose last pass raised nothing;
+ *   BHS_ERR_INTERNAL where more than n + 1 passes would be needed.  *passes_out, the passes launched, DEPENDS ON TIMING;
+ *   nothing else does.  Nothing spins on the device, nothing waits for another workgroup.
+ * Outputs.  d_level: n ints in [0, nlevels).  d_order: the n rows sorted by (level, index).  d_levelPtr: CAPACITY n + 1
+ *   ints, of which nlevels + 1 are written: level l is d_order[d_levelPtr[l] .. d_levelPtr[l + 1]).  The order is built as
+ *   the colouring's is, through a table of nlevels * ceil(n / 64) ints; beyond 2^26 of them the call returns
+ *   BHS_ERR_ALLOC -- a tridiagonal matrix of 2^20 rows is refused, and level scheduling would be pointless there.
+ * Validation, on the device, each check ahead of the dependent read: rowPtrA[i] > rowPtrA[i+1] or either outside
+ *   [0, nnzA]; a column outside [0, n).  On the host: a NULL handle, negative n or nnzA, flags other than one triangle, a
+ *   NULL d_rowPtrA, d_level, d_order or d_levelPtr with n > 0, NULL d_colIndA with nnzA > 0, an output's footprint
+ *   overlapping A or another output, and a call between bhs_spgemm_symbolic and bhs_spgemm_finish.  Each returns
+ *   BHS_ERR_INVALID_ARG.  n == 0 succeeds with *nlevels_out = 0 and *passes_out = 0 and launches nothing.
+ * bhs_get_kernel_stats then reports levels_pass (a row spread over 1, 4, 16 or 64 lanes by the mean row length) and
+ *   levels_order (the count, the scan, the numbering).
+ *
+ * bhs_csr_trsv_device.  Solves T x = alpha b for the rows listed, T the LOWER or UPPER triangle of A with its diagonal.
+ *   For every level in turn, ascending as h_levelPtr lists them, one launch per non-empty level over the rows
+ *   d_order[h_levelPtr[l] .. h_levelPtr[l + 1]):
+ *       s = sum over the triangle's off-diagonal entries of double(a_ij) * double(x_j), summed in double from +0 in an
+ *           order that depends on the row's length and the lanes per row alone (the SpMV's rule),
+ *       t = (alpha * double(b_i) - s) / double(a_ii); one rounding to the value type; IEEE results where a_ii is 0.
+ *   a_ii is the row's own FIRST entry with j == i; a listed row without one returns BHS_ERR_INVALID_ARG (found on the
+ *   device).  With BHS_TRI_UNIT_DIAG there is no division and diagonal entries are ignored.  h_levelPtr is a HOST array of
+ *   nlevels + 1 ints; the caller passes UPPER levels, from an UPPER analysis, for an UPPER solve.
+ * Aliasing.  d_x == d_b exactly is allowed: the solve is then in place.  Any other overlap of d_x with an input is refused.
+ * Listed rows.  Rows that are not listed are untouched; h_levelPtr[nlevels] <= n is allowed.
+ * Validation.  On the host: h_levelPtr starts at 0, never falls and ends <= n; nlevels in [0, n]; exactly one of
+ *   BHS_TRI_LOWER and BHS_TRI_UPPER and no unknown flag; NULL arrays; the overlaps above; a call between
+ *   bhs_spgemm_symbolic and bhs_spgemm_finish.  On the device, ahead of the dependent read: every d_order entry, row bounds,
+ *   columns, the diagonal.  Each returns BHS_ERR_INVALID_ARG; after a refusal by the device x is unspecified.
+ * Repeatability.  Given the levels of the pattern the result is a function of the arguments: the same bits from call to
+ *   call and from handle to handle.  With levels that are not the pattern's -- two rows of one level of which one reads
+ *   the other -- values depend on timing.  One control round trip per call, at its end.
+ *   bhs_get_kernel_stats then reports trsv_level.  (A run of thin levels is NOT fused into one launch of one workgroup:
+ *   measured, that was 3.4 to 4.8 times slower than a launch per level on poisson27pt 128^3 and poisson5pt 1024^2 in natural
+ *   order and no faster in colour order; profiles/trsv_case.md.)
+ *
+ * bhs_csr_ilu0_device.  A = L U on A's pattern, IN PLACE on d_valA.  Rows must be strictly ascending and every listed row
+ *   needs a diagonal entry; both are checked on the device and return BHS_ERR_INVALID_ARG.  h_levelPtr / d_order are the
+ *   LOWER levels of this pattern.  On return the entries with j < i hold L, whose unit diagonal is not stored, and the
+ *   entries with j >= i hold U: the two solves above, LOWER | UNIT_DIAG then UPPER, apply (L U)^-1 to a vector.
+ *   Row i, in its level's launch, for each of its entries k < i in ascending order:
+ *       l_ik = value_t(double(a_ik) / double(u_kk)),
+ *       a_ij = value_t(double(a_ij) - double(l_ik) * double(u_kj)) for every entry j > k of row i that row k also holds.
+ *   Owner computes: a row takes 1, 4, 16 or 64 lanes of one wave, every entry of the row has one lane that alone reads and
+ *   writes it, rows of earlier levels are final by the kernel boundary -- the result is a function of the input.
+ * Pivots.  *pivot_out (may be NULL) is the smallest listed row whose pivot u_ii is 0 or not finite, or -1; the call still
+ *   returns BHS_SUCCESS and the values follow IEEE.  flags must be 0.  d_valA overlapping another argument is refused.
+ *   One control round trip per call, at its end.  bhs_get_kernel_stats then reports ilu0_level.
+ * ms_out (may be NULL) of all three: device time of the call.                                                        */
+#define BHS_TRI_LOWER     1
+#define BHS_TRI_UPPER     2
+#define BHS_TRI_UNIT_DIAG 4
+BHS_API int bhs_csr_levels_device(bhs_handle *h, int n, int nnzA,
+        const int *d_rowPtrA, const int *d_colIndA /* n x n pattern; values are not taken */,
+        int flags /* BHS_TRI_LOWER or BHS_TRI_UPPER */,
+        int *d_level /* out: n ints in [0, nlevels) */,
+        int *d_order /* out: the n rows by (level, index) */,
+        int *d_levelPtr /* out: capacity n + 1, nlevels + 1 written */,
+        int *nlevels_out /* may be NULL */, int *passes_out /* may be NULL; depends on timing */, double *ms_out /* may be NULL */);
+BHS_API int bhs_csr_trsv_device(bhs_handle *h, int n, int nnzA,
+        const int *d_rowPtrA, const int *d_colIndA, const bhs_value_t *d_valA,
+        int nlevels, const int *h_levelPtr /* HOST: nlevels + 1 ints */, const int *d_order,
+        double alpha, const bhs_value_t *d_b, bhs_value_t *d_x /* out; may be d_b itself */,
+        int flags /* BHS_TRI_LOWER or BHS_TRI_UPPER, | BHS_TRI_UNIT_DIAG */, double *ms_out /* may be NULL */);
+BHS_API int bhs_csr_ilu0_device(bhs_handle *h, int n, int nnzA,
+        const int *d_rowPtrA, const int *d_colIndA, bhs_value_t *d_valA /* in/out */,
+        int nlevels, const int *h_levelPtr /* HOST: the LOWER levels */, const int *d_order,
+        int flags /* must be 0 */, int *pivot_out /* may be NULL */, double *ms_out /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif
