@@ -25,17 +25,28 @@ import numpy as np
 import pytest
 import torch
 
+import aggref
 import extractref
+import gsref
+import pushref
 import reduceref as rr
 import selectref as sr
 import semiringref
+import spmvref
+import spmvsrref
 import test_add_gpu as addt
+import test_aggregate_gpu as aggt
+import test_gs_gpu as gst
+import test_push_sr_gpu as pusht
+import test_spmv_gpu as spmvt
+import test_spmv_sr_gpu as srt
+import test_trsv_gpu as trsvt
 import test_values_gpu as vals
 import transposeref
 from helpers import poisson_case, random_csr, real_values
 from valuecheck import check_bounded, on_pattern
 
-from benchmark_spgemm_using_csr_amd import _lib, gallery
+from benchmark_spgemm_using_csr_amd import _lib, amg, gallery
 from benchmark_spgemm_using_csr_amd import facade as bhmod
 
 pytestmark = pytest.mark.gpu
@@ -524,31 +535,133 @@ def op_csr_scale(oracle, bh, data, size, what):
     _same_exactly(got.cpu().numpy(), want, what)
 
 
+# the CSR x dense products, the push product, the aggregation, the colouring with its sweep and the levels with the solve
+# and ILU(0): workspaces of their own on the handle, each exact against its numpy restatement of tests/
+def _same_bits(got, ref, what):
+    assert semiringref.same_bits(np.asarray(got).astype(np.float64), np.asarray(ref, np.float64)), what
+
+
+def _dense_ints(rows, k, seed):
+    return np.random.default_rng(seed).integers(-9, 10, (rows, k)).astype(np.float64)
+
+
+def op_spmv_spmm(oracle, bh, data, size, what):
+    m, n, X = _unrelated(size)
+    D = _cached(("spmv dev", size, bh._vdt), lambda: spmvt.Dev(m, n, X, bh._vdt))
+    for k in (1, 3):
+        V, Y = _dense_ints(n, k, 20 + k), _dense_ints(m, k, 30 + k)
+        want = _cached(("spmm", size, k), lambda: spmvref.spmm(m, n, X[0], X[1], X[2], V, 2.0, -1.0, Y)[0])
+        _same_exactly(spmvt.run(bh, D, V, 2.0, -1.0, Y, what=what), want.astype(bh._vdt), (what, k))
+
+
+def op_spmv_semiring(oracle, bh, data, size, what):
+    m, n, X = _unrelated(size)
+    D = _cached(("spmv dev", size, bh._vdt), lambda: spmvt.Dev(m, n, X, bh._vdt))
+    k = 4 if size == "large" else 1
+    V, Y = _dense_ints(n, k, 41), np.where(_dense_ints(m, k, 42) < 0, np.inf, _dense_ints(m, k, 43))
+    want = _cached(("srmv", size), lambda: spmvsrref.spmm_semiring("min_plus", m, n, X[0], X[1], X[2], V, Y, None, True))
+    got, changed = srt.run(bh, "min_plus", D, V, Y, None, True, what=what)
+    _same_bits(got, want[0], what)
+    assert changed == want[1], (what, changed, want[1])
+
+
+def op_push(oracle, bh, data, size, what):
+    m, n, G = _unrelated(size)
+    D = _cached(("push dev", size, bh._vdt), lambda: pusht.Dev(m, n, G, bh._vdt))
+    rng = np.random.default_rng(44)
+    k, nf = (4, 200) if size == "large" else (1, 10)
+    fidx = rng.integers(0, m, nf)
+    fidx[:3] = (3, 3, m - 1)                                          # (the large shape's 1500-entry row, twice)
+    F = rng.integers(0, 20, (nf, k)).astype(np.float64)
+    Y = np.where(rng.random((n, k)) < 0.5, np.inf, rng.integers(0, 30, (n, k)).astype(np.float64))
+    want = _cached(("push", size), lambda: pushref.push_semiring("min_plus", m, n, G[0], G[1], G[2], fidx, F, Y))
+    got, changed, nxt = pusht.run(bh, "min_plus", D, fidx, F, Y, what=what)
+    _same_bits(got, want[0], what)
+    assert changed == want[1] and np.array_equal(nxt, want[2]), (what, changed, want[1])
+
+
+def op_aggregate(oracle, bh, data, size, what):
+    name = "uniform2048" if size == "large" else "two_one_edge"
+    n, Sp, Sj = aggt.cases()[name]
+    aggt.check(aggt.run(bh, n, Sp, Sj, 1, what=what), aggt.reference(name, 1), what)
+
+
+def _poisson_sweep(size):
+    """(n, Ap, Aj, Ax, b, x0, the restatement's colouring with seed 0 and its forward sweep): poisson5pt (diagonal 4, -1 beside
+    it) on integers, every value an integer over 4^colours of fewer than 24 bits -- exact in both builds
+    (test_gs_gpu.test_sweep_bit_for_bit_on_dyadic_values)"""
+    def make():
+        n, Ap, Aj, Ax = aggref.poisson("poisson5pt", *((33, 33) if size == "large" else (7, 5)))
+        rng = np.random.default_rng(45)
+        b, x0 = rng.integers(-8, 9, n).astype(np.float64), rng.integers(-8, 9, n).astype(np.float64)
+        col = gsref.colouring(n, Ap, Aj, 0)
+        want = gsref.sweep(Ap, Aj, Ax, np.full(n, 4.0), col[3], col[2], b, x0, 1.0, 1, gsref.FORWARD)
+        scaled = want * 4.0 ** col[1]
+        assert col[1] <= 5 and np.array_equal(scaled, np.round(scaled)) and np.abs(scaled).max() < 2.0 ** 24
+        return n, Ap, Aj, Ax, b, x0, col, want
+    return _cached(("poisson sweep", size), make)
+
+
+def op_color_sweep(oracle, bh, data, size, what):
+    """the sweep runs on the device arrays the colouring has just returned"""
+    n, Ap, Aj, Ax, b, x0, col, want = _poisson_sweep(size)
+    A = (up(Ap, np.int32), up(Aj, np.int32), up(Ax, bh._vdt))
+    color, ncolors, order, cptr = amg.color_device(bh, n, A, 0)
+    gst.color_check((color.cpu().numpy(), ncolors, order.cpu().numpy(), cptr, bh.color_rounds), col, what)
+    x = amg.gs_device(bh, A, up(np.full(n, 4.0), bh._vdt), (color, ncolors, order, cptr), up(b, bh._vdt), up(x0, bh._vdt),
+                      direction="forward", verify=True)
+    _same_exactly(x.cpu().numpy(), want.astype(bh._vdt), what)
+
+
+def op_levels_solve_ilu(oracle, bh, data, size, what):
+    """the levels of both triangles, the lower solve on the device arrays the levels call returned, ILU(0)"""
+    name = "uniform2048" if size == "large" else "path300"
+    n, Ap, Aj, Ax, xs, bl, bu = trsvt.exact_case(name)
+    A = (up(Ap, np.int32), up(Aj, np.int32), up(Ax, bh._vdt))
+    lev = amg.levels_device(bh, n, A)
+    want = trsvt.level_reference(name, False, True)
+    trsvt.levels_check((lev[0].cpu().numpy(), lev[1], lev[2].cpu().numpy(), lev[3], bh.levels_passes), want, what)
+    trsvt.levels_check(trsvt.levels_run(bh, n, Ap, Aj, _lib.BHS_TRI_UPPER, what=what), trsvt.level_reference(name, True, True), what)
+    x = amg.trsv_device(bh, A, lev, up(bl, bh._vdt), up(np.zeros(n), bh._vdt), alpha=0.5)
+    _same_exactly(x.cpu().numpy(), xs.astype(bh._vdt), what)
+    fname = "two_dense70" if size == "large" else "arrow200"
+    fn, Fp, Fj, Fx, factors = trsvt.factor_case(fname)
+    T = _cached(("tri", fname, bh._vdt), lambda: trsvt.Tri(fn, Fp, Fj, Fx, bh._vdt))
+    got, pivot = trsvt.ilu_run(bh, T, what=what)
+    assert pivot == -1 and np.array_equal(got, factors), (what, pivot)
+
+
 OPERATIONS = [op_masked, op_semiring_masked, op_spgemm_add, op_spgemm_select, op_csr_add, op_csr_select, op_csr_transpose,
-              op_csr_extract, op_csr_reduce, op_csr_scale]
+              op_csr_extract, op_csr_reduce, op_csr_scale, op_spmv_spmm, op_spmv_semiring, op_push, op_aggregate, op_color_sweep,
+              op_levels_solve_ilu]
+OPS_A_STATION = 4
 
 
 @pytest.mark.parametrize("build", sorted(BUILDS))
 def test_tour_with_operations(oracle, build):
-    """The path_flips order with another operation of the handle after each data set's first multiply: station i runs
-    operation i and operation i + 5 (of ten), each operation on a large shape at one call and a small one at its next, so
-    that its own pool grows and is then reused oversized; the multiplies after it are checked like every other."""
+    """The path_flips order with other operations of the handle after each data set's first multiply: station i runs the
+    four operations from 4 i on (of sixteen, in a circle), each operation on a large shape at one call and a small one at
+    its next, so that its own pool grows and is then reused oversized; the multiplies after them are checked like every
+    other.  Nine stations: every operation runs at least twice, once large and once small."""
     oracle = memo(oracle)
     bh = new_handle(build)
-    calls = {}
+    calls, sizes = {}, {}
+    nops = len(OPERATIONS)
     try:
         for i, name in enumerate(ORDERS["path_flips"]):
             def between(data, kind, i=i, name=name):
                 if kind != "int":                                       # (the operations' references are exact on integers)
                     return
-                for j in (i % 10, (i + 5) % 10):
+                for j in [(OPS_A_STATION * i + t) % nops for t in range(OPS_A_STATION)]:
                     op = OPERATIONS[j]
                     calls[j] = calls.get(j, j) + 1                      # (even operations start large, odd ones small)
                     size = "large" if calls[j] % 2 else "small"
+                    sizes.setdefault(j, set()).add(size)
                     op(oracle, bh, data, size, "%s %s after %s[%d] %s" % (op.__name__, size, name, i, build))
                     torch.cuda.synchronize()
             visit(oracle, bh, name, build, between=between, what="operations[%d] " % i)
-        assert set(calls) == set(range(10))
+        assert set(calls) == set(range(nops))
+        assert all(sizes[j] == {"large", "small"} for j in range(nops)), sizes
         assert bh.free_mem() == 0
     finally:
         bh.freePlatform()
