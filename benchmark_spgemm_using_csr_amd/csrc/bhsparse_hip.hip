@@ -409,6 +409,9 @@ struct bhs_handle {
     DevBuf colOff;                       // the scanned counts: every (colour, 64 vertices)' first place in the order
     // the level sets, the triangular solve and ILU(0) (bhs_host_trsv.inc.h): the table of the levels' order in its count buffer
     SideWs trsvWs;
+    // the connected components (bhs_host_components.inc.h): the root bitmap and the scanned offsets in its queue buffer, the
+    // roots per bitmap word in its count buffer
+    SideWs ccWs;
 };
 
 namespace {
@@ -578,6 +581,7 @@ inline int one_launch(int rc) { return rc != BHS_SUCCESS ? rc : 1; }
 #include "bhs_host_aggregate.inc.h"
 #include "bhs_host_color.inc.h"
 #include "bhs_host_trsv.inc.h"
+#include "bhs_host_components.inc.h"
 #include "bhs_host_transpose.inc.h"
 #include "bhs_host_reduce.inc.h"
 #include "bhs_host_semiring.inc.h"

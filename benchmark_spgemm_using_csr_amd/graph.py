@@ -9,12 +9,18 @@ A(i, j) an edge i -> j -- transpose first (facade.csr_transpose, bhsparse.csr_tr
 The *_frontier_* functions give the same results and choose a direction per step: a step whose frontier is small goes by
 push (dense.csr_push_semiring_device; "sparse frontier x CSR"), which reads the out-edges of the frontier's vertices and
 nothing else, a step whose frontier is large by the pull call above.  On a graph of high diameter -- a road network, a mesh,
-a banded matrix -- that is the difference between touching every edge once and touching every edge once per level."""
+a banded matrix -- that is the difference between touching every edge once and touching every edge once per level.
+
+components_* answer which vertices belong together, for all components at once and whatever the direction of the entries
+(bhs_csr_components_device; "connected components"): the passes grow like the logarithm of the diameter, not like the
+diameter."""
+import ctypes as C
+
 import numpy as np
 
 from . import _lib
 from .dense import csr_push_semiring_device, csr_spmm_semiring_device
-from .facade import BhsparseError, _device_csr, _handle
+from .facade import BhsparseError, _alloc, _check, _device_csr, _handle, _host, _ptr, extract_csr
 
 
 def _sources(sources, n):
@@ -237,6 +243,67 @@ def _sssp_frontier(bh, n, A, sources, At=None, max_rounds=None, push_below=None)
             return D, rounds, ms, pushes
     why = "a cycle of negative weight" if rounds >= n else "max_rounds is below the number of vertices: no verdict on a negative cycle"
     raise BhsparseError("sssp_frontier_device: still changing after %d rounds (%s)" % (rounds, why), _lib.BHS_ERR_INVALID_ARG)
+
+
+# ---------------------------------------------------------------- connected components
+def components_raw_device(bh, n, nnz, dAp, dAj, flags, root, comp, size):
+    """bhs_csr_components_device on caller-given arrays, the C arguments in order (comp and size may be None): the status
+    code; sets bh.components_ncomp, bh.components_passes (the passes depend on timing) and bh.components_ms on success
+    only."""
+    if bh._h is None:
+        return _lib.BHS_ERR_NOT_READY
+    ncomp, passes, ms = C.c_int(0), C.c_int(0), C.c_double(0)
+    err = bh._lib.bhs_csr_components_device(bh._h, int(n), int(nnz), _ptr(dAp), _ptr(dAj), int(flags), _ptr(root), _ptr(comp),
+                                            _ptr(size), C.byref(ncomp), C.byref(passes), C.byref(ms))
+    if err == _lib.BHS_SUCCESS:
+        bh.components_ncomp, bh.components_passes, bh.components_ms = int(ncomp.value), int(passes.value), float(ms.value)
+    return err
+
+
+def components_device(bh, n, A):
+    """The connected components of the n-vertex pattern A = (rowPtr, colInd[, anything]), torch tensors on the handle's GPU:
+    i and j are joined where A stores (i, j) or (j, i), so A need not be symmetric; values are not taken.  Returns (root
+    int32[n], comp int32[n], sizes int32[ncomp]) as device tensors: the smallest vertex of i's component, the component's
+    number by ascending root, and the components' sizes.  bh.components_ncomp, bh.components_passes and bh.components_ms
+    hold the count, the passes and the device time.  Raises BhsparseError on failure."""
+    import torch
+    Ap, Aj = A[0], A[1]
+    root, comp, size = (_alloc(n, torch.int32, Ap.device) for _ in range(3))
+    torch.cuda.synchronize()                           # the library works on its own stream (see facade.initData_device)
+    _check(components_raw_device(bh, n, Aj.numel(), Ap, Aj if Aj.numel() else None, 0, root, comp, size),
+           "bhs_csr_components_device")
+    return root[:n], comp[:n], size[:bh.components_ncomp]
+
+
+def component_lists_device(bh, n, comp, ncomp):
+    """The vertices by (component, index) from components_device's comp: (order int32[n], compPtr int32[ncomp + 1]) as device
+    tensors, component c is order[compPtr[c] : compPtr[c + 1]].  The handle's stable transpose of the n x ncomp membership
+    pattern (rowPtr = 0 .. n, colInd = comp, no values): T's columns are the order, T's row pointer the offsets."""
+    import torch
+    rowptr = torch.arange(n + 1, dtype=torch.int32, device=comp.device)
+    Tp, Tj, _, _ = bh.csr_transpose_device(n, ncomp, (rowptr, comp, None), values=False)
+    return Tj, Tp
+
+
+def components_csr(n, Ap, Aj, device=0):
+    """Convenience: components_device once on host CSR arrays.  Returns numpy (root int32[n], comp int32[n], sizes
+    int32[ncomp])."""
+    A = _device_csr(Ap, Aj, None, np.float64, device)
+    with _handle(np.float64, device, None) as bh:
+        return _host(*components_device(bh, n, A))
+
+
+def largest_component_csr(n, Ap, Aj, Ax, value_dtype=np.float64, device=0):
+    """Convenience: the largest connected component of the n x n matrix (Ap, Aj, Ax) on host CSR arrays -- of the greatest
+    size, ties to the smaller root.  Returns (vertices int32[size] ascending, (Zp, Zj, Zx)): Z = A(vertices, vertices)
+    through facade.extract_csr."""
+    _, comp, sizes = components_csr(n, Ap, Aj, device=device)
+    if n == 0:
+        return np.zeros(0, np.int32), (np.zeros(1, np.int32), np.zeros(0, np.int32), np.zeros(0, value_dtype))
+    c = int(np.argmax(sizes))                                         # (the first of equal sizes: components are numbered by ascending root)
+    vertices = np.flatnonzero(comp == c).astype(np.int32)
+    Zp, Zj, Zx, _ = extract_csr(n, n, Ap, Aj, Ax, rows=vertices, cols=vertices, value_dtype=value_dtype, device=device)
+    return vertices, (Zp, Zj, Zx)
 
 
 def bfs_levels_csr(n, Ap, Aj, Ax, sources, value_dtype=np.float64, device=0):

@@ -156,6 +156,14 @@ public:
     int csr_ilu0_device(int n, int nnzA, const index_type *d_rowPtrA, const index_type *d_colIndA, value_type *d_valA,
                         int nlevels, const index_type *h_levelPtr, const index_type *d_order, int flags, int *pivot_out);
 
+    // EXTENSION, not part of the reference's API: the connected components of an n x n pattern S on DEVICE arrays, weakly
+    // (bhs_csr_components_device; include/bhsparse_hip.h, "connected components").  d_root (n ints) receives the smallest
+    // vertex of every vertex's component, d_comp (n ints, may be null) the component's number by ascending root, d_compSize
+    // (room for n ints, may be null, needs d_comp) the *ncomp_out sizes; *passes_out depends on timing.  flags must be 0.
+    // Needs initPlatform only.
+    int csr_components_device(int n, int nnzS, const index_type *d_rowPtrS, const index_type *d_colIndS, int flags,
+                              index_type *d_root, index_type *d_comp, index_type *d_compSize, int *ncomp_out, int *passes_out);
+
     // EXTENSION, not part of the reference's API: the multiply over a semiring (bhs_spgemm_semiring*, include/bhsparse_hip.h,
     // "semiring multiply"; semiring: a BHS_SR_* constant) on the data of initData.  spgemm_semiring is the full product: it
     // fills the csrRowPtrC of initData, and get_nnzC / get_C then return A (+).(x) B on the pattern of A·B.
@@ -397,6 +405,14 @@ inline int bhsparse::csr_ilu0_device(int n, int nnzA, const index_type *d_rowPtr
 {
     if (!_h) return BHS_ERR_NOT_READY;
     return bhs_csr_ilu0_device(_h, n, nnzA, d_rowPtrA, d_colIndA, d_valA, nlevels, h_levelPtr, d_order, flags, pivot_out, 0);
+}
+
+inline int bhsparse::csr_components_device(int n, int nnzS, const index_type *d_rowPtrS, const index_type *d_colIndS, int flags,
+                                           index_type *d_root, index_type *d_comp, index_type *d_compSize, int *ncomp_out,
+                                           int *passes_out)
+{
+    if (!_h) return BHS_ERR_NOT_READY;
+    return bhs_csr_components_device(_h, n, nnzS, d_rowPtrS, d_colIndS, flags, d_root, d_comp, d_compSize, ncomp_out, passes_out, 0);
 }
 
 inline int bhsparse::get_nnzC()

@@ -668,6 +668,54 @@ BHS_API int bhs_csr_spmm_semiring_device(bhs_handle *h, int semiring, int m, int
         bhs_value_t *d_Y /* m x k, in/out */, long long ldY /* >= k */, long long *changed_out /* may be NULL */,
         double *ms_out /* may be NULL */);
 
+/* ---- connected components ---------------------------------------------------
+ * Which vertices of an n x n pattern S belong together: the question asked of a graph before a traversal, an aggregation or
+ * a solver setup runs (no reference counterpart; bhs_components.hip.h).  One traversal finds one component and costs the
+ * graph's diameter in steps; this call finds all of them in a number of passes that grows like the diameter's logarithm.
+ * S is 0-based int32 CSR; values are NOT TAKEN, so the double and the float library run the same code and give the same bits.
+ * Definition.  Vertices i and j are joined where S stores (i, j) or (j, i): WEAK connectivity, S need not be symmetric.
+ *   Diagonal entries, repeated columns and the order inside a row make no difference; an isolated vertex is its own
+ *   component.  root[i] is the smallest vertex index in i's component.  comp[i] is the rank of root[i] among the roots, of
+ *   which there are ncomp: components are numbered by ascending smallest vertex.  compSize[c] is the number of vertices
+ *   with comp == c.  Everything except *passes_out is a function of the pattern: the same bits from run to run, from
+ *   handle to handle, and in the double and the float library.
+ * Passes.  Monotone relaxation in place on d_root, which starts as parent[i] = i.  At every instant parent[v] <= v,
+ *   parent[v] lies in v's component, and a word only ever falls: every write after the start is an atomic minimum.  A pass
+ *   lowers both ends of every stored entry (i, j) to the smaller of the two parents, lowers the word of i's grandparent
+ *   to the row's minimum (hooking: a whole tree moves under a smaller root) and lowers parent[i] to parent[parent[i]]
+ *   twice (pointer jumping).  An atomic is issued only where the value read is greater than what it would store.  A pass
+ *   that lowered nothing wrote nothing and therefore read one stable array in which both ends of every entry are equal:
+ *   it is constant on components, and at the component's smallest vertex that constant is the vertex itself -- the
+ *   definition, however a pass's reads race with other lanes' writes.  The host launches 8 passes per control round trip
+ *   and stops after a batch whose last pass lowered nothing; BHS_ERR_INTERNAL where more than n + 1 passes would be
+ *   needed.  *passes_out, the passes launched, DEPENDS ON TIMING; nothing else does.  Nothing spins on the device,
+ *   nothing waits for another workgroup.  A relabelled path of 32 768 vertices takes 16 passes where plain minimum-label
+ *   propagation takes its diameter (profiles/components_case.md).
+ * Outputs.  d_root: n ints.  d_comp (may be NULL): n ints in [0, ncomp).  d_compSize (may be NULL, needs d_comp): CAPACITY
+ *   n ints, of which ncomp are written.  *ncomp_out is the number of vertices with root[i] == i, counted by the last pass:
+ *   it is written with or without d_comp.  The numbering flags the roots, scans the flags per 64 vertices with the
+ *   library's one-pass scan as the aggregation numbers its roots, and sets comp[i] to the rank of root[i]; the sizes are
+ *   integer atomic adds, which do not depend on order.  The vertices sorted by component are NOT an output: the stable
+ *   transpose of the n x ncomp membership pattern (rowPtr = 0 .. n, colInd = comp) is that list.
+ * Validation, on the device, each check ahead of the dependent read: rowPtrS[i] > rowPtrS[i+1] or either outside
+ *   [0, nnzS]; a column outside [0, n).  On the host: a NULL handle, negative n or nnzS, flags != 0, a NULL d_rowPtrS or
+ *   d_root with n > 0, NULL d_colIndS with nnzS > 0, d_compSize without d_comp, an output's footprint overlapping S or
+ *   another output, and a call between bhs_spgemm_symbolic and bhs_spgemm_finish.  Each returns BHS_ERR_INVALID_ARG.  After
+ *   a refusal by the device the outputs are unspecified; nothing beyond their stated sizes is ever written.
+ * n == 0 succeeds with *ncomp_out = 0 and *passes_out = 0 and launches nothing.
+ * Synchronous on the handle's stream, needs no bound data, leaves the handle as it was (a workspace of its own).  ms_out
+ *   (may be NULL): device time of the call, the batches' round trips included.  bhs_get_kernel_stats then reports
+ *   components_pass (the relaxation, a row spread over 1, 4, 16 or 64 lanes by the pattern's mean row length) and, where
+ *   d_comp is given, components_number (the root flags, the scan, the numbering and the sizes).                      */
+BHS_API int bhs_csr_components_device(bhs_handle *h, int n, int nnzS,
+        const int *d_rowPtrS, const int *d_colIndS /* n x n pattern; values are not taken */,
+        int flags /* must be 0 */,
+        int *d_root     /* out: n ints: the smallest vertex of i's component */,
+        int *d_comp     /* out, may be NULL: n ints in [0, ncomp), components numbered by ascending root */,
+        int *d_compSize /* out, may be NULL, needs d_comp: CAPACITY n, ncomp written */,
+        int *ncomp_out /* may be NULL */, int *passes_out /* may be NULL; depends on timing */,
+        double *ms_out /* may be NULL */);
+
 /* ---- sparse frontier x CSR ------------------------------------------------
  * The push direction of the same traversal step: Y (+)= F (+).(x) G restricted to a LIST of rows of G (GraphBLAS vxm with a
  * sparse vector operand; no reference counterpart; bhs_push_sr.hip.h).  The pull calls above visit all m rows of A every
