@@ -130,6 +130,8 @@ SYMBOLS = {
     "bhs_csr_trsv_device": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, C.c_double, _vp, _vp, _i, C.POINTER(C.c_double)]),
     "bhs_csr_ilu0_device": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, C.POINTER(_i), C.POINTER(C.c_double)]),
     "bhs_csr_components_device": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(C.c_double)]),
+    "bhs_csr_match_device": (_i, [_vp, _i, _i, _vp, _vp, _vp, C.c_uint, _i, _vp, _vp, C.POINTER(_i), C.POINTER(_i),
+                                  C.POINTER(C.c_double)]),
     "bhs_strerror": (C.c_char_p, [_i]),
     "bhs_version": (C.c_char_p, []),
 }

@@ -3,8 +3,11 @@ include/bhsparse_hip.h, "aggregation") and, built from it and the existing devic
 strength pattern, the tentative and the smoothed prolongator, the Galerkin product, a V-cycle and a solver.  The cycle's
 smoother is weighted Jacobi or multicolour Gauss-Seidel on a device colouring (bhs_csr_color_device, bhs_csr_gs_device;
 "colouring and relaxation"); with forward sweeps before and backward sweeps after the coarse correction the cycle is
-symmetric and preconditions CG (pcg_device).  Beside it: the level sets of a triangle, the sparse triangular solve and
-ILU(0) in place (bhs_csr_levels_device, bhs_csr_trsv_device, bhs_csr_ilu0_device; "triangular solve and ILU(0)") and CG
+symmetric and preconditions CG (pcg_device).  A second, value-driven coarsening stands beside MIS(2): heavy-edge matching
+(bhs_csr_match_device; "matching"), repeated on the Galerkin-coarsened matrix into pairwise aggregates of up to 2^passes
+vertices that follow the strong couplings (pairwise_aggregate_device), and the same hierarchy on them (pa_setup_device):
+more levels and a higher operator complexity for fewer iterations (profiles/match_case.md has what that costs in time).
+Beside it: the level sets of a triangle, the sparse triangular solve and ILU(0) in place (bhs_csr_levels_device, bhs_csr_trsv_device, bhs_csr_ilu0_device; "triangular solve and ILU(0)") and CG
 preconditioned with that factorisation in natural or colour order (ilu0_pcg_device).
 
 Everything is a torch tensor on the handle's GPU: a matrix is (rowPtr int32, colInd int32, val), a pattern the first two.
@@ -52,6 +55,78 @@ def aggregate_device(bh, n, S, seed=0, prio=None):
     torch.cuda.synchronize()                           # the library works on its own stream (see facade.initData_device)
     _check(aggregate_raw_device(bh, n, Sj.numel(), Sp, Sj, prio, seed, 0, agg, roots), "bhs_csr_aggregate_device")
     return agg[:n], bh.aggregate_nagg, roots[:bh.aggregate_nagg]
+
+
+# ---------------------------------------------------------------- matching and pairwise aggregation
+def match_raw_device(bh, n, nnzA, d_rowPtrA, d_colIndA, d_valA, seed, flags, d_mate, d_agg):
+    """bhs_csr_match_device on caller-given arrays, the C arguments in order (d_valA and d_agg may be None): the status code;
+    sets bh.match_ms, bh.match_npairs and bh.match_rounds on success."""
+    if bh._h is None:
+        return _lib.BHS_ERR_NOT_READY
+    npairs, rounds, ms = C.c_int(0), C.c_int(0), C.c_double(0)
+    err = bh._lib.bhs_csr_match_device(bh._h, int(n), int(nnzA), _ptr(d_rowPtrA), _ptr(d_colIndA), _ptr(d_valA),
+                                       int(seed) & 0xFFFFFFFF, int(flags), _ptr(d_mate), _ptr(d_agg), C.byref(npairs),
+                                       C.byref(rounds), C.byref(ms))
+    if err == _lib.BHS_SUCCESS:
+        bh.match_ms, bh.match_npairs, bh.match_rounds = float(ms.value), int(npairs.value), int(rounds.value)
+    return err
+
+
+def match_device(bh, n, A, seed=0):
+    """The heavy-edge matching of the n x n matrix A = (rowPtr, colInd, val-or-None), torch tensors on the handle's GPU: the
+    greedy matching in descending (|a_ij|, hash, indices) where pattern and weights are symmetric; None for the values:
+    every weight 1.  Returns (mate int32[n], agg int32[n], nagg, npairs): mate[i] == i where i is unmatched, agg the pairs
+    and singletons numbered by ascending smaller member, nagg = n - npairs.  bh.match_rounds and bh.match_ms hold the rounds
+    and the device time.  Raises BhsparseError on failure."""
+    import torch
+    Ap, Aj = A[0], A[1]
+    Ax = A[2] if len(A) > 2 else None
+    mate = _alloc(n, torch.int32, Ap.device)
+    agg = _alloc(n, torch.int32, Ap.device)
+    torch.cuda.synchronize()                           # the library works on its own stream (see facade.initData_device)
+    _check(match_raw_device(bh, n, Aj.numel(), Ap, Aj if Aj.numel() else None, Ax if Aj.numel() else None, seed, 0, mate, agg),
+           "bhs_csr_match_device")
+    return mate[:n], agg[:n], n - bh.match_npairs, bh.match_npairs
+
+
+def match_csr(n, Ap, Aj, Ax, seed=0, value_dtype=np.float64, device=0):
+    """Convenience: match_device once on host CSR arrays (Ax may be None: every weight 1).  Returns numpy (mate int32[n],
+    agg int32[n], nagg, npairs)."""
+    A = _device_csr(Ap, Aj, Ax, value_dtype, device)
+    with _handle(value_dtype, device, None) as bh:
+        mate, agg, nagg, npairs = match_device(bh, n, A, seed)
+        return _host(mate, agg) + (nagg, npairs)
+
+
+def pairwise_aggregate_device(handles, n, A, passes=2, seed=0):
+    """Pairwise aggregation of the n x n matrix A = (rowPtr, colInd, val): `passes` (1..4) heavy-edge matchings, pass p on the
+    current matrix with seed + p; between two passes the matrix is coarsened with the unit tentative prolongator of the
+    pass's pairs, T = (0..m, agg_p, ones), through galerkin_device (T^T A T: the sums of A over the pairs), and the
+    aggregates are composed, agg = agg_p[agg].  handles: (h1, h2) as galerkin_device takes them.  Stops early where a pass
+    matches nothing.  Returns (agg int32[n], nagg, info): aggregates of at most 2^passes vertices, numbered by ascending
+    smallest member (a pass numbers its pairs by ascending smaller member, and by induction that is the aggregate of the
+    smallest fine vertex); info a list with one entry per pass: n, npairs, rounds and the device ms of match / galerkin."""
+    import torch
+    if not 1 <= int(passes) <= 4:
+        raise ValueError("passes is 1, 2, 3 or 4")
+    h1, h2 = handles
+    agg, m, info = None, n, []
+    for p in range(int(passes)):
+        _, agg_p, nagg, npairs = match_device(h1, m, A, seed + p)
+        rec = {"n": m, "npairs": npairs, "rounds": h1.match_rounds, "match_ms": h1.match_ms}
+        info.append(rec)
+        if npairs == 0:
+            break
+        agg = agg_p if agg is None else agg_p[agg.long()]
+        if p + 1 < int(passes):
+            T = (torch.arange(m + 1, dtype=torch.int32, device=agg_p.device), agg_p.contiguous(),
+                 torch.ones(m, dtype=_tdt(h1), device=agg_p.device))
+            A, _ = galerkin_device(h1, h2, m, nagg, A, T)
+            rec["galerkin_ms"] = h1.galerkin_ms
+        m = nagg
+    if agg is None:
+        agg = torch.arange(n, dtype=torch.int32, device=A[0].device)
+    return agg.to(torch.int32).contiguous(), m, info
 
 
 # ---------------------------------------------------------------- colouring and relaxation
@@ -224,6 +299,17 @@ def sa_setup_device(handles, n, A, theta=0.0, omega=2.0 / 3.0, max_levels=10, mi
     Returns (levels, info): levels a list of (A_l, P_l, R_l = P_l^T) with P = R = None on the last; info a list with one
     entry per level: n, nnz and, where the level was coarsened, nagg, rounds and the device ms of strength / aggregate /
     prolongator / galerkin."""
+    def coarsen(h1, h2, n, A, lvl):
+        S = strength_device(h1, n, A, theta)
+        agg, nagg, _ = aggregate_device(h1, n, S, seed)
+        return agg, nagg, {"rounds": h1.aggregate_rounds, "strength_ms": h1.strength_ms, "aggregate_ms": h1.aggregate_ms}
+    return _setup_levels(handles, n, A, coarsen, omega, max_levels, min_coarse)
+
+
+def _setup_levels(handles, n, A, coarsen, omega, max_levels, min_coarse):
+    """The level loop of sa_setup_device and pa_setup_device: coarsen(h1, h2, n, A, level) -> (agg, nagg, what the level's
+    record says of it), then tentative -> smoothed prolongator -> Galerkin product, until max_levels, min_coarse rows or
+    fewer, or a level on which nothing is merged."""
     own = callable(handles)
     h1, h2 = (handles(), handles()) if own else handles
     try:
@@ -233,15 +319,15 @@ def sa_setup_device(handles, n, A, theta=0.0, omega=2.0 / 3.0, max_levels=10, mi
             info.append(rec)
             if len(levels) + 1 >= max_levels or n <= min_coarse:
                 break
-            S = strength_device(h1, n, A, theta)
-            agg, nagg, _ = aggregate_device(h1, n, S, seed)
+            agg, nagg, said = coarsen(h1, h2, n, A, len(levels))
             if nagg >= n:
                 break
             T, _ = tentative_device(h1, n, agg, nagg)
             P = smoothed_prolongator_device(h1, n, nagg, A, T, omega)
             Ac, R = galerkin_device(h1, h2, n, nagg, A, P)
-            rec.update({"nagg": nagg, "rounds": h1.aggregate_rounds, "strength_ms": h1.strength_ms,
-                        "aggregate_ms": h1.aggregate_ms, "prolongator_ms": h1.prolongator_ms, "galerkin_ms": h1.galerkin_ms})
+            rec.update({"nagg": nagg})
+            rec.update(said)
+            rec.update({"prolongator_ms": h1.prolongator_ms, "galerkin_ms": h1.galerkin_ms})
             levels.append((A, P, R))
             A, n = Ac, nagg
         levels.append((A, None, None))
@@ -250,6 +336,36 @@ def sa_setup_device(handles, n, A, theta=0.0, omega=2.0 / 3.0, max_levels=10, mi
         if own:
             h1.freePlatform()
             h2.freePlatform()
+
+
+def pa_setup_device(handles, n, A, passes=3, omega=2.0 / 3.0, max_levels=10, min_coarse=40, seed=0):
+    """The hierarchy of sa_setup_device with pairwise aggregation in place of strength and MIS(2): per level
+    pairwise_aggregate_device(passes) with seed + 8 * level -> tentative -> P = T - omega D^-1 A T -> A_c = P^T (A P).
+    handles, the stopping rules and (levels, info) as sa_setup_device; a level's record holds n, nnz and, where it was
+    coarsened, nagg, the passes' records ("passes") and the device ms of aggregate (the matchings and the Galerkin products
+    between them) / prolongator / galerkin.  vcycle_device, smoother_setup_device, solve_device and pcg_device run on it
+    unchanged.  passes defaults to 3: on the MI355X two passes gave fewer iterations but, at a million unknowns, eight or
+    nine levels and an operator complexity of 4 to 13, and lost to three passes in setup plus solve time on all three
+    matrices measured (profiles/match_case.md)."""
+    if not 1 <= int(passes) <= 4:
+        raise ValueError("passes is 1, 2, 3 or 4")
+
+    def coarsen(h1, h2, n, A, lvl):
+        agg, nagg, said = pairwise_aggregate_device((h1, h2), n, A, passes, seed + 8 * lvl)
+        ms = sum(r["match_ms"] + r.get("galerkin_ms", 0.0) for r in said)
+        return agg, nagg, {"passes": said, "aggregate_ms": ms}
+    return _setup_levels(handles, n, A, coarsen, omega, max_levels, min_coarse)
+
+
+def pa_setup_csr(n, Ap, Aj, Ax, passes=3, omega=2.0 / 3.0, max_levels=10, min_coarse=40, seed=0, value_dtype=np.float64,
+                 device=0):
+    """Convenience: pa_setup_device on a host CSR matrix (rows strictly ascending), built on the device and copied back, as
+    sa_setup_csr."""
+    A = _device_csr(Ap, Aj, Ax, value_dtype, device)
+    with _handle(value_dtype, device, None) as h1, _handle(value_dtype, device, None) as h2:
+        levels, info = pa_setup_device((h1, h2), n, A, passes, omega, max_levels, min_coarse, seed)
+    host = lambda M: None if M is None else _host(*M)   # noqa: E731
+    return [(host(a), host(p), host(r)) for a, p, r in levels], info
 
 
 def sa_setup_csr(n, Ap, Aj, Ax, theta=0.0, omega=2.0 / 3.0, max_levels=10, min_coarse=40, seed=0, value_dtype=np.float64,

@@ -412,6 +412,9 @@ struct bhs_handle {
     // the connected components (bhs_host_components.inc.h): the root bitmap and the scanned offsets in its queue buffer, the
     // roots per bitmap word in its count buffer
     SideWs ccWs;
+    // the matching (bhs_host_match.inc.h): the leader bitmap, the scanned offsets and the rounds' candidates in its queue
+    // buffer, the leaders per bitmap word in its count buffer
+    SideWs mtWs;
 };
 
 namespace {
@@ -582,6 +585,7 @@ inline int one_launch(int rc) { return rc != BHS_SUCCESS ? rc : 1; }
 #include "bhs_host_color.inc.h"
 #include "bhs_host_trsv.inc.h"
 #include "bhs_host_components.inc.h"
+#include "bhs_host_match.inc.h"
 #include "bhs_host_transpose.inc.h"
 #include "bhs_host_reduce.inc.h"
 #include "bhs_host_semiring.inc.h"

@@ -164,6 +164,14 @@ public:
     int csr_components_device(int n, int nnzS, const index_type *d_rowPtrS, const index_type *d_colIndS, int flags,
                               index_type *d_root, index_type *d_comp, index_type *d_compSize, int *ncomp_out, int *passes_out);
 
+    // EXTENSION, not part of the reference's API: heavy-edge matching of the vertices of an n x n matrix A on DEVICE arrays
+    // (bhs_csr_match_device; include/bhsparse_hip.h, "matching").  d_valA may be null: every weight 1.  d_mate (n ints)
+    // receives every vertex's partner, the vertex itself where it is unmatched; d_agg (n ints, may be null) the number of its
+    // pair or singleton by ascending smaller member, n - *npairs_out of them.  *rounds_out is a function of the input.
+    // flags must be 0.  Needs initPlatform only.
+    int csr_match_device(int n, int nnzA, const index_type *d_rowPtrA, const index_type *d_colIndA, const value_type *d_valA,
+                         unsigned seed, int flags, index_type *d_mate, index_type *d_agg, int *npairs_out, int *rounds_out);
+
     // EXTENSION, not part of the reference's API: the multiply over a semiring (bhs_spgemm_semiring*, include/bhsparse_hip.h,
     // "semiring multiply"; semiring: a BHS_SR_* constant) on the data of initData.  spgemm_semiring is the full product: it
     // fills the csrRowPtrC of initData, and get_nnzC / get_C then return A (+).(x) B on the pattern of A·B.
@@ -413,6 +421,14 @@ inline int bhsparse::csr_components_device(int n, int nnzS, const index_type *d_
 {
     if (!_h) return BHS_ERR_NOT_READY;
     return bhs_csr_components_device(_h, n, nnzS, d_rowPtrS, d_colIndS, flags, d_root, d_comp, d_compSize, ncomp_out, passes_out, 0);
+}
+
+inline int bhsparse::csr_match_device(int n, int nnzA, const index_type *d_rowPtrA, const index_type *d_colIndA,
+                                      const value_type *d_valA, unsigned seed, int flags, index_type *d_mate, index_type *d_agg,
+                                      int *npairs_out, int *rounds_out)
+{
+    if (!_h) return BHS_ERR_NOT_READY;
+    return bhs_csr_match_device(_h, n, nnzA, d_rowPtrA, d_colIndA, d_valA, seed, flags, d_mate, d_agg, npairs_out, rounds_out, 0);
 }
 
 inline int bhsparse::get_nnzC()

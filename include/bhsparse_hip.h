@@ -716,6 +716,64 @@ BHS_API int bhs_csr_components_device(bhs_handle *h, int n, int nnzS,
         int *ncomp_out /* may be NULL */, int *passes_out /* may be NULL; depends on timing */,
         double *ms_out /* may be NULL */);
 
+/* ---- matching ---------------------------------------------------------------
+ * Heavy-edge matching: every vertex of an n x n matrix A is paired with the neighbour it is most strongly coupled to, greedily
+ * in descending edge key -- the coarsening step of pairwise-aggregation multigrid (Notay's AGMG) and of multilevel graph
+ * partitioning, and a 1/2-approximation of the maximum-weight matching (no reference counterpart; bhs_match.hip.h).  Beside
+ * the MIS(2) aggregation below, which works on a pattern and coarsens at a fixed aggressive rate, this one is driven by
+ * the VALUES and halves the vertices at most: repeated on the Galerkin-coarsened matrix it gives aggregates of up to
+ * 2^passes vertices that follow the strong direction (amg.pairwise_aggregate_device, amg.pa_setup_device).
+ * A is 0-based int32 CSR; rows need not be sorted.
+ * Edges.  An entry (i, j) of row i is an edge seen from i where j != i, its weight w = |a_ij| is greater than 0 and w is
+ *   not NaN.  d_valA == NULL: every weight is 1.  +Inf is a legal weight, an explicit zero (or minus zero) is no connection.
+ *   Of a repeated (i, j) the greatest weight counts.
+ * Edge key.  The tuple (w, h(lo, hi), lo, hi), compared lexicographically, with lo = min(i, j), hi = max(i, j),
+ *   h(lo, hi) = mix(mix(lo ^ seed) ^ hi) and mix(x): x += 0x9e3779b9; x ^= x >> 16; x *= 0x85ebca6b; x ^= x >> 13;
+ *   x *= 0xc2b2ae35; x ^= x >> 16 (mod 2^32; the aggregation's finaliser).  w is compared in the library's value type.
+ *   Seen from one vertex, lexicographic (lo, hi) is "the greater other endpoint wins".  The hash stands in front of the
+ *   indices because with index tie-breaks alone a path of equal weights needs n / 2 rounds.
+ * Rounds, synchronous over d_mate (-1 undecided, i itself: finally unmatched, j: matched with j).  PROPOSE: every undecided
+ *   i sets cand[i] to the undecided neighbour of greatest key over its edges, -1 without one; the lanes of a decided vertex
+ *   skip its row.  ACCEPT: an undecided i with cand[i] == -1 becomes i (final: eligibility only shrinks); one with
+ *   c = cand[i] and cand[c] == i becomes c.  A launch either reads mate and writes cand or reads cand and writes the vertex's
+ *   own word of mate: no atomics touch a result, nothing depends on timing.  The host reads one word a round (the pairs it
+ *   made, the vertices it left) and stops after a round that matched nothing -- the vertices it left become unmatched --
+ *   or left nobody.  *rounds_out is the number of rounds that matched at least one pair, a function of the input;
+ *   BHS_ERR_INTERNAL where more than n / 2 + 1 rounds would be needed.  Nothing spins on the device, nothing waits for
+ *   another workgroup.
+ * What is promised.  For ANY input the result is what these synchronous rounds give: a valid matching, mate[mate[i]] == i,
+ *   and a function of the input.  Where pattern and weights are SYMMETRIC (the edge {i, j} has one weight from both ends)
+ *   the edge of greatest key among the undecided is mutual in every round, and the result is THE greedy matching in
+ *   descending key order: unique, maximal, independent of scheduling, the same bits from run to run and from handle to
+ *   handle -- and in the double and the float library where the values are exactly representable in float or d_valA is
+ *   NULL.  For other inputs the matching need not be maximal.  A path of 200 vertices with strictly increasing weights
+ *   takes 100 rounds, the worst case; grids, bands and random patterns of one to two million vertices take 5 to 10
+ *   (profiles/match_case.md).
+ * Numbering, where d_agg is given.  leader[i] = min(i, mate[i]); the aggregates -- pairs and singletons -- are numbered by
+ *   ascending leader: the leaders are flagged, the flags scanned per 64 vertices with the library's one-pass scan as the
+ *   components number their roots, agg[i] is the rank of i's leader.  There are n - npairs of them; the host checks the
+ *   scan's total against that, else BHS_ERR_INTERNAL.
+ * Validation, on the device, each check ahead of the dependent read: rowPtrA[i] > rowPtrA[i+1] or either outside
+ *   [0, nnzA]; a column outside [0, n) -- mate[j] is read only after j passed.  On the host: a NULL handle, negative n or
+ *   nnzA, flags != 0, a NULL d_rowPtrA or d_mate with n > 0, NULL d_colIndA with nnzA > 0, an output's footprint
+ *   overlapping A or the other output, and a call between bhs_spgemm_symbolic and bhs_spgemm_finish.  Each returns
+ *   BHS_ERR_INVALID_ARG; the host's refusals leave the outputs untouched, after a refusal by the device they are
+ *   unspecified; nothing beyond their stated sizes is ever written.
+ * n == 0 succeeds with *npairs_out = 0, *rounds_out = 0 and *ms_out = 0 and launches nothing.
+ * Synchronous on the handle's stream, needs no bound data, leaves the handle as it was (a workspace of its own).  ms_out
+ *   (may be NULL): device time of the call, the rounds' round trips included.  bhs_get_kernel_stats then reports match_init
+ *   (the row bounds, mate = -1), match_round (propose and accept, a row spread over 1, 4, 16 or 64 lanes by the mean row
+ *   length; the closing of a round that left vertices) and, where d_agg is given, match_number (the leader flags, the scan,
+ *   the numbering).                                                                                                   */
+BHS_API int bhs_csr_match_device(bhs_handle *h, int n, int nnzA,
+        const int *d_rowPtrA, const int *d_colIndA,
+        const bhs_value_t *d_valA /* may be NULL: every weight 1 */,
+        unsigned seed, int flags /* must be 0 */,
+        int *d_mate /* out: n ints; mate[i] == i where i is unmatched */,
+        int *d_agg  /* out, may be NULL: n ints in [0, n - npairs) */,
+        int *npairs_out /* may be NULL */, int *rounds_out /* may be NULL */,
+        double *ms_out /* may be NULL */);
+
 /* ---- sparse frontier x CSR ------------------------------------------------
  * The push direction of the same traversal step: Y (+)= F (+).(x) G restricted to a LIST of rows of G (GraphBLAS vxm with a
  * sparse vector operand; no reference counterpart; bhs_push_sr.hip.h).  The pull calls above visit all m rows of A every
