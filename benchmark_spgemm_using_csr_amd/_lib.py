@@ -61,6 +61,9 @@ BHS_GS_FORWARD, BHS_GS_BACKWARD, BHS_GS_SYMMETRIC, BHS_GS_VERIFY = 1, 2, 3, 4
 # bhs_csr_levels_device / bhs_csr_trsv_device (include/bhsparse_hip.h, "triangular solve and ILU(0)")
 BHS_TRI_LOWER, BHS_TRI_UPPER, BHS_TRI_UNIT_DIAG = 1, 2, 4
 
+# bhs_csr_spanning_forest_device (include/bhsparse_hip.h, "spanning forest")
+BHS_FOREST_MAXIMUM, BHS_FOREST_ABS = 1, 2
+
 
 # every symbol include/bhsparse_hip.h declares: (restype, argtypes)
 _vp, _i, _i64 = C.c_void_p, C.c_int, C.c_int64
@@ -132,6 +135,8 @@ SYMBOLS = {
     "bhs_csr_components_device": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(C.c_double)]),
     "bhs_csr_match_device": (_i, [_vp, _i, _i, _vp, _vp, _vp, C.c_uint, _i, _vp, _vp, C.POINTER(_i), C.POINTER(_i),
                                   C.POINTER(C.c_double)]),
+    "bhs_csr_spanning_forest_device": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, C.POINTER(_i), C.POINTER(_i),
+                                            C.POINTER(C.c_double)]),
     "bhs_strerror": (C.c_char_p, [_i]),
     "bhs_version": (C.c_char_p, []),
 }

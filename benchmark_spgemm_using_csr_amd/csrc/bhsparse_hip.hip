@@ -415,6 +415,9 @@ struct bhs_handle {
     // the matching (bhs_host_match.inc.h): the leader bitmap, the scanned offsets and the rounds' candidates in its queue
     // buffer, the leaders per bitmap word in its count buffer
     SideWs mtWs;
+    // the spanning forest (bhs_host_forest.inc.h): the trees' picks, the slot bitmap, the slots, parent and the scanned offsets
+    // in its queue buffer, the written slots per bitmap word in its count buffer
+    SideWs sfWs;
 };
 
 namespace {
@@ -586,6 +589,7 @@ inline int one_launch(int rc) { return rc != BHS_SUCCESS ? rc : 1; }
 #include "bhs_host_trsv.inc.h"
 #include "bhs_host_components.inc.h"
 #include "bhs_host_match.inc.h"
+#include "bhs_host_forest.inc.h"
 #include "bhs_host_transpose.inc.h"
 #include "bhs_host_reduce.inc.h"
 #include "bhs_host_semiring.inc.h"

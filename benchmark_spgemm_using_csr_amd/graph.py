@@ -13,7 +13,11 @@ a banded matrix -- that is the difference between touching every edge once and t
 
 components_* answer which vertices belong together, for all components at once and whatever the direction of the entries
 (bhs_csr_components_device; "connected components"): the passes grow like the logarithm of the diameter, not like the
-diameter."""
+diameter.
+
+spanning_forest_* give the minimum or maximum spanning forest of the weighted graph (bhs_csr_spanning_forest_device;
+"spanning forest"), unique for any input, in at most log2 n Boruvka rounds; single_linkage_device cuts its heaviest edges
+and calls the components on the rest."""
 import ctypes as C
 
 import numpy as np
@@ -304,6 +308,85 @@ def largest_component_csr(n, Ap, Aj, Ax, value_dtype=np.float64, device=0):
     vertices = np.flatnonzero(comp == c).astype(np.int32)
     Zp, Zj, Zx, _ = extract_csr(n, n, Ap, Aj, Ax, rows=vertices, cols=vertices, value_dtype=value_dtype, device=device)
     return vertices, (Zp, Zj, Zx)
+
+
+# ---------------------------------------------------------------- spanning forest
+def spanning_forest_raw_device(bh, n, nnzA, d_rowPtrA, d_colIndA, d_valA, flags, d_label, d_edgeLo, d_edgeHi, d_edgeVal):
+    """bhs_csr_spanning_forest_device on caller-given arrays, the C arguments in order (d_valA and d_edgeVal may be None): the
+    status code; sets bh.forest_nedges, bh.forest_rounds and bh.forest_ms on success only."""
+    if bh._h is None:
+        return _lib.BHS_ERR_NOT_READY
+    nedges, rounds, ms = C.c_int(0), C.c_int(0), C.c_double(0)
+    err = bh._lib.bhs_csr_spanning_forest_device(bh._h, int(n), int(nnzA), _ptr(d_rowPtrA), _ptr(d_colIndA), _ptr(d_valA),
+                                                 int(flags), _ptr(d_label), _ptr(d_edgeLo), _ptr(d_edgeHi), _ptr(d_edgeVal),
+                                                 C.byref(nedges), C.byref(rounds), C.byref(ms))
+    if err == _lib.BHS_SUCCESS:
+        bh.forest_nedges, bh.forest_rounds, bh.forest_ms = int(nedges.value), int(rounds.value), float(ms.value)
+    return err
+
+
+def spanning_forest_device(bh, n, A, maximum=False, absolute=False):
+    """The minimum spanning forest of the n-vertex graph A = (rowPtr, colInd, val or None), torch tensors on the handle's GPU
+    (include/bhsparse_hip.h, "spanning forest"): every entry (i, j), j != i, whose weight is not NaN is an undirected edge,
+    from whichever end and however often it is stored; val None: every weight 1.  maximum: the maximum forest; absolute: the
+    weights are |a_ij|.  Returns (lo int32[m], hi int32[m], w[m], label int32[n]) as device tensors: the forest's edges
+    sorted by (lo, hi), lo < hi, with the weights as compared, and the root of every vertex's tree.  bh.forest_nedges,
+    bh.forest_rounds and bh.forest_ms hold m, the rounds and the device time.  Raises BhsparseError on failure."""
+    import torch
+    Ap, Aj, Ax = A[0], A[1], A[2] if len(A) > 2 else None
+    dt = _value_type(bh, (Ap, Aj, Ax))
+    label, lo, hi = (_alloc(n, torch.int32, Ap.device) for _ in range(3))
+    w = _alloc(n, dt, Ap.device)
+    flags = (_lib.BHS_FOREST_MAXIMUM if maximum else 0) | (_lib.BHS_FOREST_ABS if absolute else 0)
+    torch.cuda.synchronize()                           # the library works on its own stream (see facade.initData_device)
+    _check(spanning_forest_raw_device(bh, n, Aj.numel(), Ap, Aj if Aj.numel() else None, Ax if Aj.numel() else None, flags,
+                                      label, lo, hi, w), "bhs_csr_spanning_forest_device")
+    m = bh.forest_nedges
+    order = torch.argsort((lo[:m].to(torch.int64) << 32) | hi[:m].to(torch.int64))
+    return lo[:m][order], hi[:m][order], w[:m][order], label[:n]
+
+
+def forest_csr_device(n, lo, hi, w):
+    """The edge list (lo, hi, w) of spanning_forest_device as a symmetric n x n CSR (rowPtr int32[n + 1], colInd int32[2 m],
+    val[2 m]), both directions stored, rows ascending: torch plumbing only."""
+    import torch
+    rows = torch.cat([lo, hi]).to(torch.int64)
+    cols = torch.cat([hi, lo]).to(torch.int64)
+    order = torch.argsort((rows << 32) | cols)
+    rowptr = torch.zeros(n + 1, dtype=torch.int32, device=lo.device)
+    if rows.numel():
+        rowptr[1:] = torch.cumsum(torch.bincount(rows, minlength=n), 0).to(torch.int32)
+    return rowptr, cols[order].to(torch.int32), torch.cat([w, w])[order]
+
+
+def _weight_order(w):
+    """int64 whose signed order is the order of the weights as numbers, -0 below +0 (the library's key)"""
+    import torch
+    b = w.to(torch.float64).view(torch.int64)
+    return torch.where(b < 0, b ^ 0x7fffffffffffffff, b)
+
+
+def single_linkage_device(bh, n, A, nclusters):
+    """Single-linkage clustering of the n-vertex graph A = (rowPtr, colInd, val or None) into nclusters clusters: the minimum
+    spanning forest, without its heaviest edges -- by the forest's own key order (weight, lo, hi) -- until nclusters trees
+    remain, then components_device on what is left.  Returns comp int32[n], the clusters numbered by ascending smallest
+    vertex.  ValueError where nclusters is below the number of components of A or above n."""
+    import torch
+    lo, hi, w, _ = spanning_forest_device(bh, n, A)
+    m = lo.numel()
+    if nclusters < n - m or nclusters > n:
+        raise ValueError("single_linkage_device: %d clusters of a graph with %d vertices and %d components" % (nclusters, n, n - m))
+    keep = torch.sort(_weight_order(w), stable=True)[1][:n - nclusters]   # (the edges came sorted by (lo, hi): ties keep that order)
+    rest = forest_csr_device(n, lo[keep], hi[keep], w[keep])
+    return components_device(bh, n, rest)[1]
+
+
+def spanning_forest_csr(n, Ap, Aj, Ax, maximum=False, absolute=False, value_dtype=np.float64, device=0):
+    """Convenience: spanning_forest_device once on host CSR arrays.  Returns numpy (lo int32[m], hi int32[m], w
+    value_dtype[m], label int32[n])."""
+    A = _device_csr(Ap, Aj, Ax, value_dtype, device)
+    with _handle(value_dtype, device, None) as bh:
+        return _host(*spanning_forest_device(bh, n, A, maximum, absolute))
 
 
 def bfs_levels_csr(n, Ap, Aj, Ax, sources, value_dtype=np.float64, device=0):

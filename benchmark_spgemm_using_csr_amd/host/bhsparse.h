@@ -172,6 +172,15 @@ public:
     int csr_match_device(int n, int nnzA, const index_type *d_rowPtrA, const index_type *d_colIndA, const value_type *d_valA,
                          unsigned seed, int flags, index_type *d_mate, index_type *d_agg, int *npairs_out, int *rounds_out);
 
+    // EXTENSION, not part of the reference's API: the minimum (flags: BHS_FOREST_MAXIMUM, BHS_FOREST_ABS) spanning forest of
+    // the graph of an n x n matrix A on DEVICE arrays (bhs_csr_spanning_forest_device; include/bhsparse_hip.h, "spanning
+    // forest").  d_valA may be null: every weight 1.  d_label (n ints) receives the root of every vertex's tree; d_edgeLo,
+    // d_edgeHi and d_edgeVal (room for n each, d_edgeVal may be null) the *nedges_out edges, lo < hi.  *rounds_out is a function
+    // of the input.  Needs initPlatform only.
+    int csr_spanning_forest_device(int n, int nnzA, const index_type *d_rowPtrA, const index_type *d_colIndA,
+                                   const value_type *d_valA, int flags, index_type *d_label, index_type *d_edgeLo,
+                                   index_type *d_edgeHi, value_type *d_edgeVal, int *nedges_out, int *rounds_out);
+
     // EXTENSION, not part of the reference's API: the multiply over a semiring (bhs_spgemm_semiring*, include/bhsparse_hip.h,
     // "semiring multiply"; semiring: a BHS_SR_* constant) on the data of initData.  spgemm_semiring is the full product: it
     // fills the csrRowPtrC of initData, and get_nnzC / get_C then return A (+).(x) B on the pattern of A·B.
@@ -429,6 +438,15 @@ inline int bhsparse::csr_match_device(int n, int nnzA, const index_type *d_rowPt
 {
     if (!_h) return BHS_ERR_NOT_READY;
     return bhs_csr_match_device(_h, n, nnzA, d_rowPtrA, d_colIndA, d_valA, seed, flags, d_mate, d_agg, npairs_out, rounds_out, 0);
+}
+
+inline int bhsparse::csr_spanning_forest_device(int n, int nnzA, const index_type *d_rowPtrA, const index_type *d_colIndA,
+                                                const value_type *d_valA, int flags, index_type *d_label, index_type *d_edgeLo,
+                                                index_type *d_edgeHi, value_type *d_edgeVal, int *nedges_out, int *rounds_out)
+{
+    if (!_h) return BHS_ERR_NOT_READY;
+    return bhs_csr_spanning_forest_device(_h, n, nnzA, d_rowPtrA, d_colIndA, d_valA, flags, d_label, d_edgeLo, d_edgeHi, d_edgeVal,
+                                          nedges_out, rounds_out, 0);
 }
 
 inline int bhsparse::get_nnzC()

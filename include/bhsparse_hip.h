@@ -668,6 +668,73 @@ BHS_API int bhs_csr_spmm_semiring_device(bhs_handle *h, int semiring, int m, int
         bhs_value_t *d_Y /* m x k, in/out */, long long ldY /* >= k */, long long *changed_out /* may be NULL */,
         double *ms_out /* may be NULL */);
 
+/* ---- spanning forest --------------------------------------------------------
+ * The minimum (or maximum) spanning forest of the graph that an n x n matrix A stores, by Boruvka rounds on the device: for
+ * network design, as the spanning tree under a support-graph or tree preconditioner (the MAXIMUM forest of |a_ij| is the
+ * strongest tree of a matrix), for single-linkage clustering (cut the heaviest forest edges, then call the components
+ * below), and as a spanning tree of every component in O(log n) rounds where one traversal costs the diameter (no reference
+ * counterpart; bhs_forest.hip.h).  A is n x n, 0-based int32 CSR; rows need not be sorted and A need not be symmetric.
+ * Edges.  Every stored entry (i, j) with j != i whose weight is not NaN is an undirected edge {i, j}, a member of a
+ *   multigraph.  Its weight w is a_ij, or |a_ij| under BHS_FOREST_ABS, or 1 where d_valA == NULL.  +-Inf, negative weights
+ *   and explicit zeros are legal weights; NaN entries and the diagonal are no edges.  It makes no difference from which
+ *   end, or how often, an edge is stored.
+ * Key.  The tuple (k(w), lo, hi) compared lexicographically, lo = min(i, j), hi = max(i, j).  k is the reductions'
+ *   order-preserving key (rd_key(x, false)): the order of the numbers with -0 below +0; in the float library the value is
+ *   widened exactly, so both builds compare alike.  Under BHS_FOREST_MAXIMUM the whole order is reversed, index
+ *   tie-breaks included: the complement of both words.  The order is strict over distinct (w, lo, hi); entries with equal
+ *   tuples are the same edge.
+ * Result.  THE spanning forest that Kruskal's algorithm builds taking edges in ascending key order: unique for ANY input,
+ *   symmetric or not, repeated columns, ties everywhere.  Of a repeated {i, j} the lightest weight counts, under MAXIMUM
+ *   the heaviest.  It has n - (number of weak components) edges.  The same bits come back from run to run and from handle
+ *   to handle, and in the double and the float library where the weights are exactly representable in float or d_valA is
+ *   NULL.
+ * Rounds, synchronous: every launch either reads an array or writes the caller's own word of it, or lowers a word by an
+ *   integer atomicMin whose result no order can change.  PICK: for every entry crossing two trees (label[i] != label[j])
+ *   the 64-bit weight key lowers bestW[label[i]] and bestW[label[j]]; in a second launch the entries whose key equals
+ *   their tree's bestW lower bestE[label] with lo << 32 | hi.  A row's own side is reduced across its L lanes first; an
+ *   atomic is issued only where the value read (an agent-scope relaxed load) is greater than what it would store, so a
+ *   stale read only costs an unneeded atomic.  HOOK: a root c (label[c] == c) with a pick reads the label d of the pick's
+ *   far endpoint; where d picked the same tuple (a mutual pair) the smaller of c and d stays a root; every other c writes
+ *   parent[c] = d, in an array of its own, not in label, and stores its pick as the edge of SLOT c (lo, hi, rd_unkey of the
+ *   key).  A vertex is hooked at most once in the whole call, so a slot is written at most once; with a strict order the
+ *   hook graph has no cycle but the mutual pairs.  FLATTEN: pointer jumping on parent over the round's roots --
+ *   parent[c] = parent[parent[c]] in place at least doubles the distance covered in every launch, whatever the races, so
+ *   ceil(log2 R) launches reach the fixed point from R roots, R known to the host from the previous round -- then
+ *   label[i] = parent[label[i]] for every vertex in a launch of its own, which raises the error word where
+ *   parent[parent[l]] != parent[l]: BHS_ERR_INTERNAL.  The host reads one control block a round, the error word and the
+ *   trees hooked, and stops after a round that hooked nothing (or that left a single tree).  Trees with a crossing edge at
+ *   least halve per round, so at most floor(log2 n) rounds hook; *rounds_out is the number of rounds that hooked at least
+ *   one tree, a function of the input; BHS_ERR_INTERNAL where a 33rd round would be needed.  Nothing spins on the device,
+ *   nothing waits for another workgroup, and there are no floating atomics.
+ * Outputs.  d_label: n ints, label[label[i]] == label[i]; labels are equal exactly on the vertices of one tree, which is
+ *   one weak component of the edges above; which vertex of the tree is the label is a function of the input, it need not
+ *   be the smallest (bhs_csr_components_device gives that).  The edge list: d_edgeLo, d_edgeHi and d_edgeVal (may be
+ *   NULL) have CAPACITY n, *nedges_out entries are written: the written slots in ascending slot order -- the slots are
+ *   flagged per 64 vertices and the counts go through the library's one-pass scan, as the components number their roots --
+ *   with lo < hi and d_edgeVal the weight as compared: a_ij, |a_ij| or 1.  The host checks the scan's total against the
+ *   hooks it counted, else BHS_ERR_INTERNAL.
+ * Validation, on the device, each check ahead of the dependent read: rowPtrA[i] > rowPtrA[i+1] or either outside
+ *   [0, nnzA]; a column outside [0, n).  On the host, with the outputs untouched: a NULL handle, negative n or nnzA, a flag
+ *   bit other than the two, a NULL d_rowPtrA, d_label, d_edgeLo or d_edgeHi with n > 0, NULL d_colIndA with nnzA > 0, an
+ *   output's footprint overlapping A or another output, and a call between bhs_spgemm_symbolic and bhs_spgemm_finish.
+ *   Each returns BHS_ERR_INVALID_ARG.  After a refusal by the device the outputs are unspecified; nothing beyond their
+ *   stated sizes is ever written.
+ * n == 0 succeeds with zero edges, zero rounds and *ms_out = 0 and launches nothing.
+ * Synchronous on the handle's stream, needs no bound data, leaves the handle as it was (a workspace of its own).  ms_out
+ *   (may be NULL): device time of the call, the rounds' round trips included.  bhs_get_kernel_stats then reports
+ *   forest_pick (the start, and a round's clear, weight and edge launches, a row spread over 1, 4, 16 or 64 lanes by the
+ *   mean row length), forest_hook (the hook, the jumps, the relabel) and forest_list (the slot flags, the scan, the
+ *   write-out).  Measured: profiles/forest_case.md.                                                                  */
+enum { BHS_FOREST_MAXIMUM = 1, BHS_FOREST_ABS = 2 };
+BHS_API int bhs_csr_spanning_forest_device(bhs_handle *h, int n, int nnzA,
+        const int *d_rowPtrA, const int *d_colIndA,
+        const bhs_value_t *d_valA /* may be NULL: every weight 1 */,
+        int flags /* BHS_FOREST_MAXIMUM | BHS_FOREST_ABS */,
+        int *d_label          /* out: n ints */,
+        int *d_edgeLo, int *d_edgeHi /* out: CAPACITY n ints each, nedges written */,
+        bhs_value_t *d_edgeVal /* out, may be NULL: CAPACITY n */,
+        int *nedges_out, int *rounds_out, double *ms_out /* each may be NULL */);
+
 /* ---- connected components ---------------------------------------------------
  * Which vertices of an n x n pattern S belong together: the question asked of a graph before a traversal, an aggregation or
  * a solver setup runs (no reference counterpart; bhs_components.hip.h).  One traversal finds one component and costs the
