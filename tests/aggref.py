@@ -42,9 +42,10 @@ def _near_max(n, r, c, w):
     return out
 
 
-def rounds(n, Sp, Sj, key):
+def rounds(n, Sp, Sj, key, counts=None):
     """The library's algorithm: (is_root bool[n], number of rounds).  State undecided 1, in 2, out 0 in bits 62..63 of a
-    word a vertex; a round is two max passes over the closed neighbourhoods."""
+    word a vertex; a round is two max passes over the closed neighbourhoods.  counts: a list that gets the number of
+    undecided vertices every round starts from."""
     r, c = edges(n, Sp, Sj)
     w = UNDECIDED | key
     nrounds = 0
@@ -53,6 +54,8 @@ def rounds(n, Sp, Sj, key):
         t1 = _near_max(n, r, c, w)
         t2 = _near_max(n, r, c, t1)
         und = (w >> np.uint64(62)) == 1
+        if counts is not None:
+            counts.append(int(und.sum()))
         goes_in = und & (t2 == w)
         goes_out = und & ~goes_in & ((t2 >> np.uint64(62)) == 2)
         assert goes_in.any() or goes_out.any()
@@ -106,12 +109,12 @@ def join(n, Sp, Sj, key, root):
     return agg.astype(np.int32), roots
 
 
-def aggregate(n, Sp, Sj, seed=0, prio=None):
-    """(agg int32[n], nagg, roots int32[nagg], rounds): what bhs_csr_aggregate_device returns"""
+def aggregate(n, Sp, Sj, seed=0, prio=None, counts=None):
+    """(agg int32[n], nagg, roots int32[nagg], rounds): what bhs_csr_aggregate_device returns (counts: see `rounds`)"""
     if n == 0:
         return np.zeros(0, np.int32), 0, np.zeros(0, np.int32), 0
     key = keys(n, seed, prio)
-    root, nrounds = rounds(n, Sp, Sj, key)
+    root, nrounds = rounds(n, Sp, Sj, key, counts)
     agg, roots = join(n, Sp, Sj, key, root)
     return agg, len(roots), roots, nrounds
 

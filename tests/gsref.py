@@ -39,15 +39,18 @@ def greedy(n, Sp, Sj, key):
     return color.astype(np.int32)
 
 
-def rounds(n, Sp, Sj, key):
+def rounds(n, Sp, Sj, key, counts=None):
     """The library's algorithm: (color int32[n], number of rounds).  A round colours every uncoloured vertex whose key
-    exceeds that of each uncoloured off-diagonal neighbour, from the colours of the round before."""
+    exceeds that of each uncoloured off-diagonal neighbour, from the colours of the round before.  counts: a list that gets
+    the number of uncoloured vertices every round starts from."""
     nb = neighbours(n, Sp, Sj)
     color = np.full(n, -1, np.int64)
     nrounds = 0
     while np.any(color < 0):
         assert nrounds <= n, "a round colours at least one vertex"
         new = color.copy()
+        if counts is not None:
+            counts.append(int((color < 0).sum()))
         for v in np.flatnonzero(color < 0):
             near = color[nb[v]]
             if np.any(key[nb[v]][near < 0] > key[v]):
@@ -69,11 +72,11 @@ def order_of(color):
     return order, ptr
 
 
-def colouring(n, Sp, Sj, seed=0, prio=None):
-    """(color, ncolors, order, colorPtr, rounds): what bhs_csr_color_device returns"""
+def colouring(n, Sp, Sj, seed=0, prio=None, counts=None):
+    """(color, ncolors, order, colorPtr, rounds): what bhs_csr_color_device returns (counts: see `rounds`)"""
     if n == 0:
         return np.zeros(0, np.int32), 0, np.zeros(0, np.int32), np.zeros(1, np.int32), 0
-    color, nrounds = rounds(n, Sp, Sj, ar.keys(n, seed, prio))
+    color, nrounds = rounds(n, Sp, Sj, ar.keys(n, seed, prio), counts)
     order, ptr = order_of(color)
     return color, len(ptr) - 1, order, ptr, nrounds
 

@@ -30,11 +30,12 @@ def seen_edges(n, Ap, Aj, Ax):
     return r[keep], c[keep], w[keep]
 
 
-def rounds(n, Ap, Aj, Ax=None, seed=0):
+def rounds(n, Ap, Aj, Ax=None, seed=0, counts=None):
     """The library's algorithm: (mate int32[n], npairs, productive rounds).  mate is -1 undecided, i finally unmatched, j
     matched with j.  The entries are sorted once by (row, key seen from the row); a round takes, per undecided row, the last
     entry whose other end is undecided -- its proposal -- and accepts the mutual ones.  Entries with a decided end never
-    come back and are dropped from the list as the rounds go."""
+    come back and are dropped from the list as the rounds go.  counts: a list that gets the number of undecided vertices
+    every round starts from (no round starts from none) and, where the last round leaves some, their number."""
     if n == 0:
         return np.zeros(0, np.int32), 0, 0
     r, c, w = seen_edges(n, Ap, Aj, Ax)
@@ -47,6 +48,8 @@ def rounds(n, Ap, Aj, Ax=None, seed=0):
     while True:
         assert nrounds <= n // 2, "a productive round makes a pair"
         und = mate < 0
+        if counts is not None and und.any():
+            counts.append(int(und.sum()))
         live = und[r] & und[c]
         r, c = r[live], c[live]
         cand = np.full(n, -1, np.int64)
@@ -64,6 +67,8 @@ def rounds(n, Ap, Aj, Ax=None, seed=0):
         npairs += made
         nrounds += 1
     left = mate < 0                                                  # (only where pattern or weights are not symmetric)
+    if counts is not None and left.any():
+        counts.append(int(left.sum()))
     mate[left] = me[left]
     return mate.astype(np.int32), npairs, nrounds
 
@@ -96,9 +101,9 @@ def number(mate):
     return rank[np.minimum(me, mate)].astype(np.int32), int(leads.sum())
 
 
-def match(n, Ap, Aj, Ax=None, seed=0):
-    """(mate, agg, nagg, npairs, rounds): what bhs_csr_match_device returns"""
-    mate, npairs, nrounds = rounds(n, Ap, Aj, Ax, seed)
+def match(n, Ap, Aj, Ax=None, seed=0, counts=None):
+    """(mate, agg, nagg, npairs, rounds): what bhs_csr_match_device returns (counts: see `rounds`)"""
+    mate, npairs, nrounds = rounds(n, Ap, Aj, Ax, seed, counts)
     agg, nagg = number(mate)
     assert nagg == n - npairs
     return mate, agg, nagg, npairs, nrounds

@@ -66,11 +66,13 @@ def expected_families(Xp):
     return fam
 
 
-def check_select(bh, m, n, X, spec, dtype, what=""):
-    """The stand-alone selection of X on the device against selectref: bit for bit; the kernel families that must have run did."""
+def check_select(bh, m, n, X, spec, dtype, what="", ref=None):
+    """The stand-alone selection of X on the device against selectref (or `ref`, where the caller has it): bit for bit; the
+    kernel families that must have run did."""
     Xp, Xj, Xx = X
     Xx = np.ascontiguousarray(Xx, dtype)
-    ref = sr.select(m, n, Xp, Xj, Xx, spec)
+    if ref is None:
+        ref = sr.select(m, n, Xp, Xj, Xx, spec)
     dX = (up(Xp, np.int32), up(Xj, np.int32), up(Xx, dtype))
     Zp = torch.full((m + 1,), -7, dtype=torch.int32).cuda()
     torch.cuda.synchronize()
