@@ -64,6 +64,9 @@ BHS_TRI_LOWER, BHS_TRI_UPPER, BHS_TRI_UNIT_DIAG = 1, 2, 4
 # bhs_csr_spanning_forest_device (include/bhsparse_hip.h, "spanning forest")
 BHS_FOREST_MAXIMUM, BHS_FOREST_ABS = 1, 2
 
+# bhs_csr_cfsplit_device (include/bhsparse_hip.h, "C/F splitting and interpolation")
+BHS_CF_DEGREE = 1
+
 
 # every symbol include/bhsparse_hip.h declares: (restype, argtypes)
 _vp, _i, _i64 = C.c_void_p, C.c_int, C.c_int64
@@ -137,6 +140,12 @@ SYMBOLS = {
                                   C.POINTER(C.c_double)]),
     "bhs_csr_spanning_forest_device": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, C.POINTER(_i), C.POINTER(_i),
                                             C.POINTER(C.c_double)]),
+    "bhs_csr_cfsplit_device": (_i, [_vp, _i, _i, _vp, _vp, _vp, C.c_uint, _i, _vp, _vp, C.POINTER(_i), C.POINTER(_i),
+                                    C.POINTER(C.c_double)]),
+    "bhs_csr_interp_symbolic_device": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, C.POINTER(C.c_longlong),
+                                            C.POINTER(C.c_double)]),
+    "bhs_csr_interp_numeric_device": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, C.c_longlong, _vp, _vp, _i,
+                                           C.POINTER(C.c_double)]),
     "bhs_strerror": (C.c_char_p, [_i]),
     "bhs_version": (C.c_char_p, []),
 }

@@ -7,6 +7,10 @@ symmetric and preconditions CG (pcg_device).  A second, value-driven coarsening 
 (bhs_csr_match_device; "matching"), repeated on the Galerkin-coarsened matrix into pairwise aggregates of up to 2^passes
 vertices that follow the strong couplings (pairwise_aggregate_device), and the same hierarchy on them (pa_setup_device):
 more levels and a higher operator complexity for fewer iterations (profiles/match_case.md has what that costs in time).
+The classical (Ruge-Stueben) half of the family stands beside the aggregations: a C/F splitting of the strength pattern
+(bhs_csr_cfsplit_device; "C/F splitting and interpolation": the greedy maximal independent set under the PMIS measure), the
+direct interpolation on it as a symbolic / numeric pair (bhs_csr_interp_symbolic_device, bhs_csr_interp_numeric_device) and
+the hierarchy of the two (rs_setup_device; profiles/cf_case.md).
 Beside it: the level sets of a triangle, the sparse triangular solve and ILU(0) in place (bhs_csr_levels_device, bhs_csr_trsv_device, bhs_csr_ilu0_device; "triangular solve and ILU(0)") and CG
 preconditioned with that factorisation in natural or colour order (ilu0_pcg_device).
 
@@ -127,6 +131,104 @@ def pairwise_aggregate_device(handles, n, A, passes=2, seed=0):
     if agg is None:
         agg = torch.arange(n, dtype=torch.int32, device=A[0].device)
     return agg.to(torch.int32).contiguous(), m, info
+
+
+# ---------------------------------------------------------------- C/F splitting and direct interpolation
+def cfsplit_raw_device(bh, n, nnzS, d_rowPtrS, d_colIndS, d_prio, seed, flags, d_cf, d_cpts):
+    """bhs_csr_cfsplit_device on caller-given arrays, the C arguments in order (d_prio and d_cpts may be None): the status code;
+    sets bh.cfsplit_ms, bh.cfsplit_nc and bh.cfsplit_rounds on success."""
+    if bh._h is None:
+        return _lib.BHS_ERR_NOT_READY
+    nc, rounds, ms = C.c_int(0), C.c_int(0), C.c_double(0)
+    err = bh._lib.bhs_csr_cfsplit_device(bh._h, int(n), int(nnzS), _ptr(d_rowPtrS), _ptr(d_colIndS), _ptr(d_prio),
+                                         int(seed) & 0xFFFFFFFF, int(flags), _ptr(d_cf), _ptr(d_cpts), C.byref(nc),
+                                         C.byref(rounds), C.byref(ms))
+    if err == _lib.BHS_SUCCESS:
+        bh.cfsplit_ms, bh.cfsplit_nc, bh.cfsplit_rounds = float(ms.value), int(nc.value), int(rounds.value)
+    return err
+
+
+def cfsplit_device(bh, n, S, seed=0, prio=None, degree=True):
+    """The C/F splitting of the n x n pattern S = (rowPtr, colInd[, anything]) of strong connections, torch tensors on the
+    handle's GPU: the greedy maximal independent set in descending key order.  degree (the default; not with prio): the key's
+    priority is the row's length over the hash of (vertex, seed), the PMIS measure; else prio as in aggregate_device.
+    Returns (cf int32[n], nc, cpts int32[nc]): the coarse index of every C point, -1 at an F point, and the C points,
+    ascending, cf[cpts[c]] == c.  bh.cfsplit_rounds and bh.cfsplit_ms hold the rounds and the device time.  Raises
+    BhsparseError on failure."""
+    import torch
+    Sp, Sj = S[0], S[1]
+    cf = _alloc(n, torch.int32, Sp.device)
+    cpts = _alloc(n, torch.int32, Sp.device)
+    flags = _lib.BHS_CF_DEGREE if degree and prio is None else 0
+    torch.cuda.synchronize()                           # the library works on its own stream (see facade.initData_device)
+    _check(cfsplit_raw_device(bh, n, Sj.numel(), Sp, Sj if Sj.numel() else None, prio, seed, flags, cf, cpts),
+           "bhs_csr_cfsplit_device")
+    return cf[:n], bh.cfsplit_nc, cpts[:bh.cfsplit_nc]
+
+
+def interp_symbolic_raw_device(bh, n, nnzA, d_rowPtrA, d_colIndA, nnzS, d_rowPtrS, d_colIndS, d_cf, nc, d_rowPtrP):
+    """bhs_csr_interp_symbolic_device on caller-given arrays, the C arguments in order: the status code; sets
+    bh.interp_symbolic_ms and bh.interp_nnzP on success."""
+    if bh._h is None:
+        return _lib.BHS_ERR_NOT_READY
+    nnzP, ms = C.c_longlong(0), C.c_double(0)
+    err = bh._lib.bhs_csr_interp_symbolic_device(bh._h, int(n), int(nnzA), _ptr(d_rowPtrA), _ptr(d_colIndA), int(nnzS),
+                                                 _ptr(d_rowPtrS), _ptr(d_colIndS), _ptr(d_cf), int(nc), _ptr(d_rowPtrP),
+                                                 C.byref(nnzP), C.byref(ms))
+    if err == _lib.BHS_SUCCESS:
+        bh.interp_symbolic_ms, bh.interp_nnzP = float(ms.value), int(nnzP.value)
+    return err
+
+
+def interp_numeric_raw_device(bh, n, nnzA, d_rowPtrA, d_colIndA, d_valA, nnzS, d_rowPtrS, d_colIndS, d_cf, nc, d_rowPtrP, nnzP,
+                              d_colIndP, d_valP, flags=0):
+    """bhs_csr_interp_numeric_device on caller-given arrays, the C arguments in order: the status code; sets
+    bh.interp_numeric_ms on success."""
+    if bh._h is None:
+        return _lib.BHS_ERR_NOT_READY
+    ms = C.c_double(0)
+    err = bh._lib.bhs_csr_interp_numeric_device(bh._h, int(n), int(nnzA), _ptr(d_rowPtrA), _ptr(d_colIndA), _ptr(d_valA),
+                                                int(nnzS), _ptr(d_rowPtrS), _ptr(d_colIndS), _ptr(d_cf), int(nc),
+                                                _ptr(d_rowPtrP), int(nnzP), _ptr(d_colIndP), _ptr(d_valP), int(flags),
+                                                C.byref(ms))
+    if err == _lib.BHS_SUCCESS:
+        bh.interp_numeric_ms = float(ms.value)
+    return err
+
+
+def _none_if_empty(t):
+    return t if t is not None and t.numel() else None
+
+
+def interp_values_device(bh, n, A, S, cf, nc, rowPtrP):
+    """The numeric call alone on a kept pattern: (colIndP, valP) of the direct interpolation for the row pointer an earlier
+    interp_direct_device returned on the same patterns and cf -- A's values may have changed.  bh.interp_numeric_ms holds
+    the device time.  Raises BhsparseError on failure (a row pointer of another splitting among them)."""
+    import torch
+    nnzP = int(rowPtrP[n]) if n else 0
+    Pj = _alloc(nnzP, torch.int32, A[0].device)
+    Px = _alloc(nnzP, _tdt(bh), A[0].device)
+    torch.cuda.synchronize()                           # the library works on its own stream (see facade.initData_device)
+    _check(interp_numeric_raw_device(bh, n, A[1].numel(), A[0], _none_if_empty(A[1]), _none_if_empty(A[2]), S[1].numel(), S[0],
+                                     _none_if_empty(S[1]), cf, nc, rowPtrP, nnzP, Pj, Px), "bhs_csr_interp_numeric_device")
+    return Pj[:nnzP], Px[:nnzP]
+
+
+def interp_direct_device(bh, n, A, S, cf, nc):
+    """The direct interpolation P (n x nc) of the n x n matrix A = (rowPtr, colInd, val) on the splitting cf (what
+    cfsplit_device returned) and the pattern S = (rowPtr, colInd) of strong connections, rows of both strictly ascending:
+    an identity row at a C point, at an F point the weights of include/bhsparse_hip.h ("C/F splitting and interpolation") on
+    its strong C neighbours.  Returns (rowPtr, colInd, val); bh.interp_ms is the device time of the symbolic and the numeric
+    call.  Raises BhsparseError on failure."""
+    import torch
+    Pp = _alloc(n + 1, torch.int32, A[0].device)
+    torch.cuda.synchronize()                           # the library works on its own stream (see facade.initData_device)
+    _check(interp_symbolic_raw_device(bh, n, A[1].numel(), A[0], _none_if_empty(A[1]), S[1].numel(), S[0], _none_if_empty(S[1]),
+                                      cf, nc, Pp), "bhs_csr_interp_symbolic_device")
+    Pp = Pp[:n + 1]
+    Pj, Px = interp_values_device(bh, n, A, S, cf, nc, Pp)
+    bh.interp_ms = bh.interp_symbolic_ms + bh.interp_numeric_ms
+    return Pp, Pj, Px
 
 
 # ---------------------------------------------------------------- colouring and relaxation
@@ -306,10 +408,12 @@ def sa_setup_device(handles, n, A, theta=0.0, omega=2.0 / 3.0, max_levels=10, mi
     return _setup_levels(handles, n, A, coarsen, omega, max_levels, min_coarse)
 
 
-def _setup_levels(handles, n, A, coarsen, omega, max_levels, min_coarse):
-    """The level loop of sa_setup_device and pa_setup_device: coarsen(h1, h2, n, A, level) -> (agg, nagg, what the level's
-    record says of it), then tentative -> smoothed prolongator -> Galerkin product, until max_levels, min_coarse rows or
-    fewer, or a level on which nothing is merged."""
+def _setup_levels(handles, n, A, coarsen, omega, max_levels, min_coarse, prolong=None, count="nagg"):
+    """The level loop of sa_setup_device, pa_setup_device and rs_setup_device: coarsen(h1, h2, n, A, level) -> (agg, nagg,
+    what the level's record says of it), then tentative -> smoothed prolongator -> Galerkin product, until max_levels,
+    min_coarse rows or fewer, or a level on which nothing is merged.  prolong (None: the tentative and the smoothed
+    prolongator): prolong(h1, n, A, agg, nagg) -> (P, what the record says of it) in their place; count: the record's key
+    for the coarse size."""
     own = callable(handles)
     h1, h2 = (handles(), handles()) if own else handles
     try:
@@ -322,12 +426,17 @@ def _setup_levels(handles, n, A, coarsen, omega, max_levels, min_coarse):
             agg, nagg, said = coarsen(h1, h2, n, A, len(levels))
             if nagg >= n:
                 break
-            T, _ = tentative_device(h1, n, agg, nagg)
-            P = smoothed_prolongator_device(h1, n, nagg, A, T, omega)
+            if prolong is None:
+                T, _ = tentative_device(h1, n, agg, nagg)
+                P = smoothed_prolongator_device(h1, n, nagg, A, T, omega)
+                timing = {"prolongator_ms": h1.prolongator_ms}
+            else:
+                P, timing = prolong(h1, n, A, agg, nagg)
             Ac, R = galerkin_device(h1, h2, n, nagg, A, P)
-            rec.update({"nagg": nagg})
+            rec.update({count: nagg})
             rec.update(said)
-            rec.update({"prolongator_ms": h1.prolongator_ms, "galerkin_ms": h1.galerkin_ms})
+            rec.update(timing)
+            rec.update({"galerkin_ms": h1.galerkin_ms})
             levels.append((A, P, R))
             A, n = Ac, nagg
         levels.append((A, None, None))
@@ -355,6 +464,38 @@ def pa_setup_device(handles, n, A, passes=3, omega=2.0 / 3.0, max_levels=10, min
         ms = sum(r["match_ms"] + r.get("galerkin_ms", 0.0) for r in said)
         return agg, nagg, {"passes": said, "aggregate_ms": ms}
     return _setup_levels(handles, n, A, coarsen, omega, max_levels, min_coarse)
+
+
+def rs_setup_device(handles, n, A, theta=0.25, max_levels=10, min_coarse=40, seed=0):
+    """The classical (Ruge-Stueben) hierarchy of the n x n matrix A = (rowPtr, colInd, val), rows strictly ascending: per
+    level strength_device(theta) -> cfsplit_device (the PMIS measure, seed + 8 * level) -> interp_direct_device ->
+    A_c = P^T (A P).  handles, the stopping rules and (levels, info) as sa_setup_device; a level's record holds n, nnz and,
+    where it was coarsened, nc, rounds and the device ms of strength / split / interp / galerkin.  P has an identity row at
+    every C point and no more entries a row than the strength pattern, so the coarse operators stay sparse where the smoothed
+    prolongator's grow.  vcycle_device, smoother_setup_device, solve_device and pcg_device run on it unchanged
+    (profiles/cf_case.md has what it costs and where it loses)."""
+    kept = {}
+
+    def coarsen(h1, h2, n, A, lvl):
+        S = strength_device(h1, n, A, theta)
+        cf, nc, _ = cfsplit_device(h1, n, S, seed + 8 * lvl)
+        kept["S"] = S
+        return cf, nc, {"rounds": h1.cfsplit_rounds, "strength_ms": h1.strength_ms, "split_ms": h1.cfsplit_ms}
+
+    def prolong(h1, n, A, cf, nc):
+        P = interp_direct_device(h1, n, A, kept.pop("S"), cf, nc)
+        return P, {"interp_ms": h1.interp_ms}
+    return _setup_levels(handles, n, A, coarsen, None, max_levels, min_coarse, prolong, "nc")
+
+
+def rs_setup_csr(n, Ap, Aj, Ax, theta=0.25, max_levels=10, min_coarse=40, seed=0, value_dtype=np.float64, device=0):
+    """Convenience: rs_setup_device on a host CSR matrix (rows strictly ascending), built on the device and copied back, as
+    sa_setup_csr."""
+    A = _device_csr(Ap, Aj, Ax, value_dtype, device)
+    with _handle(value_dtype, device, None) as h1, _handle(value_dtype, device, None) as h2:
+        levels, info = rs_setup_device((h1, h2), n, A, theta, max_levels, min_coarse, seed)
+    host = lambda M: None if M is None else _host(*M)   # noqa: E731
+    return [(host(a), host(p), host(r)) for a, p, r in levels], info
 
 
 def pa_setup_csr(n, Ap, Aj, Ax, passes=3, omega=2.0 / 3.0, max_levels=10, min_coarse=40, seed=0, value_dtype=np.float64,

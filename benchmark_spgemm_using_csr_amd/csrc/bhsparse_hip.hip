@@ -418,6 +418,9 @@ struct bhs_handle {
     // the spanning forest (bhs_host_forest.inc.h): the trees' picks, the slot bitmap, the slots, parent and the scanned offsets
     // in its queue buffer, the written slots per bitmap word in its count buffer
     SideWs sfWs;
+    // the C/F splitting and the interpolation (bhs_host_cfsplit.inc.h): the two word arrays, the C-point bitmap and the scanned
+    // offsets in its queue buffer, the C points per bitmap word -- or the entries per row of P -- in its count buffer
+    SideWs cfWs;
 };
 
 namespace {
@@ -590,6 +593,7 @@ inline int one_launch(int rc) { return rc != BHS_SUCCESS ? rc : 1; }
 #include "bhs_host_components.inc.h"
 #include "bhs_host_match.inc.h"
 #include "bhs_host_forest.inc.h"
+#include "bhs_host_cfsplit.inc.h"
 #include "bhs_host_transpose.inc.h"
 #include "bhs_host_reduce.inc.h"
 #include "bhs_host_semiring.inc.h"

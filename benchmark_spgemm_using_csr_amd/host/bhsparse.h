@@ -181,6 +181,25 @@ public:
                                    const value_type *d_valA, int flags, index_type *d_label, index_type *d_edgeLo,
                                    index_type *d_edgeHi, value_type *d_edgeVal, int *nedges_out, int *rounds_out);
 
+    // EXTENSION, not part of the reference's API: the C/F splitting of an n x n pattern S of strong connections on DEVICE
+    // arrays (bhs_csr_cfsplit_device; include/bhsparse_hip.h, "C/F splitting and interpolation").  d_prio may be null: the
+    // hash of (vertex, seed); flags: 0 or BHS_CF_DEGREE (not with d_prio).  d_cf (n ints) receives the coarse index of every
+    // C point and -1 at an F point, d_cpts (room for n ints, may be null) the *nc_out C points, ascending.  *rounds_out is a
+    // function of the input.  Needs initPlatform only.
+    int csr_cfsplit_device(int n, int nnzS, const index_type *d_rowPtrS, const index_type *d_colIndS, const unsigned *d_prio,
+                           unsigned seed, int flags, index_type *d_cf, index_type *d_cpts, int *nc_out, int *rounds_out);
+
+    // EXTENSION, not part of the reference's API: the direct interpolation P (n x nc) of A on the splitting d_cf and the
+    // pattern S, a symbolic / numeric pair on DEVICE arrays (bhs_csr_interp_symbolic_device, bhs_csr_interp_numeric_device;
+    // same heading).  Rows of A and S strictly ascending.  The symbolic call fills d_rowPtrP (n + 1 ints) and *nnzP_out; the
+    // numeric call d_colIndP and d_valP (nnzP each) and may be repeated with new values of A.  Need initPlatform only.
+    int csr_interp_symbolic_device(int n, int nnzA, const index_type *d_rowPtrA, const index_type *d_colIndA, int nnzS,
+                                   const index_type *d_rowPtrS, const index_type *d_colIndS, const index_type *d_cf, int nc,
+                                   index_type *d_rowPtrP, long long *nnzP_out);
+    int csr_interp_numeric_device(int n, int nnzA, const index_type *d_rowPtrA, const index_type *d_colIndA, const value_type *d_valA,
+                                  int nnzS, const index_type *d_rowPtrS, const index_type *d_colIndS, const index_type *d_cf, int nc,
+                                  const index_type *d_rowPtrP, long long nnzP, index_type *d_colIndP, value_type *d_valP);
+
     // EXTENSION, not part of the reference's API: the multiply over a semiring (bhs_spgemm_semiring*, include/bhsparse_hip.h,
     // "semiring multiply"; semiring: a BHS_SR_* constant) on the data of initData.  spgemm_semiring is the full product: it
     // fills the csrRowPtrC of initData, and get_nnzC / get_C then return A (+).(x) B on the pattern of A·B.
@@ -447,6 +466,33 @@ inline int bhsparse::csr_spanning_forest_device(int n, int nnzA, const index_typ
     if (!_h) return BHS_ERR_NOT_READY;
     return bhs_csr_spanning_forest_device(_h, n, nnzA, d_rowPtrA, d_colIndA, d_valA, flags, d_label, d_edgeLo, d_edgeHi, d_edgeVal,
                                           nedges_out, rounds_out, 0);
+}
+
+inline int bhsparse::csr_cfsplit_device(int n, int nnzS, const index_type *d_rowPtrS, const index_type *d_colIndS,
+                                        const unsigned *d_prio, unsigned seed, int flags, index_type *d_cf, index_type *d_cpts,
+                                        int *nc_out, int *rounds_out)
+{
+    if (!_h) return BHS_ERR_NOT_READY;
+    return bhs_csr_cfsplit_device(_h, n, nnzS, d_rowPtrS, d_colIndS, d_prio, seed, flags, d_cf, d_cpts, nc_out, rounds_out, 0);
+}
+
+inline int bhsparse::csr_interp_symbolic_device(int n, int nnzA, const index_type *d_rowPtrA, const index_type *d_colIndA, int nnzS,
+                                                const index_type *d_rowPtrS, const index_type *d_colIndS, const index_type *d_cf,
+                                                int nc, index_type *d_rowPtrP, long long *nnzP_out)
+{
+    if (!_h) return BHS_ERR_NOT_READY;
+    return bhs_csr_interp_symbolic_device(_h, n, nnzA, d_rowPtrA, d_colIndA, nnzS, d_rowPtrS, d_colIndS, d_cf, nc, d_rowPtrP, nnzP_out, 0);
+}
+
+inline int bhsparse::csr_interp_numeric_device(int n, int nnzA, const index_type *d_rowPtrA, const index_type *d_colIndA,
+                                               const value_type *d_valA, int nnzS, const index_type *d_rowPtrS,
+                                               const index_type *d_colIndS, const index_type *d_cf, int nc,
+                                               const index_type *d_rowPtrP, long long nnzP, index_type *d_colIndP,
+                                               value_type *d_valP)
+{
+    if (!_h) return BHS_ERR_NOT_READY;
+    return bhs_csr_interp_numeric_device(_h, n, nnzA, d_rowPtrA, d_colIndA, d_valA, nnzS, d_rowPtrS, d_colIndS, d_cf, nc, d_rowPtrP,
+                                         nnzP, d_colIndP, d_valP, 0, 0);
 }
 
 inline int bhsparse::get_nnzC()

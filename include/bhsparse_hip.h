@@ -668,6 +668,116 @@ BHS_API int bhs_csr_spmm_semiring_device(bhs_handle *h, int semiring, int m, int
         bhs_value_t *d_Y /* m x k, in/out */, long long ldY /* >= k */, long long *changed_out /* may be NULL */,
         double *ms_out /* may be NULL */);
 
+/* ---- C/F splitting and interpolation ----------------------------------------
+ * The other half of algebraic multigrid: classical (Ruge-Stueben) coarsening splits the vertices of an n x n pattern S of
+ * strong connections into coarse (C) and fine (F) points, and the interpolation P (n x nc) has an identity row at every C
+ * point and, at an F point, weights on its strong C neighbours (no reference counterpart; bhs_cfsplit.hip.h,
+ * bhs_interp.hip.h).  Beside the two aggregations ("aggregation", "matching") the Galerkin operators stay sparse: P has no more entries a row than
+ * S has.  amg.rs_setup_device builds the hierarchy.
+ *
+ * bhs_csr_cfsplit_device.  S is 0-based int32 CSR; values are NOT TAKEN, so the double and the float library run the same
+ * code.
+ * Neighbours and keys are the aggregation's.  N(i) is the set of columns of row i of S; the diagonal, repeated columns and
+ *   the order inside a row make no difference; rows need not be sorted.  Vertex i has the key prio31(i) << 31 | i:
+ *   prio31(i) = d_prio[i] >> 1 where d_prio is given, else h(i, seed) >> 1 of the aggregation's hash.  With BHS_CF_DEGREE
+ *   (d_prio must be NULL, else BHS_ERR_INVALID_ARG)
+ *       prio31(i) = min(rowPtrS[i+1] - rowPtrS[i], 1023) << 21 | h(i, seed) >> 11,
+ *   the PMIS measure on a symmetric strength pattern: many dependants first, ties by hash, then by index.  Keys are distinct.
+ * Result.  For a structurally symmetric S the C points are THE greedy maximal independent set in descending key order: a
+ *   vertex is C exactly when no off-diagonal neighbour of greater key is C.  That set is unique; every F point has a C
+ *   neighbour, no two C points are neighbours, an isolated vertex is C.  C points are numbered in ascending vertex order:
+ *   d_cf[i] is the coarse index in [0, nc) of a C point and -1 for an F point, d_cpts (may be NULL) the C points, ascending,
+ *   d_cf[d_cpts[c]] == c.  With the same d_prio or seed (no BHS_CF_DEGREE) d_cf[i] >= 0 exactly where bhs_csr_color_device
+ *   gives colour 0.
+ * Non-symmetric S.  The call still ends and every vertex is C or F; which one, is unspecified.
+ * Rounds, synchronous over one word a vertex, state << 62 | key (undecided 1, in 2, out 0); a round reads one array of
+ *   words and writes another.  For every undecided i, m is the maximum of the words over i and N(i): m's state is in: i is
+ *   out; m is i's own word: i is in; else i stays undecided.  The undecided vertex of greatest key is decided in every
+ *   round.  The host reads the error word and the count of undecided vertices once a round, one round trip; *rounds_out is
+ *   the number of rounds until nobody is undecided, a function of the input (a path whose keys ascend with the index takes
+ *   n, the worst case; grids and random patterns of a million vertices take about ten, profiles/cf_case.md).  The call returns
+ *   BHS_ERR_INTERNAL when a round decides nothing or after n + 1 rounds; nothing spins on the device, no workgroup waits for
+ *   another.
+ * Numbering.  The C points are flagged per 64 vertices as a bitmap word, the words' counts go through the library's one-pass
+ *   scan as the aggregation's roots do, a C point's number is its word's first number plus the C points below it in the word.
+ *   No atomic touches a result.
+ * Reproducibility.  The result is a function of (pattern, priorities or seed, flags) alone: the same bits from run to run,
+ *   from handle to handle, and in the double and the float library.
+ * Validation, on the device, each check ahead of the dependent read: rowPtrS[i] > rowPtrS[i+1] or either outside
+ *   [0, nnzS]; a column outside [0, n).  On the host: a NULL handle, negative n or nnzS, a flag other than BHS_CF_DEGREE,
+ *   BHS_CF_DEGREE with d_prio, NULL d_rowPtrS or d_cf with n > 0, NULL d_colIndS with nnzS > 0, the footprint of d_cf or
+ *   d_cpts (n ints each) overlapping S, d_prio or each other, and a call between bhs_spgemm_symbolic and bhs_spgemm_finish.
+ *   Each returns BHS_ERR_INVALID_ARG; the host's refusals leave the outputs untouched, after a refusal by the device they are
+ *   unspecified; nothing beyond their stated sizes is ever written, nothing stays queued.
+ * n == 0 succeeds with *nc_out = 0, *rounds_out = 0 and *ms_out = 0 and launches nothing.
+ * Synchronous on the handle's stream, needs no bound data, leaves the handle as it was (a workspace of its own, shared with
+ *   the interpolation).  ms_out (may be NULL): device time of the call, the rounds' round trips included.
+ *   bhs_get_kernel_stats then reports cf_init (keys, the row pointer's validation), cf_round (the gather of a round, a row
+ *   spread over 1, 4, 16 or 64 lanes by the pattern's mean row length) and cf_number (the C points counted per 64 vertices,
+ *   the scan, the numbering).                                                                                        */
+#define BHS_CF_DEGREE 1
+BHS_API int bhs_csr_cfsplit_device(bhs_handle *h, int n, int nnzS,
+        const int *d_rowPtrS, const int *d_colIndS /* n x n pattern of strong connections; values are not taken */,
+        const unsigned *d_prio /* n caller priorities, or NULL: the hash */,
+        unsigned seed, int flags /* 0 or BHS_CF_DEGREE */,
+        int *d_cf /* out: n ints, the coarse index in [0, nc) of a C point, -1 for an F point */,
+        int *d_cpts /* out, may be NULL: the C points, ascending; room for n ints */,
+        int *nc_out /* may be NULL */, int *rounds_out /* may be NULL */, double *ms_out /* may be NULL */);
+
+/* bhs_csr_interp_symbolic_device / bhs_csr_interp_numeric_device.  Direct interpolation P (n x nc) of the n x n matrix A on
+ * the splitting d_cf (nc C points) and the pattern S of strong connections, as a symbolic / numeric pair with pattern reuse
+ * like the add, the selection and the extraction: the pattern is a function of the patterns of A and S and of d_cf alone, so
+ * the symbolic call takes no values and the numeric call may be repeated on a kept pattern with new values.
+ * Input order.  Rows of A and of S are strictly ascending; checked on the device, else BHS_ERR_INVALID_ARG.
+ * Interpolatory set.  C_i = { j != i : (i, j) is stored in A, j is in row i of S, d_cf[j] >= 0 } (membership in S's row: a
+ *   binary search in the sorted row).
+ * Pattern.  A C point's row is the single entry (d_cf[i], 1).  An F point's row has one entry d_cf[j] per j in C_i, in
+ *   ascending j: P's rows are strictly ascending.  C_i may be empty on non-symmetric input; that row is empty.  An explicit
+ *   zero a_ij keeps its entry, with value 0.
+ * Values, in double with one rounding to the value type.  d = a_ii, or 0 where the diagonal is not stored.  An off-diagonal
+ *   entry is of negative type where a_ij d < 0 and of positive type where a_ij d > 0.  N- and N+ are the sums over ALL
+ *   off-diagonal entries of each type, C- and C+ the sums over C_i of each type.  d' = d, plus N+ where C+ == 0, plus N-
+ *   where C- == 0, added in that order.  Then
+ *       w_ij = -((N- / C-) a_ij) / d' for a negative-type j,   w_ij = -((N+ / C+) a_ij) / d' for a positive-type j,
+ *   evaluated exactly in that order; an entry of neither type (a_ij d is 0 or NaN: an explicit zero, a diagonal that is not
+ *   stored) carries none of either sum, w_ij = -(0 a_ij) / d'.  Where d' is 0 the IEEE results stand (a row of A without its
+ *   diagonal gives NaNs).  Where A's row sums to 0 and every sign has a coarse representative, P's row sums to 1.
+ *   The sums follow the SpMV's rule: a row is spread over 1, 4, 16 or 64 lanes by A's mean row length, a lane adds its
+ *   entries in row order, the lanes meet in a butterfly -- the order depends on the row's length and the lanes a row alone,
+ *   two calls give the same bits.
+ * Symbolic.  Counts the entries of every row, scans the counts with the library's one-pass scan into d_rowPtrP (n + 1 ints)
+ *   and returns *nnzP_out; one round trip for the error word and nnzP.  nnzP beyond INT_MAX: BHS_ERR_ALLOC.  After a refusal
+ *   by the device d_rowPtrP is untouched.
+ * Numeric.  Recomputes each row's count and compares it with rowPtrP (rowPtrP[0] == 0 and rowPtrP[n] == nnzP too); any
+ *   disagreement returns BHS_ERR_INVALID_ARG with nothing written.  The fill writes entry k of row i only where
+ *   k < rowPtrP[i+1] - rowPtrP[i] and rowPtrP[i] + k < nnzP: whatever the arrays hold, nothing is read or written out of
+ *   bounds.  flags must be 0.
+ * Validation, on the device, each check ahead of the dependent read or write: the row pointers of A, S and (numeric) P as
+ *   the aggregation checks S's; a column of A or S outside [0, n); a row of A or S that does not ascend strictly; a d_cf
+ *   value outside [-1, nc).  On the host: a NULL handle, negative n, nnzA, nnzS, nc or nnzP, nc > n, nnzP beyond INT_MAX,
+ *   flags != 0, NULL arrays where sizes are positive (d_rowPtrA, d_rowPtrS, d_cf and d_rowPtrP with n > 0 -- d_rowPtrP of
+ *   the symbolic call always --, d_colIndA and d_valA with nnzA > 0, d_colIndS with nnzS > 0, d_colIndP and d_valP with
+ *   nnzP > 0), an output's footprint overlapping an input or another output, and a call between bhs_spgemm_symbolic and
+ *   bhs_spgemm_finish.  Each returns BHS_ERR_INVALID_ARG; the host's refusals leave the outputs untouched.
+ * n == 0: the symbolic call writes d_rowPtrP[0] = 0 and returns *nnzP_out = 0, the numeric call accepts nnzP == 0 alone; both
+ *   launch no kernel.
+ * Synchronous on the handle's stream, need no bound data, leave the handle as it was (the splitting's workspace).  ms_out
+ *   (may be NULL): device time of the call.  bhs_get_kernel_stats then reports interp_count (validation, the rows' counts and
+ *   their scan) and interp_fill (the sums, the entries).                                                             */
+BHS_API int bhs_csr_interp_symbolic_device(bhs_handle *h, int n, int nnzA,
+        const int *d_rowPtrA, const int *d_colIndA,
+        int nnzS, const int *d_rowPtrS, const int *d_colIndS,
+        const int *d_cf /* n ints in [-1, nc) */, int nc,
+        int *d_rowPtrP /* out: n + 1 ints */,
+        long long *nnzP_out /* may be NULL */, double *ms_out /* may be NULL */);
+BHS_API int bhs_csr_interp_numeric_device(bhs_handle *h, int n, int nnzA,
+        const int *d_rowPtrA, const int *d_colIndA, const bhs_value_t *d_valA,
+        int nnzS, const int *d_rowPtrS, const int *d_colIndS,
+        const int *d_cf /* n ints in [-1, nc) */, int nc,
+        const int *d_rowPtrP /* the symbolic call's */, long long nnzP,
+        int *d_colIndP /* out: nnzP ints */, bhs_value_t *d_valP /* out: nnzP values */,
+        int flags /* must be 0 */, double *ms_out /* may be NULL */);
+
 /* ---- spanning forest --------------------------------------------------------
  * The minimum (or maximum) spanning forest of the graph that an n x n matrix A stores, by Boruvka rounds on the device: for
  * network design, as the spanning tree under a support-graph or tree preconditioner (the MAXIMUM forest of |a_ij| is the
