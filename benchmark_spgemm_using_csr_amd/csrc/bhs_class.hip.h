@@ -56,7 +56,8 @@ enum { CS_MAXRING = 0 /* most staged B values any class's ring needs (bhs_class_
        CS_HEADS = 8 + 2 * kClassSumSlots + 5 /* rows of A that went through the class table (k_class_rows on the heads' lists) */,
        CS_RINGFULL = 8 + 2 * kClassSumSlots + 6 /* bhs_class_ring.hip.h: most values of a ring of (longest chain + 1) slabs among the classes whose ring fits kClassRingBudget */,
        CS_RINGONE = 8 + 2 * kClassSumSlots + 7 /* ... most values of (longest chain) slabs among the others (their rows load what they need, row by row); 0x7fffffff: some class cannot */,
-       CS_INTS = 8 + 2 * kClassSumSlots + 8 };
+       CS_KEEPFLAG = 8 + 2 * kClassSumSlots + 8 /* kept columns (k_class_patterns, k_class_scan): 1 a row whose columns are not the kept ones, 2 a class without a kept twin */,
+       CS_INTS = 8 + 2 * kClassSumSlots + 10 };
 constexpr int kClassRingDma = kClassMaxP + 64 + kClassMaxNnz;      // classRing: where the slab-load words of bhs_class_ring.hip.h's kernel begin (kClassMaxLoads x 64, then the slab's size)
 constexpr int kClassRingStride = kClassRingDma + 4 * 64 + 4;       // words per class of classRing: 16 steps x 64 lanes, a word per lane, the relative columns in pairs, the slab loads
 constexpr int kClassColourUnits = 128;                             // slabs of up to this many 16-byte units get their units coloured over the bank groups
@@ -112,7 +113,8 @@ __global__ __launch_bounds__(kClassRowsBlock) void k_class_rows(int nrows, const
                                                     const int* __restrict__ range,     // rows [range[0], range[1]] only (nullptr: all)
                                                     const int* __restrict__ rowList,   // nullptr: all rows; else the rows to classify: segment
                                                     const int* __restrict__ rowCount,  //   blockIdx.y of kClassHeadSegs lists (k_class_heads),
-                                                    int segCap)                        //   segCap slots apart, its length at rowCount[16 * segment]
+                                                    int segCap,                        //   segCap slots apart, its length at rowCount[16 * segment]
+                                                    int slotOffset = 0)                //   (tests, option "class_slot_offset": added to a row's home slot)
 {
     static_assert(G * E <= kClassMaxRowBig, "rows of up to kClassMaxRowBig entries");
     constexpr int PW = G * E > kClassMaxRow ? G * E : kClassMaxRow;   // entries per pattern of the block's class cache
@@ -259,7 +261,7 @@ __global__ __launch_bounds__(kClassRowsBlock) void k_class_rows(int nrows, const
                 if (cand && !(__ballot(cand && !same) & gmask)) { cls = (int)(tg >> 20); searching = false; }
             }
             const unsigned long long mine = ((unsigned long long)hr << 32) | (unsigned)row;
-            int s = (int)(hr & (kClassSlots - 1));
+            int s = (int)((hr + (unsigned)slotOffset) & (kClassSlots - 1));
             for (int probe = 0; probe < kClassProbe; ++probe) {
                 if (!__any(searching)) break;
                 // An entry changes once (empty -> final).  The load is device-coherent: a plain one could keep
@@ -630,6 +632,53 @@ constexpr int kClassSpanWords = 4096;                            // k_class_patt
 constexpr int kClassMaxSteps = kClassMaxP / 64;                  // steps of the stored map
 constexpr int kClassMaxLoads = 4;                                // LDS-direct loads per slab (64 lanes x 16 bytes each)
 
+// Kept columns (round 7): what the handle keeps of the last multiply that wrote every column of its colIndC (keepTab, ints)
+// and the per-step slot map into it.  A class number is a table slot -- whichever block won the CAS --, so the same pattern
+// may sit in another slot a multiply later: a class is named by the FIRST saved class whose entry count and relative-column
+// list are equal entry by entry (no hash decides anything; the count only saves comparisons).
+constexpr int kKeepMaxClasses = 256;
+enum { KT_COUNT = 0 /* classes the writing multiply had (beyond kKeepMaxClasses: the copy is incomplete and matches nothing) */,
+       KT_SLOT = 4 /* saved class c: its slot then */, KT_NNZ = KT_SLOT + kKeepMaxClasses /* its entries; its list: keepRel[c * kClassMaxNnz ..] */,
+       KT_CANON = KT_NNZ + kKeepMaxClasses /* kClassSlots: slot of the writing multiply -> first saved class with its list (-1: no class) */,
+       KT_MAP = KT_CANON + kClassSlots /* kClassSlots: slot of THIS multiply -> first saved class with its list (-1: none) */,
+       KT_INTS = KT_MAP + kClassSlots };
+// first saved class whose list equals rel[0 .. nnz) entry by entry, -1: none.  One wave; wave-uniform result.  Three
+// dependent round trips where few saved classes have as many entries: the table's head and counts, the candidates' lists
+// four at a time, all in flight together.
+__device__ __forceinline__ int keep_first_equal(const int* __restrict__ keepTab, const int* __restrict__ keepRel, int nnz,
+                                                const int* rel, int lane)
+{
+    static_assert(kKeepMaxClasses == 4 * 64, "four counts per lane");
+    const int count = keepTab[KT_COUNT];
+    int n4[4];
+#pragma unroll
+    for (int g = 0; g < 4; ++g) n4[g] = keepTab[KT_NNZ + g * 64 + lane];
+    if (count > kKeepMaxClasses) return -1;
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        unsigned long long cand = __ballot(g * 64 + lane < count && n4[g] == nnz);
+        while (cand) {
+            int c[4];
+            bool differs[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                c[k] = cand ? g * 64 + __builtin_ctzll(cand) : -1;
+                cand &= cand - (cand ? 1ull : 0ull);
+                differs[k] = false;
+            }
+            for (int e = lane; e < nnz; e += 64) {
+                const int mine = rel[e];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) differs[k] = differs[k] || (c[k] >= 0 && keepRel[(size_t)c[k] * kClassMaxNnz + e] != mine);
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (c[k] >= 0 && __ballot(differs[k]) == 0ull) return c[k];
+        }
+    }
+    return -1;
+}
+
 __global__ __launch_bounds__(256) void k_class_patterns(const unsigned long long* __restrict__ tableA,
                                                         const int* __restrict__ Ap, const int* __restrict__ Aj,
                                                         const int* __restrict__ Bp, const int* __restrict__ Bj,
@@ -638,7 +687,9 @@ __global__ __launch_bounds__(256) void k_class_patterns(const unsigned long long
                                                         int* __restrict__ classRel, int* __restrict__ classLane,
                                                         unsigned* __restrict__ classRing,   // nullptr: not wanted
                                                         int* __restrict__ stats,
-                                                        const int* __restrict__ rowCount = nullptr)   // round 6 (bhs_class_mix.hip.h): rows per class; a class of a few rows is not worked out (z = -1: its rows are irregular)
+                                                        const int* __restrict__ rowCount = nullptr,   // round 6 (bhs_class_mix.hip.h): rows per class; a class of a few rows is not worked out (z = -1: its rows are irregular)
+                                                        int* __restrict__ keepTab = nullptr,          // kept columns (round 7): this slot's class named by the first saved class with its list,
+                                                        const int* __restrict__ keepRel = nullptr)    //   keepTab[KT_MAP + s] (-1: no class here, or no such saved class: CS_KEEPFLAG)
 {
     __shared__ int keys[kClassMaxP], srt[kClassMaxP], pk[kClassMaxP];
     __shared__ int sIncl[kClassMaxRow], sB0[kClassMaxRow], scan[256];
@@ -646,6 +697,7 @@ __global__ __launch_bounds__(256) void k_class_patterns(const unsigned long long
     __shared__ unsigned char sUnitPos[4 * 64], sUnitOwner[4 * 64];          // a 16-byte unit of the slab -> its place (in units), and back
     const int tid = threadIdx.x, s = blockIdx.x;
     const unsigned long long v = tableA[s];
+    if (keepTab != nullptr && tid == 0) keepTab[KT_MAP + s] = -1;  // (whichever way this block ends; thread 0 alone writes the word)
     if (v == kClassEmpty) {
         if (tid == 0) classInfo[s] = make_int4(0, 0, 0, -1);
         return;
@@ -774,6 +826,13 @@ __global__ __launch_bounds__(256) void k_class_patterns(const unsigned long long
     }
     __syncthreads();
     for (int e = tid; e < nnz; e += 256) classRel[(size_t)s * kClassMaxNnz + e] = ulist[e];
+    if (keepTab != nullptr && tid < 64) {                          // (the first wave; the others go on)
+        const int c = keep_first_equal(keepTab, keepRel, nnz, ulist, tid);
+        if (tid == 0) {
+            if (c < 0) atomicOr(&stats[CS_KEEPFLAG], 2);
+            else keepTab[KT_MAP + s] = c;
+        }
+    }
     // second sort: the products by (position, product number) -- position << 10 | product
     for (int p = tid; p < N2; p += 256) {
         int sv = 0x7fffffff;
@@ -1076,12 +1135,15 @@ __global__ __launch_bounds__(256) void k_class_expand_columns(int n, int row0, c
 // ordering between words is needed).  A tile only waits for tiles with smaller tickets, which are running.
 // ---------------------------------------------------------------------------
 constexpr int kClassScanBlock = 1024, kClassScanPer = 8, kClassScanTile = kClassScanBlock * kClassScanPer;   // (few tiles: short look-backs)
+template <bool KEEP>
 __global__ __launch_bounds__(kClassScanBlock) void k_class_scan(int m, const int* __restrict__ classC, const int4* __restrict__ classInfo,
                                                     int* __restrict__ Cp, unsigned long long* __restrict__ state,
                                                     long long* __restrict__ totalOut, int* __restrict__ stats,
                                                     bool mixed,       // round 6 (bhs_class_mix.hip.h): a row without a class has its count in Cp already (the general pipeline's symbolic kernels)
                                                     const int* __restrict__ Ap, const int* __restrict__ ub, BinSpec numSpec,
-                                                    int* __restrict__ binCount)   // ... and is counted into its numeric bin here
+                                                    int* __restrict__ binCount,   // ... and is counted into its numeric bin here
+                                                    const int* __restrict__ prevClass,   // KEEP: every row's class in the multiply that wrote the columns now in colIndC,
+                                                    const int* __restrict__ keepTab)     // ... and the two maps (KT_CANON, KT_MAP) that name both by their lists
 {
     constexpr int NW = kClassScanBlock / 64;
     __shared__ int sTile, wsum[NW], hist[kMaxBins];
@@ -1096,10 +1158,19 @@ __global__ __launch_bounds__(kClassScanBlock) void k_class_scan(int m, const int
     int v[kClassScanPer], mine = 0;
     unsigned long long products = 0;
     bool pending = false;
+    [[maybe_unused]] bool moved = false;                            // KEEP: a row whose columns in colIndC are not provably this multiply's
 #pragma unroll
     for (int j = 0; j < kClassScanPer; ++j) {
         v[j] = 0;
         const int c = base + j < m ? classC[base + j] : -1;
+        if constexpr (KEEP) {
+            if (base + j < m) {
+                const int pc = prevClass[base + j];
+                const int now = (unsigned)c < (unsigned)kClassSlots ? keepTab[KT_MAP + c] : -1;
+                const int then = (unsigned)pc < (unsigned)kClassSlots ? keepTab[KT_CANON + pc] : -2;
+                moved = moved || now < 0 || now != then;
+            }
+        }
         if (c >= 0 && c != kClassDummy) {
             const int4 ci = classInfo[c];
             v[j] = ci.z > 0 ? ci.z : 0;
@@ -1113,6 +1184,12 @@ __global__ __launch_bounds__(kClassScanBlock) void k_class_scan(int m, const int
         mine += v[j];
     }
     if (pending) atomicOr(&stats[CS_FLAGS], 2);                    // (a big class nobody worked out: stale hints)
+    if constexpr (KEEP) {
+        // (one word for all: a wave that sees it set already adds nothing -- same-address atomics queue, profiles/r06 section 1)
+        if (__ballot(moved) != 0ull && (threadIdx.x & 63) == 0 &&
+            (__hip_atomic_load(&stats[CS_KEEPFLAG], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & 1) == 0)
+            atomicOr(&stats[CS_KEEPFLAG], 1);
+    }
     const int incl = wave_incl_scan_dpp(mine);
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) products += __shfl_xor(products, o, 64);
@@ -1173,15 +1250,54 @@ __global__ __launch_bounds__(kClassScanBlock) void k_class_scan(int m, const int
 // ---------------------------------------------------------------------------
 struct ClassSpecKey { int cs[CS_INTS]; long long nnzC; };
 __global__ __launch_bounds__(64) void k_class_spec_check(ClassSpecKey key, const int* __restrict__ stats, const long long* __restrict__ total,
-                                                         const int* __restrict__ err, int* __restrict__ word)
+                                                         const int* __restrict__ err, int* __restrict__ word,
+                                                         int* __restrict__ keepWord = nullptr)   // kept columns: the short ring instance's second go word (1: go)
 {
     const int i = threadIdx.x;
     bool ok = *err == 0 && *total == key.nnzC;
     // (the products' partial sums and the scan's ticket are not decisions: CS_SUMS .. CS_RANGE and CS_SCANTICKET are left out)
     for (int j = i; j < CS_INTS; j += 64)
-        if (!(j >= CS_SUMS && j < CS_RANGE) && j != CS_SCANTICKET) ok = ok && stats[j] == key.cs[j];
+        if (!(j >= CS_SUMS && j < CS_RANGE) && j != CS_SCANTICKET && j != CS_KEEPFLAG && j != CS_KEEPFLAG + 1) ok = ok && stats[j] == key.cs[j];
     const bool all = __ballot(!ok) == 0ull;
     if (i == 0) *word = all ? 1 : 2;
+    // ... no row flagged by k_class_scan, no class without a kept twin (k_class_patterns), and the figures above equal (equal
+    // per-row counts: equal rowPtrC)
+    if (i == 0 && keepWord != nullptr) *keepWord = (all && stats[CS_KEEPFLAG] == 0) ? 1 : 2;
+}
+
+// ---------------------------------------------------------------------------
+// Kept columns (round 7).  colIndC[rowPtrC[i] + e] = rel[class(i)][e] + i on the class path: a function of the row's class
+// and the class's list alone.  A multiply that wrote every column of the library's own colIndC through the ring kernel
+// leaves behind its per-row classes (the handle swaps two arrays, nothing is copied) and, here, a compact copy of its
+// classes' lists; the next multiply classifies every row anew as always, maps each of its classes to the saved class with
+// the same list (k_class_patterns), compares the rows' classes through that map (k_class_scan<true>), and if all agree
+// its ring kernel goes out without the column stores (k_class_spec_check: keepWord).
+// ---------------------------------------------------------------------------
+// after a multiply that wrote every column: the compact copy (keepTab[KT_COUNT] zero at launch) ...
+__global__ __launch_bounds__(64) void k_keep_save(const int4* __restrict__ classInfo, const int* __restrict__ classRel,
+                                                  int* __restrict__ keepTab, int* __restrict__ keepRel)
+{
+    const int s = blockIdx.x, lane = threadIdx.x;
+    const int4 ci = classInfo[s];
+    if (ci.w < 0) return;                                          // (no class in this slot)
+    int c = 0;
+    // (a class without a list -- beyond the limits, not worked out -- makes the copy unusable)
+    if (lane == 0) c = atomicAdd(&keepTab[KT_COUNT], (ci.z < 0 || ci.z > kClassMaxNnz) ? kKeepMaxClasses + 1 : 1);
+    c = __builtin_amdgcn_readfirstlane(c);
+    if (c >= kKeepMaxClasses || ci.z < 0 || ci.z > kClassMaxNnz) return;
+    if (lane == 0) { keepTab[KT_SLOT + c] = s; keepTab[KT_NNZ + c] = ci.z; }
+    for (int e = lane; e < ci.z; e += 64) keepRel[(size_t)c * kClassMaxNnz + e] = classRel[(size_t)s * kClassMaxNnz + e];
+}
+
+// ... and every slot's name: the first saved class with its list (behind k_keep_save)
+__global__ __launch_bounds__(64) void k_keep_canon(const int4* __restrict__ classInfo, const int* __restrict__ classRel,
+                                                   int* __restrict__ keepTab, const int* __restrict__ keepRel)
+{
+    const int s = blockIdx.x, lane = threadIdx.x;
+    const int4 ci = classInfo[s];
+    int c = -1;
+    if (ci.w >= 0 && ci.z >= 0 && ci.z <= kClassMaxNnz) c = keep_first_equal(keepTab, keepRel, ci.z, classRel + (size_t)s * kClassMaxNnz, lane);
+    if (lane == 0) keepTab[KT_CANON + s] = c;
 }
 
 // ---------------------------------------------------------------------------

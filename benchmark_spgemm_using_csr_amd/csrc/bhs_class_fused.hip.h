@@ -25,7 +25,8 @@ __global__ __launch_bounds__(kClassHeadsBlock) void k_class_fused(int nrows, con
                                                      const int* __restrict__ classB, int* __restrict__ classOut,
                                                      unsigned long long* __restrict__ table, int* __restrict__ stats, long long nnzR, int pieceRows,
                                                      const int* __restrict__ range,     // rows [range[0], range[1]] only (nullptr: all)
-                                                     int period)                        // a row is compared with the row `period` before it
+                                                     int period,                        // a row is compared with the row `period` before it
+                                                     int slotOffset = 0)                // (tests, option "class_slot_offset": added to a row's home slot)
 {
     constexpr int GPW = 64 / G;                                    // lane groups per wave
     constexpr int R = E >= 8 ? 2 : (E >= 4 ? 4 : 8);               // consecutive rows per lane group
@@ -230,7 +231,7 @@ __global__ __launch_bounds__(kClassHeadsBlock) void k_class_fused(int nrows, con
                 if (cand && !(__ballot(cand && !same) & gmask)) { cls[r] = (int)(tg >> 20); searching = false; }
             }
             const unsigned long long mine = ((unsigned long long)hr << 32) | (unsigned)row;
-            int s = (int)(hr & (kClassSlots - 1));
+            int s = (int)((hr + (unsigned)slotOffset) & (kClassSlots - 1));
             for (int probe = 0; probe < kClassProbe; ++probe) {
                 if (!__any(searching)) break;
                 unsigned long long v = kClassEmpty;                 // (device-coherent: an entry changes once, empty -> final)

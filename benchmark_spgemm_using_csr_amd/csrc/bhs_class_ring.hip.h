@@ -55,7 +55,10 @@ __device__ __forceinline__ void ring_end_step(unsigned long long mask, unsigned&
                  : "memory");
 }
 
-template <int MAXU, int MAXV, int MAXJ>
+// COLS = false (round 7, "kept columns"): the instance without the column stores and without the relA / relB loads -- colIndC
+// already holds what this launch would write there, proven on the device inside this multiply (k_class_patterns, k_class_scan,
+// k_class_spec_check: keepWord).  A compile-time switch: nothing in the row loop branches on it.
+template <int MAXU, int MAXV, int MAXJ, bool COLS = true>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MAXU >= 16 ? BHS_RING_WAVES_WIDE : BHS_RING_WAVES, 8))) void k_class_ring(
     int m, const int* __restrict__ Ap, const int* __restrict__ Aj, const value_t* __restrict__ Ax, long long nnzA,
     const int* __restrict__ Bp, const value_t* __restrict__ Bx, long long nnzB, const int* __restrict__ classC,
@@ -63,9 +66,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MAXU >= 16 ?
     const int* __restrict__ classLane, const int* __restrict__ Cp, int* __restrict__ Cj, value_t* __restrict__ Cx,
     int ringBytes, int accStride, int rowBase, int superRows, int chunkRows,     // m, Ap, classC, Cp are views of the rows [rowBase, rowBase + m)
     const int* __restrict__ specWord,                                             // launched before the host saw this multiply's classes (k_class_spec_check): go on only if 1
-    int* __restrict__ tickets)                                                    // 8 counters, zero at launch: the next super-run of every XCD's band (round 6)
+    int* __restrict__ tickets,                                                    // 8 counters, zero at launch: the next super-run of every XCD's band (round 6)
+    const int* __restrict__ keepWord)                                             // COLS = false: the second go word -- 1: every column this launch would write is in Cj already
 {
     if (specWord != nullptr && *specWord != 1) return;
+    if (!COLS && (keepWord == nullptr || *keepWord != 1)) return;
     extern __shared__ __attribute__((aligned(16))) unsigned char smemRaw[];
     // (the LDS addresses below are plain integers counted from 0: the dynamic area must be all the LDS this kernel has --
     // a compile-time constant, the test costs nothing)
@@ -145,7 +150,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MAXU >= 16 ?
     unsigned slot0 = 0;                                          // LDS address of the slot of the first entry that ends in this lane
     int tail = -1;                                               // the entry this lane's last running sum is added to (-1: none)
     constexpr int MAXW = (MAXV + 1) / 2;                         // pairs of store instructions per row: a lane writes two neighbouring entries
-    int relA[MAXW], relB[MAXW];                                  // their columns, relative to the row
+    [[maybe_unused]] int relA[MAXW], relB[MAXW];                 // their columns, relative to the row (COLS)
     int dma[MAXJ];                                               // this lane's 16 bytes of each load instruction of a slab (bhs_class.hip.h: classLane[256 ..])
     unsigned src[MAXJ];                                          // ... where its next piece comes from (values of B are counted in int32: nnzB < 2^31)
     unsigned stepB = 0, wrapB = 0;                               // bytes per slab, bytes of this class's ring
@@ -226,11 +231,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MAXU >= 16 ?
                 const unsigned slabV = classRing[(size_t)cls * kClassRingStride + kClassRingDma + 4 * 64];
 #pragma unroll
                 for (int j = 0; j < MAXJ; ++j) dma[j] = (int)classRing[(size_t)cls * kClassRingStride + kClassRingDma + j * 64 + lane];
+                if constexpr (COLS) {
 #pragma unroll
-                for (int w2 = 0; w2 < MAXW; ++w2) {                  // (beyond the row: never stored)
-                    const uint2 rp = *reinterpret_cast<const uint2*>(classRing + (size_t)cls * kClassRingStride + kClassMaxP + 64 + 2 * (w2 * 64 + lane));
-                    relA[w2] = (int)rp.x;
-                    relB[w2] = (int)rp.y;
+                    for (int w2 = 0; w2 < MAXW; ++w2) {              // (beyond the row: never stored)
+                        const uint2 rp = *reinterpret_cast<const uint2*>(classRing + (size_t)cls * kClassRingStride + kClassMaxP + 64 + 2 * (w2 * 64 + lane));
+                        relA[w2] = (int)rp.x;
+                        relB[w2] = (int)rp.y;
+                    }
                 }
                 __builtin_amdgcn_s_waitcnt(kWaitVm0);                // (so that no later wait has to cover these loads)
                 nA = __builtin_amdgcn_readfirstlane(ci.x);
@@ -375,7 +382,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MAXU >= 16 ?
             if (!oneRow) request_slab();
             BHS_TICK_CLS(11);
             {
-                int* const cjRow = Cj + (long long)out;
+                [[maybe_unused]] int* const cjRow = Cj + (long long)out;
                 value_t* const cxRow = Cx + (long long)out;
                 if (nnz >= 2) {
 #pragma unroll
@@ -383,12 +390,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MAXU >= 16 ?
                         const int q = w2 * 64 + lane;
                         if (2 * q < nnz) {                           // (an odd row's last lane: its neighbour's second entry once more, and the last)
                             const int e0 = min(2 * q, nnz - 2);
-                            class_store_c2_at(cjRow, (unsigned)e0 * (unsigned)sizeof(int), relA[w2] + row + rowBase, relB[w2] + row + rowBase);
+                            if constexpr (COLS) class_store_c2_at(cjRow, (unsigned)e0 * (unsigned)sizeof(int), relA[w2] + row + rowBase, relB[w2] + row + rowBase);
                             class_store_c2_at(cxRow, (unsigned)e0 * (unsigned)sizeof(value_t), (value_t)x0[w2], (value_t)x1[w2]);
                         }
                     }
                 } else if (nnz == 1 && lane == 0) {
-                    class_store_c_at(cjRow, 0u, relA[0] + row + rowBase);
+                    if constexpr (COLS) class_store_c_at(cjRow, 0u, relA[0] + row + rowBase);
                     class_store_c_at(cxRow, 0u, (value_t)x0[0]);
                 }
             }

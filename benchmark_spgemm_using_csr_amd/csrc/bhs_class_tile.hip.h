@@ -46,7 +46,8 @@ template <bool IS_A, int G, int E>
 __global__ __launch_bounds__(kClassTileBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_class_tile(int nrows, const int* __restrict__ Rp, const int* __restrict__ Rj,
                                                   const int* __restrict__ classB, int* __restrict__ classOut,
                                                   unsigned long long* __restrict__ table, int* __restrict__ stats, long long nnzR, int pieceRows,
-                                                  const int* __restrict__ range)     // rows [range[0], range[1]] only (nullptr: all)
+                                                  const int* __restrict__ range,     // rows [range[0], range[1]] only (nullptr: all)
+                                                  int slotOffset = 0)                // (tests, option "class_slot_offset": added to a row's home slot)
 {
     constexpr int LMAX = G * E;                                    // longest row that can have a class
     constexpr int GPW = 64 / G;                                    // heads through the table at a time
@@ -271,7 +272,7 @@ __global__ __launch_bounds__(kClassTileBlock) __attribute__((amdgpu_waves_per_eu
                 if (cand && !(__ballot(cand && !same) & gmask)) { cls = (int)(tg >> 20); searching = false; }
             }
             const unsigned long long mine = ((unsigned long long)hr << 32) | (unsigned)hrow;
-            int s = (int)(hr & (kClassSlots - 1));
+            int s = (int)((hr + (unsigned)slotOffset) & (kClassSlots - 1));
             for (int probe = 0; probe < kClassProbe; ++probe) {
                 if (!__any(searching)) break;
                 unsigned long long v = kClassEmpty;                 // (device-coherent: an entry changes once, empty -> final)

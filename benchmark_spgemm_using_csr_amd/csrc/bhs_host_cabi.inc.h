@@ -77,6 +77,7 @@ static int free_data(bhs_handle* h, bool keepOutput)
         release(h->sumCx);
     }
     h->sumActive = false;
+    h->keep.valid = false;                           // (kept columns: another data set's, or nobody's)
     h->dAp = h->dAj = h->dBp = h->dBj = nullptr;
     h->dAx = h->dBx = nullptr;
     h->hasData = h->hasC = h->ownAB = false;
@@ -107,6 +108,7 @@ int bhs_destroy(bhs_handle* h)
     release(h->spaRank);
     release(h->longList); release(h->longPart);
     release(h->classB); release(h->classC); release(h->classTab); release(h->classInfo);
+    release(h->classPrev); release(h->keepTab); release(h->keepRel);
     release(h->classHeads); release(h->classHeadCnt); release(h->classMap); release(h->classMapA); release(h->classRing); release(h->classRel); release(h->classLane);
     release(h->classBigIdx); release(h->classBigMap);
     release(h->mixList); release(h->classCount); release(h->laneBlockSums);
@@ -202,6 +204,7 @@ int bhs_warmup(bhs_handle* h)
     h->wantHostRowPtr = h->ownAB;      // host-pointer callers get rowPtrC back: warm that path up too
     const int rc = run_pipeline(h);
     h->wantHostRowPtr = false;
+    h->keep.valid = false;             // (kept columns: the first multiply proper writes every column)
     if (rc == BHS_SUCCESS && h->rowPtrStaged) BHS_HIP(hipEventSynchronize(h->evCopyDone));
     return rc;
 }
@@ -289,6 +292,7 @@ int bhs_spgemm_finish(bhs_handle* h, double stage_ms_out[4])
 int bhs_set_output_device(bhs_handle* h, int* d_colIndC, bhs_value_t* d_valC, int64_t capacity)
 {
     if (!h || capacity < 0 || ((d_colIndC == nullptr) != (d_valC == nullptr))) return BHS_ERR_INVALID_ARG;
+    h->keep.valid = false;             // (kept columns: a multiply into the caller's arrays leaves the pool's as they were, not as the classes say)
     h->extCj = d_colIndC;
     h->extCx = (value_t*)d_valC;
     h->extCap = d_colIndC ? (long long)capacity : 0;
@@ -393,6 +397,7 @@ int bhs_get_kernel_stats(bhs_handle* h, bhs_kernel_stat* out, int cap)
 int bhs_set_option(bhs_handle* h, const char* key, int64_t value)
 {
     if (!h || !key) return BHS_ERR_INVALID_ARG;
+    h->keep.valid = false;                                          // (kept columns: the multiply after any option writes every column)
     // (2: event pairs around the numeric kernels only -- what a roofline of the dominant kernel needs, at a fifth of the events;
     // timers decide nothing: what the next multiply may assume of the last one stands)
     if (!strcmp(key, "kernel_stats")) { h->kernelStats = (int)std::max<int64_t>(0, std::min<int64_t>(value, 2)); return BHS_SUCCESS; }
@@ -407,6 +412,8 @@ int bhs_set_option(bhs_handle* h, const char* key, int64_t value)
     h->classSpec.valid = false;                                     // (any other option may change what a multiply decides)
     h->laneSpec.valid = false;
     if (!strcmp(key, "spec_numeric")) { h->specNumeric = value ? 1 : 0; return BHS_SUCCESS; }
+    if (!strcmp(key, "keep_columns")) { h->keepColumns = value ? 1 : 0; return BHS_SUCCESS; }
+    if (!strcmp(key, "class_slot_offset")) { h->classSlotOffset = (int)(value & (kClassSlots - 1)); return BHS_SUCCESS; }   // (tests: class numbers change, classes do not)
     if (!strcmp(key, "class_tile_piece")) { h->classTilePiece = (int)std::max<long long>(0, std::min<long long>(value, 1 << 17)); return BHS_SUCCESS; }
     if (!strcmp(key, "class_tile")) { h->classTile = value ? 1 : 0; return BHS_SUCCESS; }
     if (!strcmp(key, "class_mixed")) { h->mixOn = value ? 1 : 0; h->classMixed = 0; if (h->classState < 0) h->classState = 0; return BHS_SUCCESS; }
@@ -487,6 +494,14 @@ int bhs_get_info(bhs_handle* h, const char* key, int64_t* value_out)
     if (!strcmp(key, "span_words")) { *value_out = h->ps.spanWPL; return BHS_SUCCESS; }   // bitmap words per lane of the last multiply's span kernels (0: hash kernels)
     if (!strcmp(key, "spec_launches")) { *value_out = h->specLaunches; return BHS_SUCCESS; }   // multiplies whose numeric kernel went out before the host saw the classes, so far
     if (!strcmp(key, "spec_refuted")) { *value_out = h->specRefuted; return BHS_SUCCESS; }     // ... of them, refuted on the device and run again
+    if (!strcmp(key, "class_of_row0")) {                                                       // (tests: the class NUMBER row 0 of A got in the last class-path multiply)
+        int v = -1;
+        if (h->classC.p && h->m > 0) { BHS_HIP(hipStreamSynchronize(h->stream)); BHS_HIP(hipMemcpy(&v, h->classC.p, sizeof(int), hipMemcpyDeviceToHost)); }
+        *value_out = v;
+        return BHS_SUCCESS;
+    }
+    if (!strcmp(key, "cols_kept")) { *value_out = h->colsKept; return BHS_SUCCESS; }           // multiplies whose ring kernel left colIndC as the last writing multiply made it (proven equal on the device)
+    if (!strcmp(key, "cols_refuted")) { *value_out = h->colsRefuted; return BHS_SUCCESS; }     // launches without column stores the device refuted: those multiplies ran again and wrote their columns
     if (!strcmp(key, "mixed_rows")) { *value_out = h->ps.mixed ? h->ps.mixRows : 0; return BHS_SUCCESS; }   // rows of the last multiply that went through the general kernels beside the class kernels
     if (!strcmp(key, "class_state")) { *value_out = h->classState < 0 ? -1 : (h->classMixed ? 2 : 1); return BHS_SUCCESS; }   // -1 general pipeline for good, 1 row classes, 2 row classes with irregular rows
     if (!strcmp(key, "max_row_a")) { *value_out = h->maxRowA; return BHS_SUCCESS; }

@@ -306,10 +306,19 @@ bool class_ring2_fits(bhs_handle* h)
     return l.ringBytes <= 32 * 1024 && l.bytes <= 40 * 1024;
 }
 
-template <int MAXU, int MAXV, int MAXJ>
+// COLS = false: the instance without column stores (kept columns, bhs_class.hip.h) -- only ever a speculative launch of the
+// clean flow on all rows into the pool whose colIndC the handle knows (symbolic_attempt: ps.keepLaunched)
+template <int MAXU, int MAXV, int MAXJ, bool COLS = true>
 int launch_class_ring_impl(bhs_handle* h, int r0, int r1)
 {
-    auto kern = k_class_ring<MAXU, MAXV, MAXJ>;
+    const bool whole = r0 == 0 && r1 == h->m && !h->extCj && !h->extCx && !h->lazyOut;
+    if constexpr (COLS) {
+        if (h->ps.keepLaunched && h->ps.specLaunched && !h->ps.mixed && whole && h->ps.ringLaunches == 0)
+            return launch_class_ring_impl<MAXU, MAXV, MAXJ, false>(h, r0, r1);
+        if (h->ps.keepLaunched) h->ps.keepLaunched = false;       // (any other launch writes its columns: whatever it is, it is not a keeping multiply)
+    }
+    h->ps.ringWhole = whole && h->ps.ringLaunches == 0;
+    auto kern = k_class_ring<MAXU, MAXV, MAXJ, COLS>;
     const Ring2Lds lds = class_ring2_lds(h);
     int perCU = 1;
     BHS_TRY(kernel_occupancy(h, reinterpret_cast<const void*>(kern), 64, lds.bytes, &perCU));
@@ -328,7 +337,8 @@ int launch_class_ring_impl(bhs_handle* h, int r0, int r1)
                        (long long)h->nnzA, h->dBp, h->dBx, (long long)h->nnzB, (const int*)h->classC.p + r0, (const int4*)h->classInfo.p,
                        (const unsigned*)h->classRing.p, (const int*)h->classRel.p, (const int*)h->classLane.p, (const int*)h->Cp.p + r0, out_cj(h),
                        out_cx(h), lds.ringBytes, lds.accStride, r0, superRows, chunkRows,
-                       h->ps.specLaunched ? (const int*)h->small.p + S_SPEC : (const int*)nullptr, (h->ringDynamic == 1 || (h->ringDynamic == 2 && h->ps.ringBeside)) ? (int*)h->small.p + S_RING_TICKETS : (int*)nullptr);
+                       h->ps.specLaunched ? (const int*)h->small.p + S_SPEC : (const int*)nullptr, (h->ringDynamic == 1 || (h->ringDynamic == 2 && h->ps.ringBeside)) ? (int*)h->small.p + S_RING_TICKETS : (int*)nullptr,
+                       COLS ? (const int*)nullptr : (const int*)h->small.p + S_KEEP);
     BHS_HIP(hipGetLastError());
     return BHS_SUCCESS;
 }

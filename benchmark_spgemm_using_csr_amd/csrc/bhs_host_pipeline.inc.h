@@ -2,6 +2,7 @@
 // (A part of bhsparse_hip.hip's translation unit: included there, inside its unnamed namespace where that applies.)
 
 constexpr int kSpecRefuted = -1000;      // pipeline_finish to run_pipeline_impl only: never leaves the library
+constexpr int kKeepRefuted = -1002;      // ... the same for the ring launch without column stores (kept columns): the figures stood, the columns did not
 
 // The host waits for h->stream in the middle of a multiply (the bins' counts, nnzC) and at its end.  hipStreamSynchronize puts
 // the thread to sleep when the wait is long, and waking it costs ~20 us -- of a multiply of 0.2 .. 2 ms, two or three times.
@@ -326,6 +327,10 @@ int hub_min_products(const bhs_handle* h)
     return (h->hubMin > 0 && h->useSpa && h->forcePath == 0 && h->maxTableLog2 >= 15 && h->n <= (1 << 25)) ? h->hubMin : 0;
 }
 
+// (tests, option "class_slot_offset": the classifiers' home slot moves by that much from one multiply to the next -- the same
+// patterns land in other slots, class NUMBERS change while the classes do not)
+int class_slot_seed(const bhs_handle* h) { return (int)((h->classSlotOffset * h->multiplies) & (kClassSlots - 1)); }
+
 // mixed: the flow of bhs_class_mix.hip.h -- B's single-row classes are pruned before A is classified, classes of a few rows
 // are not worked out, the irregular rows of A are listed and get their product counts (symSpec: their symbolic bins)
 int symbolic_class(bhs_handle* h, bool mixed, const BinSpec& symSpec)
@@ -412,22 +417,22 @@ int symbolic_class(bhs_handle* h, bool mixed, const BinSpec& symSpec)
                             blocksT = std::max<long long>(1, ((long long)n + perBlockT - 1) / perBlockT);
                         }
                         hipLaunchKernelGGL((k_class_tile<IS_A, GG, E>), dim3((unsigned)blocksT), dim3(kClassTileBlock), 0,
-                                           h->stream, n, Rp, Rj, cb, out, tab, cstats, (long long)(IS_A ? h->nnzA : h->nnzB), pieceT, rng);
+                                           h->stream, n, Rp, Rj, cb, out, tab, cstats, (long long)(IS_A ? h->nnzA : h->nnzB), pieceT, rng, class_slot_seed(h));
                         return (int)BHS_SUCCESS;
                     }
                 }
                 const long long perBlock = (long long)(kClassHeadsBlock / 64) * piece;
                 hipLaunchKernelGGL((k_class_fused<IS_A, GG, E>), dim3((unsigned)std::max<long long>(1, ((long long)n + perBlock - 1) / perBlock)), dim3(kClassHeadsBlock), 0,
-                                   h->stream, n, Rp, Rj, cb, out, tab, cstats, (long long)(IS_A ? h->nnzA : h->nnzB), piece, rng, period);
+                                   h->stream, n, Rp, Rj, cb, out, tab, cstats, (long long)(IS_A ? h->nnzA : h->nnzB), piece, rng, period, class_slot_seed(h));
             } else if (h->classHeadsOn) {
                 hipLaunchKernelGGL((k_class_heads<IS_A, GG, E>), dim3(heads_grid(n, GG)), dim3(kClassHeadsBlock), 0, h->stream, n, Rp, Rj, cb, out,
                                    headsL, nHeads, heads_cap(n, GG), rng, period);
                 hipLaunchKernelGGL((k_class_rows<IS_A, GG, E>), dim3(rowsGridList, kClassHeadSegs), dim3(kClassRowsBlock), 0, h->stream, n, Rp, Rj, cb,
-                                   tab, out, cstats, (const int*)nullptr, (const int*)headsL, (const int*)nHeads, heads_cap(n, GG));
+                                   tab, out, cstats, (const int*)nullptr, (const int*)headsL, (const int*)nHeads, heads_cap(n, GG), class_slot_seed(h));
                 hipLaunchKernelGGL(k_class_propagate, dim3(propGrid), dim3(256), 0, h->stream, n, out, rng);
             } else
                 hipLaunchKernelGGL((k_class_rows<IS_A, GG, E>), dim3(rows_grid(n, GG)), dim3(kClassRowsBlock), 0, h->stream, n, Rp, Rj, cb, tab, out,
-                                   cstats, rng, (const int*)nullptr, (const int*)nullptr, 0);
+                                   cstats, rng, (const int*)nullptr, (const int*)nullptr, 0, class_slot_seed(h));
             return (int)BHS_SUCCESS;
         });
     };
@@ -462,7 +467,9 @@ int symbolic_class(bhs_handle* h, bool mixed, const BinSpec& symSpec)
         hipLaunchKernelGGL(k_class_patterns, dim3(kClassSlots), dim3(256), 0, h->stream, (const unsigned long long*)tabA,
                            h->dAp, h->dAj, h->dBp, h->dBj, (int4*)h->classInfo.p,
                            (unsigned*)h->classMap.p, (unsigned*)h->classMapA.p, (int*)h->classRel.p, (int*)h->classLane.p,
-                           (unsigned*)h->classRing.p, cstats, (const int*)countA);
+                           (unsigned*)h->classRing.p, cstats, (const int*)countA,
+                           // kept columns: this multiply's classes named by the saved class with the same list (k_class_scan compares the rows')
+                           h->ps.keepTry ? (int*)h->keepTab.p : (int*)nullptr, h->ps.keepTry ? (const int*)h->keepRel.p : (const int*)nullptr);
         if (!bigPossible) return 1;
         const size_t smemBig = sizeof(int) * 2 * kClassBigMaxP;
         int unused = 0;
@@ -652,9 +659,12 @@ int scan_rowptr(bhs_handle* h, bool useClass, const SymChoices& sc)
             // one pass: every row's count from its class, scanned with look-back over the tiles before (k_class_scan)
             const int nTiles = (m + kClassScanTile - 1) / kClassScanTile;
             // (blockSum holds the tile words, cleared by k_class_reset)
-            hipLaunchKernelGGL(k_class_scan, dim3((unsigned)nTiles), dim3(kClassScanBlock), 0, h->stream, m, (const int*)h->classC.p,
+            // (kept columns: the same pass reads every row's class in the multiply that wrote colIndC beside this multiply's)
+            auto scan = h->ps.keepTry ? k_class_scan<true> : k_class_scan<false>;
+            hipLaunchKernelGGL(scan, dim3((unsigned)nTiles), dim3(kClassScanBlock), 0, h->stream, m, (const int*)h->classC.p,
                                (const int4*)h->classInfo.p, (int*)h->Cp.p, (unsigned long long*)h->blockSum.p,
-                               (long long*)(small + S_TOTAL_C), small + S_CT_SLOTS, sc.mixRows > 0, h->dAp, (const int*)h->ub.p, numSpec, small + S_NUM_COUNT);
+                               (long long*)(small + S_TOTAL_C), small + S_CT_SLOTS, sc.mixRows > 0, h->dAp, (const int*)h->ub.p, numSpec, small + S_NUM_COUNT,
+                               h->ps.keepTry ? (const int*)h->classPrev.p : (const int*)nullptr, h->ps.keepTry ? (const int*)h->keepTab.p : (const int*)nullptr);
             return 1;
         }
         if (h->scanOnePass) {
@@ -778,6 +788,12 @@ int symbolic_attempt(bhs_handle* h, bool restart)
     h->sumActive = false;             // (a sum of the last bhs_spgemm_add goes with the product it was made from)
     h->rowPtrStaged = false;          // (an empty product returns early: the previous multiply's staging must not be read)
     h->ps = bhs_handle::PipeState();
+    // Kept columns: whatever this multiply turns out to be, the pool's colIndC counts as unknown from here on -- only a whole
+    // clean multiply on the ring kernel that ends without error says otherwise again (keep_after_multiply).  A restart
+    // finds the state cleared: it writes its columns.
+    const bool keepWas = h->keep.valid;
+    h->keep.valid = false;
+    if (!restart) h->multiplies++;
 
     BHS_TRY(ensure(h, h->Cp, sizeof(int) * ((size_t)m + 1)));
     if (m == 0 || h->nnzA == 0 || h->nnzB == 0) {
@@ -801,6 +817,15 @@ int symbolic_attempt(bhs_handle* h, bool restart)
     // pipeline's kernels, everything else stays on the class kernels.  sc.mixRows: how many this multiply found.
     const bool mixedFlow = useClass && h->mixOn && h->classMixed;
     if (useClass) {
+        // Kept columns: may this multiply's ring kernel leave colIndC alone?  Only a speculative launch of the clean flow into
+        // the pool, whose allocation is the one the state was set for; the device decides (k_class_spec_check).
+        if (keepWas && !restart && !mixedFlow && h->keepColumns && h->specNumeric && h->classSpec.valid && !h->lazyOut && !h->extCj && !h->extCx &&
+            h->Cj.p && h->keep.cj == h->Cj.p && h->keep.cap == h->Cj.cap && h->keep.m == m && h->keep.nnzC == h->classSpec.nnzC &&
+            h->classPrev.p && h->keepTab.p && h->keepRel.p) {
+            // (the classes of the writing multiply stay where they are: this multiply classifies into the other array)
+            if (h->keep.classInC) { std::swap(h->classC, h->classPrev); h->keep.classInC = false; }
+            h->ps.keepTry = true;
+        }
         const int hubMin = mixedFlow ? hub_min_products(h) : 0;
         const BinSpec symSpec = make_spec(kSymCfg, kNumSymBins, h->maxTableLog2, h->symLoadPct, true, 0, hubMin);
         BHS_TRY(symbolic_class(h, mixedFlow, symSpec));
@@ -830,8 +855,10 @@ int symbolic_attempt(bhs_handle* h, bool restart)
         memcpy(key.cs, h->classSpec.cs, sizeof(key.cs));
         key.nnzC = h->classSpec.nnzC;
         hipLaunchKernelGGL(k_class_spec_check, dim3(1), dim3(64), 0, h->stream, key, (const int*)(small + S_CT_SLOTS),
-                           (const long long*)(small + S_TOTAL_C), (const int*)(small + S_ERR), small + S_SPEC);
+                           (const long long*)(small + S_TOTAL_C), (const int*)(small + S_ERR), small + S_SPEC,
+                           h->ps.keepTry ? small + S_KEEP : (int*)nullptr);
         BHS_HIP(hipGetLastError());
+        h->ps.keepLaunched = h->ps.keepTry;
         return open_speculative(h, sc, false, h->classSpec.nnzC, h->classSpec.nnzCt);
     }
     // ... and a lane-first multiply likewise (round 6): the last multiply's nnz(C) and "every row in the lane bin" stand in,
@@ -1091,6 +1118,7 @@ int pipeline_finish(bhs_handle* h)
         h->nnzCt = h->laneSpec.nnzCt = (long long)t;
     } else if (h->ps.specLaunched) {
         if (hs[S_SPEC] != 1) return kSpecRefuted;       // (the numeric kernel has written nothing: run_pipeline_impl starts over)
+        if (h->ps.keepLaunched && hs[S_KEEP] != 1) return kKeepRefuted;   // (likewise: colIndC is not provably this multiply's)
         unsigned long long t = 0, v;
         for (int i = 0; i < kClassSumSlots; ++i) { memcpy(&v, hs + S_CT_SLOTS + CS_SUMS + 2 * i, 8); t += v; }
         // (numeric_stage booked the numeric kernel's products on the figure of the multiply before: put this multiply's there)
@@ -1129,20 +1157,58 @@ int pipeline_finish(bhs_handle* h)
     return BHS_SUCCESS;
 }
 
+// Kept columns, the end of a whole bhs_spgemm that succeeded: what does the handle now know about the pool's colIndC?  Nothing
+// (the state stays cleared) unless the clean class flow's ring kernel ran once on all rows into the pool.  If that was the
+// instance without column stores, the state of the writing multiply stands (its classes and lists still describe the
+// columns: the device has just proven it); if it wrote the columns, this multiply becomes the writing one -- its per-row
+// classes stay in classC until the next multiply swaps the two arrays, its lists are copied (<= 256 classes of <= 512 ints).
+void keep_after_multiply(bhs_handle* h)
+{
+    if (h->ps.empty || !h->ps.useClass || h->ps.mixed || !h->ps.ringWhole || h->ps.rangesRun != 1 || h->extCj || h->extCx || !h->Cj.p) return;
+    if (h->ps.keepLaunched) {
+        h->colsKept++;
+        h->keep.valid = true;
+        return;
+    }
+    if (!h->keepColumns || h->classSpec.cs[CS_CLASSES] > kKeepMaxClasses || h->classSpec.cs[CS_FLAGS] || h->classSpec.cs[CS_BIGCOUNT]) return;
+    if (ensure(h, h->classPrev, sizeof(int) * (size_t)std::max(h->m, 1)) != BHS_SUCCESS) return;
+    if (ensure(h, h->keepTab, sizeof(int) * KT_INTS) != BHS_SUCCESS) return;
+    if (ensure(h, h->keepRel, sizeof(int) * (size_t)kKeepMaxClasses * kClassMaxNnz) != BHS_SUCCESS) return;
+    if (hipMemsetAsync((int*)h->keepTab.p + KT_COUNT, 0, sizeof(int), h->stream) != hipSuccess) return;
+    hipLaunchKernelGGL(k_keep_save, dim3(kClassSlots), dim3(64), 0, h->stream, (const int4*)h->classInfo.p, (const int*)h->classRel.p,
+                       (int*)h->keepTab.p, (int*)h->keepRel.p);
+    hipLaunchKernelGGL(k_keep_canon, dim3(kClassSlots), dim3(64), 0, h->stream, (const int4*)h->classInfo.p, (const int*)h->classRel.p,
+                       (int*)h->keepTab.p, (const int*)h->keepRel.p);
+    if (hipGetLastError() != hipSuccess) return;
+    h->keep.valid = true;
+    h->keep.classInC = true;
+    h->keep.cj = h->Cj.p;
+    h->keep.cap = h->Cj.cap;
+    h->keep.m = h->m;
+    h->keep.nnzC = h->nnzC;
+}
+
 int run_pipeline_impl(bhs_handle* h)
 {
     BHS_TRY(pipeline_symbolic(h));
     BHS_TRY(numeric_stage(h, 0, h->m));
-    const int rc = pipeline_finish(h);
-    if (rc != kSpecRefuted) return rc;
-    // the arrays are not what they were a multiply ago: once more, every decision from this multiply's own figures
-    h->classSpec.valid = false;
-    h->laneSpec.valid = false;
-    h->specRefuted++;
-    if (h->verbose > 1) printf("  [speculative numeric launch refuted on the device: the multiply again]\n");
-    BHS_TRY(pipeline_symbolic(h, true));            // (restart: the refuted attempt's timers and kernel records stay in -- it ran inside this multiply)
-    BHS_TRY(numeric_stage(h, 0, h->m));
-    return pipeline_finish(h);
+    int rc = pipeline_finish(h);
+    if (rc == kSpecRefuted || rc == kKeepRefuted) {
+        // the arrays are not what they were a multiply ago: once more, every decision from this multiply's own figures
+        // (and every column written: the state of the kept columns was cleared when this multiply began)
+        if (h->ps.keepLaunched) h->colsRefuted++;
+        if (rc == kSpecRefuted) {
+            h->classSpec.valid = false;
+            h->laneSpec.valid = false;
+            h->specRefuted++;
+        }
+        if (h->verbose > 1) printf("  [speculative numeric launch refuted on the device%s: the multiply again]\n", rc == kKeepRefuted ? " (kept columns)" : "");
+        BHS_TRY(pipeline_symbolic(h, true));            // (restart: the refuted attempt's timers and kernel records stay in -- it ran inside this multiply)
+        BHS_TRY(numeric_stage(h, 0, h->m));
+        rc = pipeline_finish(h);
+    }
+    if (rc == BHS_SUCCESS) keep_after_multiply(h);
+    return rc;
 }
 
 // Every exit of the pipeline leaves the handle quiescent: an error taken while the bins of a stage are forked

@@ -206,7 +206,18 @@ struct bhs_handle {
     int spinWaitUs = 0;                  // option "spin_wait_us": the longest a wait polls before it sleeps (0: four times the last multiply's wall time, 0.5 .. 5 ms)
     double lastMultiplyMs = 0.5;         // wall time of this handle's last bhs_spgemm
     long long specLaunches = 0, specRefuted = 0;
-    int numDirectHint = -1;              // this data set's last whole multiply ran its numeric stage without queues (1), with them (0); -1: none yet
+    // Kept columns (round 7, bhs_class.hip.h): what is known about the CONTENT of the pool's colIndC.  valid: every column in
+    // it was written through the ring kernel by the multiply whose per-row classes and class lists the handle still has
+    // (classPrev -- or classC until the next multiply swaps the two --, keepTab, keepRel), for this very allocation (cj, cap)
+    // and nothing has written there since.  Every multiply clears it when it starts; only a whole multiply of the clean class
+    // flow on the ring kernel into the pool that ends without error sets it again (keep_after_multiply).
+    struct KeepState { bool valid = false, classInC = false; const void* cj = nullptr; size_t cap = 0; int m = 0; long long nnzC = 0; } keep;
+    DevBuf classPrev, keepTab, keepRel;
+    int keepColumns = 1;                 // option "keep_columns": 0 every multiply writes its columns
+    int classSlotOffset = 0;             // option "class_slot_offset" (tests): the classifiers' home slot moves by this much per multiply -- the same pattern lands in other slots
+    long long multiplies = 0;            // multiplies this handle has begun
+    long long colsKept = 0, colsRefuted = 0;   // multiplies that left colIndC as it was; short launches refuted on the device and run again
+    int numDirectHint = -1;             // this data set's last whole multiply ran its numeric stage without queues (1), with them (0); -1: none yet
     int earlyFill = 1;                   // general pipeline: the queues filled while the host waits for the bin counts (starts computed on the device)
     int sortedScan = 1;                  // the sortedness scan of B at hand-over: 1 element-parallel (k_sorted_flat + k_sorted_starts), 0 row by row (k_check_sorted)
     int bSorted = 1;
@@ -341,6 +352,9 @@ struct bhs_handle {
         int spanWPL = 0;                 // this multiply's wave bins run k_row_span with this many bitmap words per lane (0: hash kernels)
         bool bWinBuilt = false;          // bWin / bWinTab belong to this multiply
         bool specLaunched = false;       // the numeric kernel goes out on the last multiply's figures (classSpec), k_class_spec_check decides
+        bool keepTry = false;            // kept columns: this multiply maps its classes to the saved ones and compares the rows' (k_class_patterns, k_class_scan<true>)
+        bool keepLaunched = false;       // ... and its speculative ring launch is the instance without column stores (S_KEEP decides)
+        bool ringWhole = false;          // the ring kernel ran on all rows into the pool's arrays
         bool specLane = false;           // ... a lane-first multiply's (laneSpec, k_lane_spec_check)
         bool fromCounts = false;         // ... whose numeric kernel makes rowPtrC from the counts (no scan ran)
         bool laneFirst = false;          // this multiply's symbolic stage was the lane kernel on every row, no upper-bound pass
@@ -447,7 +461,8 @@ enum { S_SYM_COUNT = 0, S_SYM_START = 16, S_SYM_CURSOR = 32, S_NUM_COUNT = 48, S
        S_SPAN = 478 /* bhs_set_data's scans for bhs_row_span.hip.h: left reach of B's rows, right reach, widest row of A */,
        S_ROWLEN = 482 /* bhs_set_data's scans for the classifier's sizes (k_max_row): per matrix rows beyond 64 entries, the
                          longest row within 64, rows beyond 256, the longest within 256 -- A's four, then B's */,
-       S_SMALL_INTS = 490 };
+       S_KEEP = 490 /* kept columns: k_class_spec_check's second word -- 1 the ring kernel without column stores goes on, 2 refuted */,
+       S_SMALL_INTS = 492 };
 
 template <int V> struct template_int { static constexpr int value = V; };
 

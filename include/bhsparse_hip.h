@@ -1261,6 +1261,20 @@ BHS_API int bhs_get_kernel_stats(bhs_handle *h, bhs_kernel_stat *out, int cap);
  *                     (round 6: a lane-first multiply -- every row through the lane kernels -- likewise, k_lane_spec_check;
  *                     "lane_from_counts" 1 (default): its numeric kernel then makes rowPtrC from the symbolic kernel's counts
  *                     and block sums, no scan kernel)
+ *   "keep_columns"    1 (default, round 7): a multiply whose classes provably name the columns that the library's own
+ *                     colIndC already holds sends its ring kernel out without the column stores.  Nothing is trusted: the
+ *                     handle keeps the per-row classes and the classes' relative-column lists of the last multiply that
+ *                     wrote every column of that array; the next multiply classifies every row anew as always, names each of
+ *                     its classes by the saved class whose list is equal entry by entry (k_class_patterns), compares every
+ *                     row's class with the saved one through those names (k_class_scan) and launches the short kernel on
+ *                     a second go word (k_class_spec_check); a refuted launch writes nothing and the multiply runs again
+ *                     and writes its columns.  Only whole multiplies of the clean class flow into the library's own arrays;
+ *                     bhs_set_data*, bhs_free_data, bhs_warmup, bhs_set_output_device, any bhs_set_option, any other flow
+ *                     and any error make the next multiply write every column.  colIndC as bhs_get_C_device hands it out
+ *                     is const: a caller that writes there must set this to 0.  0: every multiply writes its columns.
+ *                     bhs_get_info: "cols_kept" (multiplies that left colIndC as it was), "cols_refuted" (short launches
+ *                     the device refuted).  "class_slot_offset" (tests): the classifiers' home slot moves by this much per
+ *                     multiply, so that equal patterns get other class numbers; bhs_get_info "class_of_row0" reads one back
  *   "class_mixed"     1 (default, round 6): a row without a class -- or of a class beyond the tables, or of a class with fewer
  *                     than four rows -- goes through the general pipeline's kernels inside the same multiply while the other
  *                     rows stay on the class kernels (bhs_class_mix.hip.h; the reference bins every row for itself,

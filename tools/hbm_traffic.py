@@ -10,6 +10,7 @@ read request at 64 bytes and so reads 0.5-0.65 x of what a streaming pass moves 
 the same).  The script checks the size-resolved figure where the truth is known exactly --
   k_check_sorted, k_class_heads<false>   read colIndB + rowPtrB once:   4 * nnzB + 4 * (k + 1) bytes
   k_class_numeric*                        writes every entry of C once:  12 * nnzC bytes
+  k_class_ring<.., false>                 (kept columns: the steady-state launch) the values alone: 8 * nnzC bytes
 -- and records the ratios under `check` (all within a few per cent of 1 or the file says so).  *_DRAM: requests that
 went on to HBM (the others were served by the Infinity Cache).  Stamped with the digest of the device sources:
 bench.py quotes `roofline.traffic` only for the build it was measured on."""
@@ -36,6 +37,8 @@ def stat_name(kk):
     mt = re.search(r"k_row_wave<(\d+), \d+, (true|false)", kk)
     if mt:
         return "%s_wave<%s>" % ("numeric" if mt.group(2) == "true" else "symbolic", mt.group(1))
+    if "k_class_ring" in kk and ", true>" in kk:      # (the launch that writes colIndC too: a data set's first multiply, or keep_columns = 0)
+        return "numeric_class (writing launch)"
     if "k_class_numeric" in kk or "k_class_ring" in kk:
         return "numeric_class"
     mt = re.search(r"k_row_lane<(\d+), (true|false)", kk)
@@ -66,8 +69,12 @@ for kk, d in sorted(agg.items()):
         check[kk + ": read / (4 nnzB + 4 (k + 1))"] = round(e["read_bytes"] / (4.0 * nnzB + 4.0 * (k + 1)), 4)
         if e["fetch_size_bytes"]:
             check[kk + ": FETCH_SIZE / same"] = round(e["fetch_size_bytes"] / (4.0 * nnzB + 4.0 * (k + 1)), 4)
-    if have_w and ("k_class_numeric" in kk or "k_class_ring" in kk):
+    if have_w and "k_class_ring" in kk and ", false>" in kk:
+        check[kk + ": written / (8 nnzC)"] = round(e["write_bytes"] / (8.0 * nnzC), 4)
+    elif have_w and ("k_class_numeric" in kk or "k_class_ring" in kk):
         check[kk + ": written / (12 nnzC)"] = round(e["write_bytes"] / (12.0 * nnzC), 4)
+for n in [n for n in out if n.startswith("numeric_class (writing launch)")]:      # (no steady-state instance in this profile: the writing one is the kernel)
+    out.setdefault(n.replace(" (writing launch)", ""), out[n])
 path = os.path.join(ROOT, "profiles", "hbm_traffic.json")
 doc = {"_comment": "memory-side bytes per launch (tools/hbm_traffic.py): 128/64/32-byte read requests and 64/32-byte write requests "
                    "of the L2s, separate --pmc passes (tools/prof.sh); `check` compares them with passes of exactly known traffic; "

@@ -63,7 +63,7 @@ __device__ __forceinline__ void wait_all_but_stores(int n)
     }
 }
 
-template <int MAXU, int MAXV, int MAXJ>
+template <int MAXU, int MAXV, int MAXJ, bool COLS = true>      // (COLS: the product kernel's switch, round 7 -- every lab instance writes its columns)
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BHS_RING_WAVES, 8))) void k_class_ring(
     int m, const int* __restrict__ Ap, const int* __restrict__ Aj, const value_t* __restrict__ Ax, long long nnzA,
     const int* __restrict__ Bp, const value_t* __restrict__ Bx, long long nnzB, const int* __restrict__ classC,
@@ -71,7 +71,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(BHS_RING_WAV
     const int* __restrict__ classLane, const int* __restrict__ Cp, int* __restrict__ Cj, value_t* __restrict__ Cx,
     int ringBytes, int accStride, int rowBase, int superRows, int chunkRows,     // m, Ap, classC, Cp are views of the rows [rowBase, rowBase + m)
     const int* __restrict__ specWord,                                             // launched before the host saw this multiply's classes (k_class_spec_check): go on only if 1
-    int* __restrict__ tickets)                                                    // 8 counters, zero at launch: the next super-run of every XCD's band (round 6)
+    int* __restrict__ tickets,                                                    // 8 counters, zero at launch: the next super-run of every XCD's band (round 6)
+    const int* __restrict__ keepWord)                                             // (the product kernel's second go word, round 7: the lab copy has no instance without column stores and never looks)
 {
     if (specWord != nullptr && *specWord != 1) return;
     extern __shared__ __attribute__((aligned(16))) unsigned char smemRaw[];
