@@ -67,6 +67,10 @@ BHS_FOREST_MAXIMUM, BHS_FOREST_ABS = 1, 2
 # bhs_csr_cfsplit_device (include/bhsparse_hip.h, "C/F splitting and interpolation")
 BHS_CF_DEGREE = 1
 
+# bhs_coo_assemble_device / bhs_coo_assemble_values_device (include/bhsparse_hip.h, "assembly")
+BHS_COO_SUM, BHS_COO_FIRST, BHS_COO_LAST, BHS_COO_KEEP, BHS_COO_IGNORE_NEGATIVE = 0, 1, 2, 3, 4
+COO_COMBINE = {"sum": BHS_COO_SUM, "first": BHS_COO_FIRST, "last": BHS_COO_LAST, "keep": BHS_COO_KEEP}
+
 
 # every symbol include/bhsparse_hip.h declares: (restype, argtypes)
 _vp, _i, _i64 = C.c_void_p, C.c_int, C.c_int64
@@ -146,6 +150,9 @@ SYMBOLS = {
                                             C.POINTER(C.c_double)]),
     "bhs_csr_interp_numeric_device": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, C.c_longlong, _vp, _vp, _i,
                                            C.POINTER(C.c_double)]),
+    "bhs_coo_assemble_device": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i), C.POINTER(_i),
+                                     C.POINTER(C.c_double)]),
+    "bhs_coo_assemble_values_device": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _vp, C.POINTER(C.c_double)]),
     "bhs_strerror": (C.c_char_p, [_i]),
     "bhs_version": (C.c_char_p, []),
 }

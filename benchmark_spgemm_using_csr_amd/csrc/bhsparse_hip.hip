@@ -435,6 +435,10 @@ struct bhs_handle {
     // the C/F splitting and the interpolation (bhs_host_cfsplit.inc.h): the two word arrays, the C-point bitmap and the scanned
     // offsets in its queue buffer, the C points per bitmap word -- or the entries per row of P -- in its count buffer
     SideWs cfWs;
+    // the assembly from triplets (bhs_host_assemble.inc.h): the raw rows' queues by bin in its queue buffer, the kept triplets per
+    // row and then the heads per bitmap word in its count buffer
+    SideWs asWs;
+    DevBuf asBuf[7];                     // rawPtr, the cursors, the keys (column << 32 | position), their rows, the head bitmap, its scanned offsets, entryPtr where the caller keeps none
 };
 
 namespace {
@@ -609,6 +613,7 @@ inline int one_launch(int rc) { return rc != BHS_SUCCESS ? rc : 1; }
 #include "bhs_host_match.inc.h"
 #include "bhs_host_forest.inc.h"
 #include "bhs_host_cfsplit.inc.h"
+#include "bhs_host_assemble.inc.h"
 #include "bhs_host_transpose.inc.h"
 #include "bhs_host_reduce.inc.h"
 #include "bhs_host_semiring.inc.h"

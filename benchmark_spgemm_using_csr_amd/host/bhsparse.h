@@ -181,6 +181,18 @@ public:
                                    const value_type *d_valA, int flags, index_type *d_label, index_type *d_edgeLo,
                                    index_type *d_edgeHi, value_type *d_edgeVal, int *nedges_out, int *rounds_out);
 
+    // EXTENSION, not part of the reference's API: Z (m x n, CSR) from nnzIn triplets on DEVICE arrays, rows ascending, duplicates
+    // combined as flags says (BHS_COO_SUM, _FIRST, _LAST or _KEEP, with BHS_COO_IGNORE_NEGATIVE), and the values of a known
+    // pattern from new triplet values (bhs_coo_assemble_device, bhs_coo_assemble_values_device; include/bhsparse_hip.h,
+    // "assembly").  d_valIn may be null (the pattern alone), and so may d_valZ, d_entryPtr and d_perm.  d_colIndZ, d_valZ and
+    // d_perm need room for nnzIn, d_entryPtr for nnzIn + 1; *nnzZ_out entries and *nkept_out map positions are written.
+    // Need initPlatform only.
+    int coo_assemble_device(int m, int n, int nnzIn, const index_type *d_rowInd, const index_type *d_colInd,
+                            const value_type *d_valIn, int flags, index_type *d_rowPtrZ, index_type *d_colIndZ, value_type *d_valZ,
+                            index_type *d_entryPtr, index_type *d_perm, int *nnzZ_out, int *nkept_out);
+    int coo_assemble_values_device(int nnzIn, const value_type *d_valIn, int nnzZ, const index_type *d_entryPtr,
+                                   const index_type *d_perm, int flags, value_type *d_valZ);
+
     // EXTENSION, not part of the reference's API: the C/F splitting of an n x n pattern S of strong connections on DEVICE
     // arrays (bhs_csr_cfsplit_device; include/bhsparse_hip.h, "C/F splitting and interpolation").  d_prio may be null: the
     // hash of (vertex, seed); flags: 0 or BHS_CF_DEGREE (not with d_prio).  d_cf (n ints) receives the coarse index of every
@@ -466,6 +478,22 @@ inline int bhsparse::csr_spanning_forest_device(int n, int nnzA, const index_typ
     if (!_h) return BHS_ERR_NOT_READY;
     return bhs_csr_spanning_forest_device(_h, n, nnzA, d_rowPtrA, d_colIndA, d_valA, flags, d_label, d_edgeLo, d_edgeHi, d_edgeVal,
                                           nedges_out, rounds_out, 0);
+}
+
+inline int bhsparse::coo_assemble_device(int m, int n, int nnzIn, const index_type *d_rowInd, const index_type *d_colInd,
+                                         const value_type *d_valIn, int flags, index_type *d_rowPtrZ, index_type *d_colIndZ,
+                                         value_type *d_valZ, index_type *d_entryPtr, index_type *d_perm, int *nnzZ_out, int *nkept_out)
+{
+    if (!_h) return BHS_ERR_NOT_READY;
+    return bhs_coo_assemble_device(_h, m, n, nnzIn, d_rowInd, d_colInd, d_valIn, flags, d_rowPtrZ, d_colIndZ, d_valZ, d_entryPtr, d_perm,
+                                   nnzZ_out, nkept_out, 0);
+}
+
+inline int bhsparse::coo_assemble_values_device(int nnzIn, const value_type *d_valIn, int nnzZ, const index_type *d_entryPtr,
+                                                const index_type *d_perm, int flags, value_type *d_valZ)
+{
+    if (!_h) return BHS_ERR_NOT_READY;
+    return bhs_coo_assemble_values_device(_h, nnzIn, d_valIn, nnzZ, d_entryPtr, d_perm, flags, d_valZ, 0);
 }
 
 inline int bhsparse::csr_cfsplit_device(int n, int nnzS, const index_type *d_rowPtrS, const index_type *d_colIndS,

@@ -337,6 +337,80 @@ BHS_API int bhs_csr_transpose_device(bhs_handle *h, int m, int n, int nnzX,
 BHS_API int bhs_csr_transpose_values_device(bhs_handle *h, int nnzX, const bhs_value_t *d_valX,
                                             const int *d_perm, bhs_value_t *d_valT, double *ms_out);
 
+/* ---- assembly -------------------------------------------------------------
+ * Z from triplets (MATLAB sparse(i, j, v), scipy coo_matrix.tocsr(), PETSc MatSetValuesCOO; no reference counterpart), with
+ * the map that re-values a known pattern (bhs_assemble.hip.h).  What it is for: the entry into the library for whoever holds
+ * triplets -- finite-element contributions, an edge list, the (lo, hi, w) of bhs_csr_spanning_forest_device -- and for a
+ * CSR whose rows are unsorted or hold repeats: its output has rows strictly ascending (BHS_COO_KEEP: ascending), which
+ * bhs_csr_add_*, bhs_csr_cfsplit_device, bhs_csr_interp_* and bhs_csr_ilu0_device require.
+ *
+ * The triplets: nnzIn of them, (rowInd[e], colInd[e], valIn[e]), in any order, repeats legal.  Z is m x n.
+ *   kept      triplet e is kept when 0 <= rowInd[e] < m and 0 <= colInd[e] < n.  With BHS_COO_IGNORE_NEGATIVE a triplet with a
+ *             negative row or column is dropped silently (PETSc's convention for constrained unknowns); without it a
+ *             negative index is an error.  An index >= m or >= n is always an error.
+ *   perm      the kept positions e sorted by (rowInd[e], colInd[e], e) -- the stable order; nkept is its length.
+ *   runs      a run is a maximal stretch of perm with equal (row, column); equal columns that end one row and begin the next
+ *             are never one run.  Under BHS_COO_SUM, _FIRST and _LAST each run becomes one entry of Z.  Under BHS_COO_KEEP
+ *             every kept triplet stays an entry of its own: Z is sorted but has repeats, nnzZ == nkept, entryPtr[q] == q.
+ *   outputs   rowPtrZ / colIndZ: Z's pattern, rows ascending.  Entry q is the run perm[entryPtr[q] .. entryPtr[q+1]);
+ *             entryPtr[0] == 0, entryPtr[nnzZ] == nkept.  An empty row is an empty row of Z.
+ *   values    _FIRST / _LAST (and _KEEP) copy the run's first / last value by input position, bit for bit.  _SUM:
+ *             s = double(valIn[perm[a]]) -- not 0.0 + ..., a lone -0 stays -0 --, then s += double(valIn[perm[k]]) for
+ *             k = a+1 .. b-1 in that order, one lane a run, and ONE rounding to the value type.  The order is fixed on
+ *             purpose: the result is THE result for any input, NaN and +-Inf included.
+ *   No atomic touches an output array; every output is a function of the input alone, the same bits from run to run and
+ *   from handle to handle, and for values both types hold exactly in both builds.
+ *
+ * bhs_coo_assemble_device
+ *   d_valIn    nnzIn values, or NULL: the pattern alone (d_valZ must then be NULL too)
+ *   d_rowPtrZ  m+1 ints.  d_colIndZ: CAPACITY nnzIn ints, nnzZ written.  d_valZ: CAPACITY nnzIn values, nnzZ written, or
+ *              NULL.  d_entryPtr: CAPACITY nnzIn+1 ints, nnzZ+1 written, or NULL.  d_perm: CAPACITY nnzIn ints, nkept
+ *              written, or NULL.  Caller-owned device arrays whose footprints (the capacities) must not overlap the
+ *              triplets or one another.  Nothing is written outside the capacities.
+ *   flags      one of BHS_COO_SUM, _FIRST, _LAST, _KEEP, or'ed with BHS_COO_IGNORE_NEGATIVE
+ *   nnzZ_out, nkept_out, ms_out (device time of the whole call, validation included): each may be NULL
+ *   The triplets are validated on the device BEFORE anything caller-owned is written: an index >= m or >= n, or a negative
+ *   one without the flag, returns BHS_ERR_INVALID_ARG with every output untouched.  BHS_ERR_INVALID_ARG from the host,
+ *   outputs untouched as well: a NULL handle, a negative size, an unknown flag bit, NULL index arrays or NULL d_colIndZ
+ *   with nnzIn > 0, NULL d_rowPtrZ, d_valZ without d_valIn, overlapping footprints.  The triplets must not change during
+ *   the call: a place that no longer fits its row is not written and the call returns BHS_ERR_INTERNAL.
+ *   m, n or nnzIn may be 0; d_rowPtrZ is still written (m+1 zeros when nothing is kept), and entryPtr[0].
+ * bhs_coo_assemble_values_device: the pattern-reuse half -- finite-element codes re-assemble new values on an unchanged
+ *   connectivity every time step or Newton iteration.  Assemble once with d_entryPtr and d_perm, keep Z's pattern, and
+ *   re-value Z with this call from new valIn by the same rule (flags: BHS_COO_SUM, _FIRST or _LAST; _KEEP is refused: its
+ *   values are FIRST's): the bits equal those of a full call on the same triplets.  valIn is read only at positions perm
+ *   names.  The map is checked whole BEFORE d_valZ is touched and every index again ahead of its dependent read:
+ *   entryPtr[0] != 0, a decreasing entryPtr, entryPtr[nnzZ] > nnzIn or a perm entry outside [0, nnzIn) returns
+ *   BHS_ERR_INVALID_ARG with d_valZ untouched; a bad index is never followed.  (entryPtr[q] == entryPtr[q+1], an empty run
+ *   no full call makes, gives +0.)  d_valZ must not overlap d_valIn or the map.
+ * Both calls are synchronous on the handle's stream, need no bound data (they work on a handle straight after bhs_create;
+ *   BHS_ERR_INVALID_ARG between bhs_spgemm_symbolic and bhs_spgemm_finish) and leave the handle as it was: counters, tile
+ *   words, epoch, events and scratch of their own from the grow-only pool (12 bytes a triplet for the keys and their rows,
+ *   8 bytes a row, a bit and a sixteenth of an int a triplet for the head bitmap); C of the last multiply, a sum or selection
+ *   the getters serve, "class_state", the speculative-launch figures and every option stay.  Only bhs_get_kernel_stats now
+ *   reports the assembly's families: assemble_count (validation, the rows' histogram and bins), assemble_scan,
+ *   assemble_scatter, assemble_short (raw rows of up to 32 triplets), assemble_wave (up to 1024), assemble_long,
+ *   assemble_dedupe, assemble_values; assemble_check and assemble_values after the values call.
+ * Known limits: one raw row is put in order by one workgroup (a row of millions of triplets goes through a bitonic network
+ *   in HBM), and one lane adds one run (a run of millions of triplets is added by one lane): both slow, both correct.      */
+enum { BHS_COO_SUM = 0, BHS_COO_FIRST = 1, BHS_COO_LAST = 2, BHS_COO_KEEP = 3,   /* bits 0-1: what happens to duplicates */
+       BHS_COO_IGNORE_NEGATIVE = 4 };
+
+BHS_API int bhs_coo_assemble_device(bhs_handle *h, int m, int n, int nnzIn,
+        const int *d_rowInd, const int *d_colInd,        /* nnzIn each, any order, repeats legal */
+        const bhs_value_t *d_valIn                       /* may be NULL: pattern only */,
+        int flags,
+        int *d_rowPtrZ                                   /* out: m + 1 */,
+        int *d_colIndZ                                   /* out: CAPACITY nnzIn, nnzZ written */,
+        bhs_value_t *d_valZ                              /* out, may be NULL (needs d_valIn): CAPACITY nnzIn */,
+        int *d_entryPtr                                  /* out, may be NULL: CAPACITY nnzIn + 1, nnzZ + 1 written */,
+        int *d_perm                                      /* out, may be NULL: CAPACITY nnzIn, nkept written */,
+        int *nnzZ_out, int *nkept_out, double *ms_out    /* each may be NULL */);
+
+BHS_API int bhs_coo_assemble_values_device(bhs_handle *h, int nnzIn, const bhs_value_t *d_valIn,
+        int nnzZ, const int *d_entryPtr, const int *d_perm,
+        int flags /* BHS_COO_SUM, FIRST or LAST */, bhs_value_t *d_valZ /* nnzZ */, double *ms_out);
+
 /* ---- semiring multiply ----------------------------------------------------
  * C<M> = A (+).(x) B and C = A (+).(x) B over a semiring other than plus-times (GraphBLAS mxm; no reference counterpart):
  * one relaxation step of all-pairs shortest paths (MIN_PLUS), widest / bottleneck paths (MAX_MIN, MIN_MAX), most
