@@ -58,6 +58,9 @@ BHS_MV_ACCUM, BHS_MV_MASK_COMPLEMENT = 1, 2
 # bhs_csr_gs_device (include/bhsparse_hip.h, "colouring and relaxation")
 BHS_GS_FORWARD, BHS_GS_BACKWARD, BHS_GS_SYMMETRIC, BHS_GS_VERIFY = 1, 2, 3, 4
 
+# bhs_csr_relax_device (include/bhsparse_hip.h, "relaxation and fused products")
+BHS_RELAX_ZERO_GUESS = 1
+
 # bhs_csr_levels_device / bhs_csr_trsv_device (include/bhsparse_hip.h, "triangular solve and ILU(0)")
 BHS_TRI_LOWER, BHS_TRI_UPPER, BHS_TRI_UNIT_DIAG = 1, 2, 4
 
@@ -153,6 +156,11 @@ SYMBOLS = {
     "bhs_coo_assemble_device": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i), C.POINTER(_i),
                                      C.POINTER(C.c_double)]),
     "bhs_coo_assemble_values_device": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _vp, C.POINTER(C.c_double)]),
+    "bhs_csr_relax_device": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _i, C.POINTER(C.c_double), _vp, _vp, _vp, C.c_uint,
+                                  C.POINTER(C.c_double)]),
+    "bhs_chebyshev_coefficients": (_i, [C.c_double, C.c_double, _i, C.POINTER(C.c_double)]),
+    "bhs_csr_spmv_dots_device": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, C.c_double, _vp, C.c_double, _vp, _vp, _vp,
+                                      C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "bhs_strerror": (C.c_char_p, [_i]),
     "bhs_version": (C.c_char_p, []),
 }

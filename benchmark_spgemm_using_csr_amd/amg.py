@@ -11,6 +11,10 @@ The classical (Ruge-Stueben) half of the family stands beside the aggregations: 
 (bhs_csr_cfsplit_device; "C/F splitting and interpolation": the greedy maximal independent set under the PMIS measure), the
 direct interpolation on it as a symbolic / numeric pair (bhs_csr_interp_symbolic_device, bhs_csr_interp_numeric_device) and
 the hierarchy of the two (rs_setup_device; profiles/cf_case.md).
+A third smoother needs no colouring: sweeps of a polynomial in D^-1 A as one library call (bhs_csr_relax_device;
+"relaxation and fused products": relax_device, jacobi_device), Chebyshev coefficients on an interval from a Lanczos estimate
+of rho(D^-1 A) (spectral_radius_device, cheby_setup_device), and the cycle and PCG with it (smoother="chebyshev";
+profiles/relax_case.md).
 Beside it: the level sets of a triangle, the sparse triangular solve and ILU(0) in place (bhs_csr_levels_device, bhs_csr_trsv_device, bhs_csr_ilu0_device; "triangular solve and ILU(0)") and CG
 preconditioned with that factorisation in natural or colour order (ilu0_pcg_device).
 
@@ -297,6 +301,138 @@ def gs_device(bh, A, diag, coloring, b, x, omega=1.0, sweeps=1, direction="symme
     return x
 
 
+# ---------------------------------------------------------------- polynomial relaxation
+def chebyshev_coefficients(lmin, lmax, steps):
+    """bhs_chebyshev_coefficients: the `steps` pairs (a_s, c_s) of the Chebyshev iteration on [lmin, lmax] as a float64
+    numpy array of shape (steps, 2), what relax_device takes as coef.  Raises ValueError for anything but
+    0 < lmin < lmax, both finite, steps >= 1.  No device work: needs the library, no handle."""
+    steps = int(steps)
+    out = np.zeros(2 * max(steps, 1), np.float64)
+    err = _lib.load().bhs_chebyshev_coefficients(float(lmin), float(lmax), steps, out.ctypes.data_as(C.POINTER(C.c_double)))
+    if err != _lib.BHS_SUCCESS:
+        raise ValueError("0 < lmin < lmax, both finite, and steps >= 1")
+    return out.reshape(steps, 2)
+
+
+def relax_raw_device(bh, n, nnzA, d_valA, d_rowPtrA, d_colIndA, d_diag, steps, coef, d_b, d_x, d_d, flags):
+    """bhs_csr_relax_device on caller-given arrays, the C arguments in order (coef: 2 * steps doubles on the host, anything
+    numpy makes a float64 array of, or None; d_valA and d_d may be None): the status code; sets bh.relax_ms."""
+    if bh._h is None:
+        return _lib.BHS_ERR_NOT_READY
+    hcoef = None if coef is None else np.ascontiguousarray(coef, np.float64).reshape(-1)
+    cptr = None if hcoef is None else hcoef.ctypes.data_as(C.POINTER(C.c_double))
+    return bh._timed(bh._lib.bhs_csr_relax_device, "relax_ms", int(n), int(nnzA), _ptr(d_valA), _ptr(d_rowPtrA), _ptr(d_colIndA),
+                     _ptr(d_diag), int(steps), cptr, _ptr(d_b), _ptr(d_x), _ptr(d_d), int(flags))
+
+
+def relax_device(bh, A, diag, b, x, coef, d=None, zero_guess=False):
+    """len(coef) relaxation steps on A x = b, IN PLACE on x (and on d where given): A = (rowPtr, colInd, val), diag the
+    divisor of every row, all torch tensors on the handle's GPU; coef the (steps, 2) pairs (a_s, c_s) of
+    include/bhsparse_hip.h, "relaxation and fused products" (chebyshev_coefficients; weighted Jacobi is (0, omega)).  d: the
+    last step's correction, carried between calls; made here where a step reads it and none is given.  zero_guess: x counts
+    as zero and is not read (one product less).  Returns x; bh.relax_ms holds the device time.  Raises BhsparseError on
+    failure."""
+    import torch
+    coef = np.ascontiguousarray(coef, np.float64).reshape(-1, 2)
+    if d is None and np.any(coef[:, 0] != 0.0):
+        d = torch.zeros_like(x)
+    torch.cuda.synchronize()                           # the library works on its own stream (see facade.initData_device)
+    _check(relax_raw_device(bh, _rows(A), A[1].numel(), A[2], A[0], _none_if_empty(A[1]), diag, len(coef), coef, b, x, d,
+                            _lib.BHS_RELAX_ZERO_GUESS if zero_guess else 0), "bhs_csr_relax_device")
+    return x
+
+
+def jacobi_device(bh, A, diag, b, x, omega, sweeps, zero_guess=False):
+    """`sweeps` weighted Jacobi sweeps x <- x + omega D^-1 (b - A x) in one call, IN PLACE on x (relax_device with the
+    pairs (0, omega)).  Returns x."""
+    return relax_device(bh, A, diag, b, x, [(0.0, float(omega))] * int(sweeps), None, zero_guess)
+
+
+def _start_vector(n, seed):
+    """n values in [-1, 1) from a 64-bit mix of (index, seed) (splitmix64's finaliser): the same on every machine"""
+    with np.errstate(over="ignore"):
+        z = (np.arange(n, dtype=np.uint64) + np.uint64(1)) * np.uint64(0x9E3779B97F4A7C15) + np.uint64(int(seed) & 0xFFFFFFFF)
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        z = z ^ (z >> np.uint64(31))
+    return (z >> np.uint64(11)).astype(np.float64) * (2.0 ** -52) - 1.0
+
+
+def spectral_radius_device(bh, n, A, diag=None, steps=10, seed=0):
+    """An estimate from below of rho(D^-1 A) for the symmetric n x n matrix A = (rowPtr, colInd, val) with the positive
+    diagonal `diag` (taken from A when None): `steps` Lanczos steps on D^-1/2 A D^-1/2 -- formed once with
+    csr_scale_device --, every product with its two reductions from csr_spmv_dots_device, from the start vector of
+    (index, seed); the largest eigenvalue of the small tridiagonal matrix (numpy.linalg.eigvalsh), a Ritz value and so never
+    above the largest eigenvalue.  bh.lanczos_ms holds the device time of the products.  Raises ValueError on a diagonal
+    that is not positive."""
+    import torch
+    from .dense import csr_spmv_dots_device
+    if diag is None:
+        diag = bh.csr_reduce_device(n, n, A, _lib.BHS_AXIS_DIAG, _lib.BHS_RED_PLUS)
+    if n == 0 or not bool((diag > 0).all()):
+        raise ValueError("the diagonal must be positive")
+    root = torch.sqrt(diag)
+    S = (A[0], A[1], bh.csr_scale_device(n, n, A, 1.0, left=root, right=root, left_div=True, right_div=True))
+    v = torch.from_numpy(_start_vector(n, seed)).to(device=diag.device, dtype=diag.dtype)
+    v = v / torch.linalg.norm(v)
+    prev, beta, alphas, betas, ms = None, 0.0, [], [], 0.0
+    for _ in range(max(1, min(int(steps), n))):
+        z, _, alpha = csr_spmv_dots_device(bh, n, n, S, v, 1.0, -beta, prev, v)      # z = S v - beta v_prev, alpha = <v, z>
+        ms += bh.spmv_dots_ms
+        alphas.append(alpha)
+        z = z - alpha * v
+        nrm = float(torch.linalg.norm(z))
+        if not nrm > 1e-12 * max(abs(a) for a in alphas):                          # (an invariant subspace: the Ritz values are eigenvalues)
+            break
+        betas.append(nrm)
+        prev, v, beta = v, z / nrm, nrm
+    k = len(alphas)
+    T = np.diag(alphas) + np.diag(betas[:k - 1], 1) + np.diag(betas[:k - 1], -1)
+    bh.lanczos_ms = ms
+    return float(np.linalg.eigvalsh(T)[-1])
+
+
+def cheby_setup_device(bh, levels, degree=2, lanczos_steps=10, upper=1.1, lower_ratio=0.3):
+    """What the Chebyshev smoother needs of every level but the last: (diag(A_l), coef) with the `degree` coefficient pairs
+    for [lmin, lmax], lmax = upper * spectral_radius_device(A_l, lanczos_steps) and lmin = lower_ratio * lmax (hypre's
+    defaults).  A list to pass to vcycle_device as `smoothers`."""
+    out = []
+    for A, P, _ in levels:
+        if P is None:
+            continue
+        n = _rows(A)
+        d = bh.csr_reduce_device(n, n, A, _lib.BHS_AXIS_DIAG, _lib.BHS_RED_PLUS)
+        lmax = float(upper) * spectral_radius_device(bh, n, A, d, lanczos_steps)
+        out.append((d, chebyshev_coefficients(float(lower_ratio) * lmax, lmax, degree)))
+    return out
+
+
+def _vcycle_chebyshev(bh, levels, b, x, pre, post, smoothers, lvl):
+    """The cycle of vcycle_device with the Chebyshev smoother; x None: the guess is zero (BHS_RELAX_ZERO_GUESS)."""
+    import torch
+    from .dense import csr_spmv_dots_device
+    A, P, R = levels[lvl]
+    if P is None:
+        return vcycle_device(bh, levels, b, x, lvl=lvl)            # (the dense solve: the guess is not looked at)
+    n, nc = _rows(A), _rows(R)
+    d, coef = smoothers[lvl]
+    zero = x is None
+    x = torch.empty_like(b) if zero else x.clone()
+    carry = torch.empty_like(b)                                    # (step 0 of every call has a == 0: never read before it is written)
+    for _ in range(pre):
+        relax_device(bh, A, d, b, x, coef, carry, zero)
+        zero = False
+    if zero:
+        x.zero_()
+    r, _, _ = csr_spmv_dots_device(bh, n, n, A, x, -1.0, 1.0, b)
+    rc = csr_spmv_device(bh, nc, n, R, r)
+    xc = _vcycle_chebyshev(bh, levels, rc, None, pre, post, smoothers, lvl + 1)
+    x = csr_spmv_device(bh, n, nc, P, xc, alpha=1.0, beta=1.0, y=x)
+    for _ in range(post):
+        relax_device(bh, A, d, b, x, coef, carry)
+    return x
+
+
 # ---------------------------------------------------------------- the pieces of a level
 def strength_device(bh, n, A, theta):
     """The symmetric pattern of strong connections of the n x n matrix A (rows strictly ascending): the selection keeps the
@@ -398,6 +534,8 @@ def sa_setup_device(handles, n, A, theta=0.0, omega=2.0 / 3.0, max_levels=10, mi
     strictly ascending.  handles: two initialised facade.bhsparse handles (h1, h2) of A's value type, or a callable that
     makes one (called twice; those are destroyed here).  Per level: strength -> aggregate -> tentative -> P = T - omega
     D^-1 A T -> A_c = P^T (A P); coarsening stops at max_levels, at min_coarse rows or fewer, or where nothing is merged.
+    omega "estimate" (pa_setup_device the same): 4 / (3 rho) per level, rho from spectral_radius_device on that level's
+    matrix; the level's record then holds "omega" and "lanczos_ms".
     Returns (levels, info): levels a list of (A_l, P_l, R_l = P_l^T) with P = R = None on the last; info a list with one
     entry per level: n, nnz and, where the level was coarsened, nagg, rounds and the device ms of strength / aggregate /
     prolongator / galerkin."""
@@ -428,8 +566,16 @@ def _setup_levels(handles, n, A, coarsen, omega, max_levels, min_coarse, prolong
                 break
             if prolong is None:
                 T, _ = tentative_device(h1, n, agg, nagg)
-                P = smoothed_prolongator_device(h1, n, nagg, A, T, omega)
-                timing = {"prolongator_ms": h1.prolongator_ms}
+                timing = {}
+                if isinstance(omega, str):                            # "estimate": 4 / (3 rho(D^-1 A_l)) from Lanczos
+                    if omega != "estimate":
+                        raise ValueError("omega is a number or 'estimate'")
+                    level_omega = 4.0 / (3.0 * spectral_radius_device(h1, n, A))
+                    timing = {"omega": level_omega, "lanczos_ms": h1.lanczos_ms}
+                else:
+                    level_omega = omega
+                P = smoothed_prolongator_device(h1, n, nagg, A, T, level_omega)
+                timing["prolongator_ms"] = h1.prolongator_ms
             else:
                 P, timing = prolong(h1, n, A, agg, nagg)
             Ac, R = galerkin_device(h1, h2, n, nagg, A, P)
@@ -559,10 +705,18 @@ def vcycle_device(bh, levels, b, x, omega_jacobi=2.0 / 3.0, pre=1, post=1, diago
     through csr_spmv_device, the coarsest level by a dense torch.linalg.solve.  smoother "jacobi": weighted Jacobi from
     csr_spmv_device (y = alpha A x + beta y) and the diagonal.  smoother "gs": `pre` forward multicolour Gauss-Seidel
     sweeps before the coarse correction and `post` backward sweeps after it (gs_device; smoothers: what
-    smoother_setup_device returned, made here when None) -- a symmetric cycle where pre == post.  Returns the new x."""
+    smoother_setup_device returned, made here when None) -- a symmetric cycle where pre == post.  smoother "chebyshev":
+    `pre` calls of relax_device with the level's Chebyshev coefficients before the coarse correction and `post` after it
+    (smoothers: what cheby_setup_device returned, made here when None), the coarse levels from a zero guess that is never
+    read, the residual from csr_spmv_dots_device -- a polynomial in D^-1 A on both sides, so symmetric where pre == post,
+    with no colouring.  Returns the new x."""
     import torch
-    if smoother not in ("jacobi", "gs"):
-        raise ValueError("smoother is 'jacobi' or 'gs'")
+    if smoother not in ("jacobi", "gs", "chebyshev"):
+        raise ValueError("smoother is 'jacobi', 'gs' or 'chebyshev'")
+    if smoother == "chebyshev" and levels[lvl][1] is not None:
+        if smoothers is None:
+            smoothers = cheby_setup_device(bh, levels)
+        return _vcycle_chebyshev(bh, levels, b, x, pre, post, smoothers, lvl)
     A, P, R = levels[lvl]
     n = _rows(A)
     if P is None:
@@ -612,10 +766,14 @@ def pcg_device(bh, levels, b, tol=1e-8, maxiter=100, smoother="gs"):
     """Conjugate gradients for A_0 x = b from x = 0, preconditioned with one V(1,1) cycle from zero (smoother "gs": forward
     before and backward after, a symmetric operator; "jacobi" is symmetric too), until ||r|| <= tol ||b|| or maxiter
     iterations.  The products with A_0 are csr_spmv_device, the dot products and updates torch's.  Returns (x, iterations,
-    residual norms): the norms of the recurrence's residual, the first ||b||."""
+    residual norms): the norms of the recurrence's residual, the first ||b||.  smoother "chebyshev": the cycle of
+    vcycle_device(smoother="chebyshev") on cheby_setup_device's defaults, from a zero guess that is never read, and
+    q = A p with <p, q> from one csr_spmv_dots_device call."""
     import torch
     A = levels[0][0]
     n = _rows(A)
+    if smoother == "chebyshev":
+        return _pcg_chebyshev(bh, levels, b, tol, maxiter)
     smoothers = smoother_setup_device(bh, levels) if smoother == "gs" else None
     diagonals = _diagonals(bh, levels) if smoother == "jacobi" else None
     x = torch.zeros_like(b)
@@ -629,6 +787,32 @@ def pcg_device(bh, levels, b, tol=1e-8, maxiter=100, smoother="gs"):
         rz = rz_new
         q = csr_spmv_device(bh, n, n, A, p)
         alpha = rz / float(torch.dot(p, q))
+        x = x + alpha * p
+        r = r - alpha * q
+        res.append(float(torch.linalg.norm(r)))
+        its += 1
+    return x, its, res
+
+
+def _pcg_chebyshev(bh, levels, b, tol, maxiter, smoothers=None):
+    """pcg_device's iteration with the Chebyshev cycle and the fused product"""
+    import torch
+    from .dense import csr_spmv_dots_device
+    A = levels[0][0]
+    n = _rows(A)
+    if smoothers is None:
+        smoothers = cheby_setup_device(bh, levels)
+    x = torch.zeros_like(b)
+    r = b.clone()
+    res = [float(torch.linalg.norm(r))]
+    p, rz, its = None, 0.0, 0
+    while res[-1] > tol * res[0] and its < maxiter:
+        z = _vcycle_chebyshev(bh, levels, r, None, 1, 1, smoothers, 0)
+        rz_new = float(torch.dot(r, z))
+        p = z if p is None else z + (rz_new / rz) * p
+        rz = rz_new
+        q, _, pq = csr_spmv_dots_device(bh, n, n, A, p, w=p)
+        alpha = rz / pq
         x = x + alpha * p
         r = r - alpha * q
         res.append(float(torch.linalg.norm(r)))

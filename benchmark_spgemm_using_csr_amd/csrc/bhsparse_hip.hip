@@ -435,6 +435,9 @@ struct bhs_handle {
     // the C/F splitting and the interpolation (bhs_host_cfsplit.inc.h): the two word arrays, the C-point bitmap and the scanned
     // offsets in its queue buffer, the C points per bitmap word -- or the entries per row of P -- in its count buffer
     SideWs cfWs;
+    // the relaxation (bhs_host_relax.inc.h): the queues of the rows beyond the short bin (2 x n ints) and, behind them, three
+    // vectors of n values; the product with its reductions: its results behind the counters, the queues, the partials
+    SideWs rxWs, dotWs;
     // the assembly from triplets (bhs_host_assemble.inc.h): the raw rows' queues by bin in its queue buffer, the kept triplets per
     // row and then the heads per bitmap word in its count buffer
     SideWs asWs;
@@ -614,6 +617,7 @@ inline int one_launch(int rc) { return rc != BHS_SUCCESS ? rc : 1; }
 #include "bhs_host_forest.inc.h"
 #include "bhs_host_cfsplit.inc.h"
 #include "bhs_host_assemble.inc.h"
+#include "bhs_host_relax.inc.h"
 #include "bhs_host_transpose.inc.h"
 #include "bhs_host_reduce.inc.h"
 #include "bhs_host_semiring.inc.h"

@@ -94,6 +94,33 @@ def residual_csr(m, n, Ap, Aj, Ax, x, b, value_dtype=np.float64, device=0):
     return spmv_csr(m, n, Ap, Aj, Ax, x, alpha=-1.0, beta=1.0, y=b, value_dtype=value_dtype, device=device)
 
 
+# ---------------------------------------------------------------- the product with its reductions
+def csr_spmv_dots_raw_device(bh, m, n, nnzA, d_valA, d_rowPtrA, d_colIndA, alpha, d_x, beta, d_y, d_z, d_w, dots):
+    """bhs_csr_spmv_dots_device on caller-given arrays, the C arguments in order (include/bhsparse_hip.h, "relaxation and
+    fused products"; d_valA, d_y with beta == 0 and d_w may be None; d_z may be d_y itself; dots: a numpy float64 array of
+    two on the host, or None): the status code; sets bh.spmv_dots_ms."""
+    if bh._h is None:
+        return _lib.BHS_ERR_NOT_READY
+    out = None if dots is None else dots.ctypes.data_as(C.POINTER(C.c_double))
+    return bh._timed(bh._lib.bhs_csr_spmv_dots_device, "spmv_dots_ms", int(m), int(n), int(nnzA), _ptr(d_valA), _ptr(d_rowPtrA),
+                     _ptr(d_colIndA), float(alpha), _ptr(d_x), float(beta), _ptr(d_y), _ptr(d_z), _ptr(d_w), out)
+
+
+def csr_spmv_dots_device(bh, m, n, A, x, alpha=1.0, beta=0.0, y=None, w=None):
+    """z = alpha A x + beta y out of place with the reductions of the stored z, in one call: A = (rowPtr, colInd, val or
+    None), x (n values), y (m values; None with beta == 0) and w (m values or None; may be x itself when m == n) torch
+    tensors on the handle's GPU.  Returns (z, zz, wz): z made here, zz = sum z_i^2 and wz = sum w_i z_i as Python floats
+    (wz None without w).  r = b - A x with ||r||^2 is alpha = -1, beta = 1, y = b; q = A p with <p, q> is w = p.  Raises
+    BhsparseError on failure."""
+    import torch
+    Ap, Aj, Ax = A
+    z = _alloc(m, x.dtype, x.device)[:m]
+    dots = np.zeros(2, np.float64)
+    torch.cuda.synchronize()                           # the library works on its own stream (see facade.initData_device)
+    _check(csr_spmv_dots_raw_device(bh, m, n, Aj.numel(), Ax, Ap, Aj, alpha, x, beta, y, z, w, dots), "bhs_csr_spmv_dots_device")
+    return z, float(dots[0]), (None if w is None else float(dots[1]))
+
+
 # ---------------------------------------------------------------- over a semiring, with mask and accumulate
 def _semiring(semiring):
     """a BHS_SR_* constant from a name of _lib.SEMIRINGS or from the constant itself"""

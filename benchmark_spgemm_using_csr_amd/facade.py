@@ -92,6 +92,8 @@ class bhsparse(object):
         self.reduce_ms = 0.0
         self.scale_ms = 0.0
         self.spmv_ms = 0.0
+        self.spmv_dots_ms = 0.0
+        self.relax_ms = 0.0
         self.spmv_changed = 0
         self.push_next = 0
         self.semiring_ms = 0.0

@@ -95,6 +95,21 @@ public:
                         const index_type *d_colIndA, int k, double alpha, const value_type *d_X, long long ldX, double beta,
                         value_type *d_Y, long long ldY);
 
+    // EXTENSION, not part of the reference's API: polynomial relaxation and the product with its reductions
+    // (bhs_csr_relax_device, bhs_csr_spmv_dots_device, bhs_chebyshev_coefficients; include/bhsparse_hip.h, "relaxation and
+    // fused products") on DEVICE arrays.  csr_relax_device: `steps` sweeps on the n x n matrix A in one call, coef a HOST
+    // array of the 2 * steps numbers (a_0, c_0), (a_1, c_1), ..: d <- c (b - A x) / diag + a d, x <- x + d; d_d may be 0
+    // where every a is 0; flags BHS_RELAX_ZERO_GUESS or 0.  csr_spmv_dots_device: z = alpha A x + beta y out of place (d_z
+    // may be d_y; d_y may be 0 where beta == 0) with dots[0] = z.z and dots[1] = w.z (d_w may be 0) on the HOST.  Both need
+    // initPlatform only.  chebyshev_coefficients fills coef for the spectrum interval [lmin, lmax]; no device work.
+    int csr_relax_device(int n, int nnzA, const value_type *d_valA, const index_type *d_rowPtrA, const index_type *d_colIndA,
+                         const value_type *d_diag, int steps, const double *coef, const value_type *d_b, value_type *d_x,
+                         value_type *d_d, unsigned flags);
+    int csr_spmv_dots_device(int m, int n, int nnzA, const value_type *d_valA, const index_type *d_rowPtrA,
+                             const index_type *d_colIndA, double alpha, const value_type *d_x, double beta,
+                             const value_type *d_y, value_type *d_z, const value_type *d_w, double *dots);
+    static int chebyshev_coefficients(double lmin, double lmax, int steps, double *coef);
+
     // EXTENSION, not part of the reference's API: semiring CSR x dense with an output mask and accumulation
     // (bhs_csr_spmv_semiring_device, bhs_csr_spmm_semiring_device, include/bhsparse_hip.h, "semiring CSR x dense") on DEVICE
     // arrays: Y<M> (+)= A (+).(x) X; semiring: a BHS_SR_* constant, flags: BHS_MV_ACCUM | BHS_MV_MASK_COMPLEMENT, d_mask /
@@ -372,6 +387,27 @@ inline int bhsparse::csr_spmm_device(int m, int n, int nnzA, const value_type *d
 {
     if (!_h) return BHS_ERR_NOT_READY;
     return bhs_csr_spmm_device(_h, m, n, nnzA, d_valA, d_rowPtrA, d_colIndA, k, alpha, d_X, ldX, beta, d_Y, ldY, 0);
+}
+
+inline int bhsparse::csr_relax_device(int n, int nnzA, const value_type *d_valA, const index_type *d_rowPtrA,
+                                      const index_type *d_colIndA, const value_type *d_diag, int steps, const double *coef,
+                                      const value_type *d_b, value_type *d_x, value_type *d_d, unsigned flags)
+{
+    if (!_h) return BHS_ERR_NOT_READY;
+    return bhs_csr_relax_device(_h, n, nnzA, d_valA, d_rowPtrA, d_colIndA, d_diag, steps, coef, d_b, d_x, d_d, flags, 0);
+}
+
+inline int bhsparse::csr_spmv_dots_device(int m, int n, int nnzA, const value_type *d_valA, const index_type *d_rowPtrA,
+                                          const index_type *d_colIndA, double alpha, const value_type *d_x, double beta,
+                                          const value_type *d_y, value_type *d_z, const value_type *d_w, double *dots)
+{
+    if (!_h) return BHS_ERR_NOT_READY;
+    return bhs_csr_spmv_dots_device(_h, m, n, nnzA, d_valA, d_rowPtrA, d_colIndA, alpha, d_x, beta, d_y, d_z, d_w, dots, 0);
+}
+
+inline int bhsparse::chebyshev_coefficients(double lmin, double lmax, int steps, double *coef)
+{
+    return bhs_chebyshev_coefficients(lmin, lmax, steps, coef);
 }
 
 inline int bhsparse::csr_spmv_semiring_device(int semiring, int m, int n, int nnzA, const value_type *d_valA,

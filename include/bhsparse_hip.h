@@ -680,6 +680,83 @@ BHS_API int bhs_csr_spmm_device(bhs_handle *h, int m, int n, int nnzA,
         int k, double alpha, const bhs_value_t *d_X /* n x k */, long long ldX /* >= k */,
         double beta, bhs_value_t *d_Y /* m x k, in/out */, long long ldY /* >= k */, double *ms_out /* may be NULL */);
 
+/* ---- relaxation and fused products ----------------------------------------
+ * What a multigrid cycle and a Krylov iteration do between two setups, as library calls with every array on the device
+ * (no reference counterpart; bhs_relax.hip.h): `steps` sweeps of a polynomial smoother in one call -- weighted Jacobi, or
+ * a Chebyshev polynomial in D^-1 A with the coefficients of bhs_chebyshev_coefficients --, and the vector product together
+ * with the reductions an iteration wants of its result: r = b - A x with ||r||^2, q = A p with <p, q>.
+ * A (A is n x n for the relaxation, m x n for the product): as "CSR x dense" -- 0-based int32 CSR, rows need NOT be
+ *   ascending, duplicate (row, column) pairs are legal and add up, sizes may be 0, d_valA may be NULL: every entry then
+ *   counts as the value 1.
+ * All calls but bhs_chebyshev_coefficients are synchronous on the handle's stream, need no bound data, return
+ * BHS_ERR_INVALID_ARG between bhs_spgemm_symbolic and bhs_spgemm_finish, and leave the handle as "CSR x dense" leaves it:
+ * their workspaces are buffers of their own from the grow-only pool; C of the last multiply, a served sum or selection,
+ * "class_state", the speculative-launch figures and every option stay.  ms_out (may be NULL): device time of the call.
+ *
+ * bhs_csr_relax_device.  coef holds `steps` pairs (a_s, c_s) on the HOST.  Step s, for all rows at once and reading only
+ *   the x from before the step:
+ *     sum_i = the products double(a) * double(x) of row i, summed in double from +0 exactly as bhs_csr_spmv_device sums
+ *             them (the same bits); r = double(b_i) - sum_i; q = r / double(diag_i); dn = c_s * q; where a_s != 0,
+ *             dn = dn + a_s * double(d_i); d_i <- (bhs_value_t) dn (stored when d_d is not NULL);
+ *             x_i <- (bhs_value_t)(double(x_i) + dn).
+ *   a_s == 0 never reads d_d.  d_diag is the divisor of every row, given by the caller (the diagonal of A, as a rule); a
+ *   zero or non-finite diag_i propagates by IEEE.  c_s == 0 takes no shortcut.  The operations after the row sum round
+ *   one by one (no contraction), so numpy reproduces them bit for bit from the sum.  Weighted Jacobi is a = 0, c = omega.
+ *   BHS_RELAX_ZERO_GUESS: x counts as +0 in step 0 -- d_x is never read before it is written and may hold NaN -- and
+ *   step 0 runs no product pass: dn = c_0 * b / diag (+ a_0 d).  A cycle's coarse levels and every application of a
+ *   preconditioner start from zero: one of `steps` products saved.
+ *   In place without a race: a step reads x from one array and writes another (d_x and two vectors of the workspace take
+ *   turns); the result ends in d_x.
+ *   Rows are binned once, in step 0, as the reductions bin them; later steps reuse the queues: one round trip for the
+ *   queues' lengths (only when nnzA > 32) and one at the end, whatever `steps` is.  Kernel-stat families: relax_short,
+ *   relax_wave, relax_long -- one launch per product pass each, for the bins that have rows (relax_short always) --,
+ *   relax_zero (step 0 under ZERO_GUESS: the row pointer's check, the queues, the update) and relax_finish (the copy of a
+ *   call whose last step may not write the caller's arrays yet: steps == 1, or steps == 2 under ZERO_GUESS).
+ *   Reproducibility: the same arrays give the same bits from run to run and from handle to handle; one call of S steps
+ *   gives the bits of S chained calls of one step with d_d carried between them.
+ *   Validation: on the device, before the dependent read, with the refusals of "CSR x dense": rowPtrA[0] != 0, a
+ *   decreasing rowPtrA, rowPtrA[n] != nnzA, a column outside [0, n) return BHS_ERR_INVALID_ARG.  Stricter than there, a
+ *   refused call leaves d_x and d_d untouched: up to and including the first product pass, which reads every column, the
+ *   kernels write the workspace only, and every later kernel leaves at once where the error word is raised.
+ *   On the host: a NULL handle, negative sizes, steps < 1, a NULL coef or a non-finite coefficient, unknown flag bits, a
+ *   NULL d_rowPtrA, a NULL d_colIndA with nnzA > 0, a NULL d_diag, d_b or d_x with n > 0, a NULL d_d with n > 0 and some
+ *   a_s != 0, or d_x or d_d overlapping each other or an input return BHS_ERR_INVALID_ARG with nothing written.
+ *
+ * bhs_chebyshev_coefficients.  A host function without device work: the `steps` pairs for the Chebyshev iteration on the
+ *   interval [lmin, lmax] of the spectrum of D^-1 A (Saad, Iterative Methods for Sparse Linear Systems, Algorithm 12.1).
+ *   theta = (lmax + lmin) / 2, delta = (lmax - lmin) / 2, sigma = theta / delta; step 0: (0, 1 / theta), rho_0 = 1 / sigma;
+ *   step s >= 1: rho_s = 1 / (2 sigma - rho_(s-1)), (rho_s rho_(s-1), 2 rho_s / delta).  The error after s steps is
+ *   T_s((theta - lambda) / delta) / T_s(sigma) on every eigen-component lambda.  Anything but 0 < lmin < lmax, both
+ *   finite, steps >= 1 and a coef that is not NULL returns BHS_ERR_INVALID_ARG.
+ *
+ * bhs_csr_spmv_dots_device.  z = alpha A x + beta y with the arithmetic, the single rounding, the kernels and the bits
+ *   of bhs_csr_spmv_device, out of place: d_z may be exactly d_y (in place) and may overlap no other input; otherwise y is
+ *   copied to z on the device first.  beta == 0 never reads d_y, which may then be NULL.  Then, of the STORED z:
+ *     dots[0] = sum of double(z_i)^2;  dots[1] = sum of double(w_i) * double(z_i), left unwritten when d_w is NULL.
+ *   d_w may be d_x when m == n.  Both sums run in double over 4096 consecutive elements a workgroup and then over the
+ *   workgroups' partials in their order, by one workgroup: an order that is a function of m and the build alone, no atomic
+ *   on a result; non-finite values propagate.  8 to 16 bytes a row beside the product's 12 bytes an entry.  dots is on the
+ *   HOST and is written on success only; a refused call may leave z partly written, as y there.  Refusals: those of
+ *   bhs_csr_spmv_device, a NULL dots, a NULL d_y with beta != 0 and m > 0, d_z overlapping d_w.  k = 1 only.
+ *   Kernel-stat families: spmv_short, spmv_wave, spmv_long, dots_part, dots_finish.                                     */
+#define BHS_RELAX_ZERO_GUESS 1u
+BHS_API int bhs_csr_relax_device(bhs_handle *h, int n, int nnzA,
+        const bhs_value_t *d_valA /* may be NULL: every entry counts as 1 */,
+        const int *d_rowPtrA, const int *d_colIndA,
+        const bhs_value_t *d_diag /* n: the divisor of row i */,
+        int steps, const double *coef /* HOST: 2 * steps, (a_0, c_0), (a_1, c_1), .. */,
+        const bhs_value_t *d_b /* n */, bhs_value_t *d_x /* n, in/out */,
+        bhs_value_t *d_d /* n, in/out; may be NULL when every a_s == 0 */,
+        unsigned flags /* BHS_RELAX_ZERO_GUESS or 0 */, double *ms_out /* may be NULL */);
+BHS_API int bhs_chebyshev_coefficients(double lmin, double lmax, int steps, double *coef /* out: 2 * steps */);
+BHS_API int bhs_csr_spmv_dots_device(bhs_handle *h, int m, int n, int nnzA,
+        const bhs_value_t *d_valA /* may be NULL */, const int *d_rowPtrA, const int *d_colIndA,
+        double alpha, const bhs_value_t *d_x /* n */,
+        double beta, const bhs_value_t *d_y /* m; may be NULL when beta == 0 */,
+        bhs_value_t *d_z /* m, out; may be exactly d_y */,
+        const bhs_value_t *d_w /* m; may be NULL; may be d_x when m == n */,
+        double *dots /* HOST: 2 */, double *ms_out /* may be NULL */);
+
 /* ---- semiring CSR x dense -------------------------------------------------
  * One step of a graph traversal with every array on the device: y<mask> (+)= A (+).(x) x and, for k vectors (k sources)
  * at once, Y<M> (+)= A (+).(x) X over the eight semirings of "semiring multiply" (GraphBLAS mxv / mxm with a dense
