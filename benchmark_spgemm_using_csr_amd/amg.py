@@ -40,15 +40,8 @@ def _tdt(bh):
 def aggregate_raw_device(bh, n, nnzS, d_rowPtrS, d_colIndS, d_prio, seed, flags, d_agg, d_roots):
     """bhs_csr_aggregate_device on caller-given arrays, the C arguments in order (d_prio and d_roots may be None): the status
     code; sets bh.aggregate_ms, bh.aggregate_nagg and bh.aggregate_rounds on success."""
-    if bh._h is None:
-        return _lib.BHS_ERR_NOT_READY
-    nagg, rounds, ms = C.c_int(0), C.c_int(0), C.c_double(0)
-    err = bh._lib.bhs_csr_aggregate_device(bh._h, int(n), int(nnzS), _ptr(d_rowPtrS), _ptr(d_colIndS), _ptr(d_prio),
-                                           int(seed) & 0xFFFFFFFF, int(flags), _ptr(d_agg), _ptr(d_roots), C.byref(nagg),
-                                           C.byref(rounds), C.byref(ms))
-    if err == _lib.BHS_SUCCESS:
-        bh.aggregate_ms, bh.aggregate_nagg, bh.aggregate_rounds = float(ms.value), int(nagg.value), int(rounds.value)
-    return err
+    return bh._counted("bhs_csr_aggregate_device", "aggregate", "nagg", "rounds", int(n), int(nnzS), _ptr(d_rowPtrS),
+                       _ptr(d_colIndS), _ptr(d_prio), int(seed) & 0xFFFFFFFF, int(flags), _ptr(d_agg), _ptr(d_roots))
 
 
 def aggregate_device(bh, n, S, seed=0, prio=None):
@@ -69,15 +62,8 @@ def aggregate_device(bh, n, S, seed=0, prio=None):
 def match_raw_device(bh, n, nnzA, d_rowPtrA, d_colIndA, d_valA, seed, flags, d_mate, d_agg):
     """bhs_csr_match_device on caller-given arrays, the C arguments in order (d_valA and d_agg may be None): the status code;
     sets bh.match_ms, bh.match_npairs and bh.match_rounds on success."""
-    if bh._h is None:
-        return _lib.BHS_ERR_NOT_READY
-    npairs, rounds, ms = C.c_int(0), C.c_int(0), C.c_double(0)
-    err = bh._lib.bhs_csr_match_device(bh._h, int(n), int(nnzA), _ptr(d_rowPtrA), _ptr(d_colIndA), _ptr(d_valA),
-                                       int(seed) & 0xFFFFFFFF, int(flags), _ptr(d_mate), _ptr(d_agg), C.byref(npairs),
-                                       C.byref(rounds), C.byref(ms))
-    if err == _lib.BHS_SUCCESS:
-        bh.match_ms, bh.match_npairs, bh.match_rounds = float(ms.value), int(npairs.value), int(rounds.value)
-    return err
+    return bh._counted("bhs_csr_match_device", "match", "npairs", "rounds", int(n), int(nnzA), _ptr(d_rowPtrA),
+                       _ptr(d_colIndA), _ptr(d_valA), int(seed) & 0xFFFFFFFF, int(flags), _ptr(d_mate), _ptr(d_agg))
 
 
 def match_device(bh, n, A, seed=0):
@@ -141,15 +127,8 @@ def pairwise_aggregate_device(handles, n, A, passes=2, seed=0):
 def cfsplit_raw_device(bh, n, nnzS, d_rowPtrS, d_colIndS, d_prio, seed, flags, d_cf, d_cpts):
     """bhs_csr_cfsplit_device on caller-given arrays, the C arguments in order (d_prio and d_cpts may be None): the status code;
     sets bh.cfsplit_ms, bh.cfsplit_nc and bh.cfsplit_rounds on success."""
-    if bh._h is None:
-        return _lib.BHS_ERR_NOT_READY
-    nc, rounds, ms = C.c_int(0), C.c_int(0), C.c_double(0)
-    err = bh._lib.bhs_csr_cfsplit_device(bh._h, int(n), int(nnzS), _ptr(d_rowPtrS), _ptr(d_colIndS), _ptr(d_prio),
-                                         int(seed) & 0xFFFFFFFF, int(flags), _ptr(d_cf), _ptr(d_cpts), C.byref(nc),
-                                         C.byref(rounds), C.byref(ms))
-    if err == _lib.BHS_SUCCESS:
-        bh.cfsplit_ms, bh.cfsplit_nc, bh.cfsplit_rounds = float(ms.value), int(nc.value), int(rounds.value)
-    return err
+    return bh._counted("bhs_csr_cfsplit_device", "cfsplit", "nc", "rounds", int(n), int(nnzS), _ptr(d_rowPtrS),
+                       _ptr(d_colIndS), _ptr(d_prio), int(seed) & 0xFFFFFFFF, int(flags), _ptr(d_cf), _ptr(d_cpts))
 
 
 def cfsplit_device(bh, n, S, seed=0, prio=None, degree=True):
@@ -239,15 +218,9 @@ def interp_direct_device(bh, n, A, S, cf, nc):
 def color_raw_device(bh, n, nnzS, d_rowPtrS, d_colIndS, d_prio, seed, flags, d_color, d_order, d_colorPtr):
     """bhs_csr_color_device on caller-given arrays, the C arguments in order (d_prio may be None): the status code; sets
     bh.color_ms, bh.color_ncolors and bh.color_rounds on success."""
-    if bh._h is None:
-        return _lib.BHS_ERR_NOT_READY
-    ncolors, rounds, ms = C.c_int(0), C.c_int(0), C.c_double(0)
-    err = bh._lib.bhs_csr_color_device(bh._h, int(n), int(nnzS), _ptr(d_rowPtrS), _ptr(d_colIndS), _ptr(d_prio),
-                                       int(seed) & 0xFFFFFFFF, int(flags), _ptr(d_color), _ptr(d_order), _ptr(d_colorPtr),
-                                       C.byref(ncolors), C.byref(rounds), C.byref(ms))
-    if err == _lib.BHS_SUCCESS:
-        bh.color_ms, bh.color_ncolors, bh.color_rounds = float(ms.value), int(ncolors.value), int(rounds.value)
-    return err
+    return bh._counted("bhs_csr_color_device", "color", "ncolors", "rounds", int(n), int(nnzS), _ptr(d_rowPtrS),
+                       _ptr(d_colIndS), _ptr(d_prio), int(seed) & 0xFFFFFFFF, int(flags), _ptr(d_color), _ptr(d_order),
+                       _ptr(d_colorPtr))
 
 
 def color_device(bh, n, S, seed=0, prio=None):
@@ -634,25 +607,26 @@ def rs_setup_device(handles, n, A, theta=0.25, max_levels=10, min_coarse=40, see
     return _setup_levels(handles, n, A, coarsen, None, max_levels, min_coarse, prolong, "nc")
 
 
+def _setup_csr(setup, n, Ap, Aj, Ax, value_dtype, device, *args):
+    """setup((h1, h2), n, A, *args) -- one of the three hierarchies -- on a host CSR matrix, the levels copied back"""
+    A = _device_csr(Ap, Aj, Ax, value_dtype, device)
+    with _handle(value_dtype, device, None) as h1, _handle(value_dtype, device, None) as h2:
+        levels, info = setup((h1, h2), n, A, *args)
+    host = lambda M: None if M is None else _host(*M)   # noqa: E731
+    return [(host(a), host(p), host(r)) for a, p, r in levels], info
+
+
 def rs_setup_csr(n, Ap, Aj, Ax, theta=0.25, max_levels=10, min_coarse=40, seed=0, value_dtype=np.float64, device=0):
     """Convenience: rs_setup_device on a host CSR matrix (rows strictly ascending), built on the device and copied back, as
     sa_setup_csr."""
-    A = _device_csr(Ap, Aj, Ax, value_dtype, device)
-    with _handle(value_dtype, device, None) as h1, _handle(value_dtype, device, None) as h2:
-        levels, info = rs_setup_device((h1, h2), n, A, theta, max_levels, min_coarse, seed)
-    host = lambda M: None if M is None else _host(*M)   # noqa: E731
-    return [(host(a), host(p), host(r)) for a, p, r in levels], info
+    return _setup_csr(rs_setup_device, n, Ap, Aj, Ax, value_dtype, device, theta, max_levels, min_coarse, seed)
 
 
 def pa_setup_csr(n, Ap, Aj, Ax, passes=3, omega=2.0 / 3.0, max_levels=10, min_coarse=40, seed=0, value_dtype=np.float64,
                  device=0):
     """Convenience: pa_setup_device on a host CSR matrix (rows strictly ascending), built on the device and copied back, as
     sa_setup_csr."""
-    A = _device_csr(Ap, Aj, Ax, value_dtype, device)
-    with _handle(value_dtype, device, None) as h1, _handle(value_dtype, device, None) as h2:
-        levels, info = pa_setup_device((h1, h2), n, A, passes, omega, max_levels, min_coarse, seed)
-    host = lambda M: None if M is None else _host(*M)   # noqa: E731
-    return [(host(a), host(p), host(r)) for a, p, r in levels], info
+    return _setup_csr(pa_setup_device, n, Ap, Aj, Ax, value_dtype, device, passes, omega, max_levels, min_coarse, seed)
 
 
 def sa_setup_csr(n, Ap, Aj, Ax, theta=0.0, omega=2.0 / 3.0, max_levels=10, min_coarse=40, seed=0, value_dtype=np.float64,
@@ -660,11 +634,7 @@ def sa_setup_csr(n, Ap, Aj, Ax, theta=0.0, omega=2.0 / 3.0, max_levels=10, min_c
     """Convenience: the hierarchy of a host CSR matrix (rows strictly ascending), built on the device and copied back.
     Returns (levels, info): levels a list of (A_l, P_l, R_l) with every matrix a (rowPtr, colInd, val) triple of numpy
     arrays, None for P and R on the last; info as sa_setup_device."""
-    A = _device_csr(Ap, Aj, Ax, value_dtype, device)
-    with _handle(value_dtype, device, None) as h1, _handle(value_dtype, device, None) as h2:
-        levels, info = sa_setup_device((h1, h2), n, A, theta, omega, max_levels, min_coarse, seed)
-    host = lambda M: None if M is None else _host(*M)   # noqa: E731
-    return [(host(a), host(p), host(r)) for a, p, r in levels], info
+    return _setup_csr(sa_setup_device, n, Ap, Aj, Ax, value_dtype, device, theta, omega, max_levels, min_coarse, seed)
 
 
 # ---------------------------------------------------------------- the cycle
@@ -824,14 +794,8 @@ def _pcg_chebyshev(bh, levels, b, tol, maxiter, smoothers=None):
 def levels_raw_device(bh, n, nnzA, d_rowPtrA, d_colIndA, flags, d_level, d_order, d_levelPtr):
     """bhs_csr_levels_device on caller-given arrays, the C arguments in order: the status code; sets bh.levels_ms,
     bh.levels_nlevels and bh.levels_passes (the passes depend on timing) on success."""
-    if bh._h is None:
-        return _lib.BHS_ERR_NOT_READY
-    nlevels, passes, ms = C.c_int(0), C.c_int(0), C.c_double(0)
-    err = bh._lib.bhs_csr_levels_device(bh._h, int(n), int(nnzA), _ptr(d_rowPtrA), _ptr(d_colIndA), int(flags), _ptr(d_level),
-                                        _ptr(d_order), _ptr(d_levelPtr), C.byref(nlevels), C.byref(passes), C.byref(ms))
-    if err == _lib.BHS_SUCCESS:
-        bh.levels_ms, bh.levels_nlevels, bh.levels_passes = float(ms.value), int(nlevels.value), int(passes.value)
-    return err
+    return bh._counted("bhs_csr_levels_device", "levels", "nlevels", "passes", int(n), int(nnzA), _ptr(d_rowPtrA),
+                       _ptr(d_colIndA), int(flags), _ptr(d_level), _ptr(d_order), _ptr(d_levelPtr))
 
 
 def levels_device(bh, n, A, upper=False):

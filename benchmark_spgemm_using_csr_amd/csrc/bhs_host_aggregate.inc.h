@@ -1,12 +1,13 @@
 // bhs_host_aggregate.inc.h -- MIS(2) aggregation of a pattern of strong connections (bhs_csr_aggregate_device; kernels in
 // bhs_aggregate.hip.h)
-// (A part of bhsparse_hip.hip's translation unit: included there directly after bhs_host_push_sr.inc.h.)
+// (A part of bhsparse_hip.hip's translation unit, on the shared pieces of bhs_host_side.inc.h.)
 //
 // A workspace of its own (h->aggWs): the control block of bhs_aggregate.hip.h; in its queue buffer the vertices' words, the
 // first gather's result (8 bytes a vertex each), the root bitmap (a word per 64 vertices) and pass 1's aggregates (an int a
 // vertex); in its count buffer the roots per bitmap word, scanned in place, the scanned offsets copied to h->aggOff.
-// A round is two launches and ONE round trip, for the error word and the count of undecided vertices; the loop ends when
-// the count is zero, and with BHS_ERR_INTERNAL when a round decides nothing or after n + 1 rounds.
+// A round is two launches and ONE round trip, for the error word and the count of undecided vertices (side_rounds: the loop
+// ends when the count is zero, and with BHS_ERR_INTERNAL when a round decides nothing or after n + 1 rounds); the call's
+// close is one more, for the number of roots.
 
 #include "bhs_aggregate.hip.h"
 
@@ -19,43 +20,22 @@ struct AgIn {
     int* agg; int* roots;
 };
 
-constexpr SideScanWords kAgScan = {AG_TICKET, AG_TOTAL, AG_BINS, AG_MAXCNT};
-
-// lanes per row from the pattern's mean row length: 1, 4, 16 or 64
-int ag_lanes(const AgDims& d)
-{
-    const double mean = d.n > 0 ? (double)d.nnzS / d.n : 0.0;
-    return mean <= 4.0 ? 1 : mean <= 16.0 ? 4 : mean <= 64.0 ? 16 : 64;
-}
-
 template <int L>
 int ag_rounds(bhs_handle* h, const AgIn& in, rd_u64* w, rd_u64* t1, int* ctl, int* rounds_out)
 {
     const AgDims& d = in.d;
-    SideWs& ws = h->aggWs;
     const unsigned grid = (unsigned)(((long long)d.n + 256 / L - 1) / (256 / L));
     const unsigned gridDecide = std::min<unsigned>(grid, (unsigned)h->numCU * 16);   // (a block loop: one add to the count a workgroup)
-    long long left = d.n;
-    for (long long round = 1;; ++round) {
-        if (round > (long long)d.n + 1) return BHS_ERR_INTERNAL;
-        BHS_HIP(hipMemsetAsync(ctl + AG_UNDEC, 0, sizeof(rd_u64), h->stream));
+    return side_rounds(h, h->aggWs, d.n, AG_INTS, rounds_out, [&](long long, long long left) {
         BHS_TRY(timed(h, "agg_near", d.n, [&] {
             hipLaunchKernelGGL(k_agg_near<L>, dim3(grid), dim3(256), 0, h->stream, d, in.Sp, in.Sj, (const rd_u64*)w, t1, ctl);
             return 1;
         }));
-        BHS_TRY(timed(h, "agg_decide", left, [&] {
+        return timed(h, "agg_decide", left, [&] {
             hipLaunchKernelGGL(k_agg_decide<L>, dim3(gridDecide), dim3(256), 0, h->stream, d, in.Sp, in.Sj, (const rd_u64*)t1, w, ctl);
             return 1;
-        }));
-        BHS_TRY(side_read_ctl(h, ws, AG_INTS));                       // the error word and the count: the round's one round trip
-        if (ws.host[RD_ERR]) return BHS_ERR_INVALID_ARG;
-        long long now = 0;
-        memcpy(&now, ws.host + AG_UNDEC, sizeof(now));
-        *rounds_out = (int)round;
-        if (now == 0) return BHS_SUCCESS;
-        if (now >= left) return BHS_ERR_INTERNAL;                     // (the undecided vertex of greatest key is always decided)
-        left = now;
-    }
+        });
+    });
 }
 
 template <int L>
@@ -76,8 +56,9 @@ int ag_run(bhs_handle* h, const AgIn& in, int* nagg_out, int* rounds_out, double
     const AgDims& d = in.d;
     SideWs& ws = h->aggWs;
     const size_t n = (size_t)d.n, nWords = (n + 63) / 64;
-    BHS_TRY(side_prepare(h, ws, AG_INTS, sizeof(rd_u64) * (2 * n + nWords) + sizeof(int) * n, nWords + 1));
+    BHS_TRY(side_open(h, ws, AG_INTS, sizeof(rd_u64) * (2 * n + nWords) + sizeof(int) * n, nWords + 1));
     BHS_TRY(ensure(h, h->aggOff, sizeof(int) * (nWords + 1)));
+    BHS_TRY(side_start(h, ws));
     int* ctl = (int*)ws.ctl.p;
     int* cnt = (int*)ws.cnt.p;
     int* off = (int*)h->aggOff.p;
@@ -85,18 +66,14 @@ int ag_run(bhs_handle* h, const AgIn& in, int* nagg_out, int* rounds_out, double
     rd_u64* t1 = w + n;
     rd_u64* map = t1 + n;
     int* agg1 = (int*)(map + nWords);
-    BHS_HIP(hipMemsetAsync(ctl, 0, sizeof(int) * AG_INTS, h->stream));
-    side_reset_stats(h);
-    BHS_TRY(side_begin(h, ws));
     const unsigned gridN = (unsigned)((n + 255) / 256);
     BHS_TRY(timed(h, "agg_init", d.n, [&] {
         hipLaunchKernelGGL(k_agg_init, dim3(gridN), dim3(256), 0, h->stream, d, in.Sp, in.prio, w, ctl);
         return 1;
     }));
-    const int L = ag_lanes(d);
+    const int L = side_lanes(d.n, d.nnzS);
     int rounds = 0;
-    BHS_TRY(L == 1 ? ag_rounds<1>(h, in, w, t1, ctl, &rounds) : L == 4 ? ag_rounds<4>(h, in, w, t1, ctl, &rounds)
-            : L == 16 ? ag_rounds<16>(h, in, w, t1, ctl, &rounds) : ag_rounds<64>(h, in, w, t1, ctl, &rounds));
+    BHS_TRY(with_lanes(L, [&](auto l) { return ag_rounds<l.value>(h, in, w, t1, ctl, &rounds); }));
     BHS_TRY(timed(h, "agg_scan", d.n, [&] {
         hipLaunchKernelGGL(k_agg_count, dim3(gridN), dim3(256), 0, h->stream, d.n, (const rd_u64*)w, map, cnt);
         return 1;
@@ -107,12 +84,10 @@ int ag_run(bhs_handle* h, const AgIn& in, int* nagg_out, int* rounds_out, double
                            (const rd_u64*)map, (const int*)off, agg1, in.roots);
         return 1;
     }));
-    BHS_TRY(L == 1 ? ag_join<1>(h, in, w, agg1, ctl) : L == 4 ? ag_join<4>(h, in, w, agg1, ctl)
-            : L == 16 ? ag_join<16>(h, in, w, agg1, ctl) : ag_join<64>(h, in, w, agg1, ctl));
+    BHS_TRY(with_lanes(L, [&](auto l) { return ag_join<l.value>(h, in, w, agg1, ctl); }));
     BHS_TRY(side_end(h, ws));
     BHS_TRY(side_read_ctl(h, ws, AG_INTS));                           // the number of roots
-    BHS_TRY(side_elapsed(h, ws, ms_out));
-    BHS_TRY(side_collect(h, 0));
+    BHS_TRY(side_close(h, ws, ms_out));
     if (ws.host[RD_ERR]) return BHS_ERR_INVALID_ARG;
     long long nagg = 0;
     memcpy(&nagg, ws.host + AG_TOTAL, sizeof(nagg));
@@ -131,18 +106,11 @@ int bhs_csr_aggregate_device(bhs_handle* h, int n, int nnzS, const int* d_rowPtr
 {
     if (!h || h->ps.open || n < 0 || nnzS < 0 || flags != 0) return BHS_ERR_INVALID_ARG;
     if ((n > 0 && (!d_rowPtrS || !d_agg)) || (nnzS > 0 && !d_colIndS)) return BHS_ERR_INVALID_ARG;
-    const struct { const void* p; size_t bytes; } inputs[] = {
-        {d_rowPtrS, sizeof(int) * ((size_t)n + 1)}, {d_colIndS, sizeof(int) * (size_t)nnzS}, {d_prio, sizeof(unsigned) * (size_t)n}};
     const size_t outBytes = sizeof(int) * (size_t)n;
-    for (const auto& x : inputs)
-        if (rd_overlap(d_agg, outBytes, x.p, x.bytes) || rd_overlap(d_roots, outBytes, x.p, x.bytes)) return BHS_ERR_INVALID_ARG;
-    if (rd_overlap(d_agg, outBytes, d_roots, outBytes)) return BHS_ERR_INVALID_ARG;
-    if (n == 0) {                                                     // nothing to aggregate, nothing launched
-        if (nagg_out) *nagg_out = 0;
-        if (rounds_out) *rounds_out = 0;
-        if (ms_out) *ms_out = 0.0;
-        return BHS_SUCCESS;
-    }
+    if (side_aliased({{d_agg, outBytes}, {d_roots, outBytes}},
+                     {{d_rowPtrS, sizeof(int) * ((size_t)n + 1)}, {d_colIndS, sizeof(int) * (size_t)nnzS}, {d_prio, sizeof(unsigned) * (size_t)n}}))
+        return BHS_ERR_INVALID_ARG;
+    if (n == 0) return side_nothing(nagg_out, rounds_out, ms_out);     // nothing to aggregate, nothing launched
     AgIn in;
     in.d.n = n; in.d.nnzS = nnzS; in.d.seed = seed; in.d.hasPrio = d_prio ? 1 : 0;
     in.Sp = d_rowPtrS; in.Sj = d_colIndS; in.prio = d_prio; in.agg = d_agg; in.roots = d_roots;

@@ -144,8 +144,7 @@ int as_run(bhs_handle* h, const AsIn& in, int* nnzZ_out, int* nkept_out, double*
     }
     BHS_TRY(side_end(h, ws));
     BHS_TRY(side_read_ctl(h, ws, AS_INTS));                           // the number of entries, the error word of our own indices
-    BHS_TRY(side_elapsed(h, ws, ms_out));
-    BHS_TRY(side_collect(h, 0));
+    BHS_TRY(side_close(h, ws, ms_out));
     if (ws.host[AS_ERR]) return BHS_ERR_INTERNAL;                     // (a place outside its row: the triplets changed under the call)
     long long nnzZ = 0;
     if (nkept > 0) memcpy(&nnzZ, ws.host + AS_TOTAL_B, sizeof(nnzZ));
@@ -182,8 +181,7 @@ int as_values_run(bhs_handle* h, int nnzIn, const value_t* vals, int nnzZ, const
     }
     BHS_TRY(side_end(h, ws));
     BHS_TRY(side_read_ctl(h, ws, AS_INTS));
-    BHS_TRY(side_elapsed(h, ws, ms_out));
-    BHS_TRY(side_collect(h, 0));
+    BHS_TRY(side_close(h, ws, ms_out));
     return ws.host[AS_ERR] ? (int)BHS_ERR_INVALID_ARG : (int)BHS_SUCCESS;   // (the map changed between the two kernels: not followed)
 }
 
@@ -199,17 +197,10 @@ int bhs_coo_assemble_device(bhs_handle* h, int m, int n, int nnzIn, const int* d
     if (nnzIn > 0 && (!d_rowInd || !d_colInd || !d_colIndZ)) return BHS_ERR_INVALID_ARG;
     if (d_valZ && !d_valIn) return BHS_ERR_INVALID_ARG;
     const size_t nz = (size_t)nnzIn;
-    const struct { const void* p; size_t bytes; } inputs[] = {
-        {d_rowInd, sizeof(int) * nz}, {d_colInd, sizeof(int) * nz}, {d_valIn, sizeof(value_t) * nz}};
-    const struct { const void* p; size_t bytes; } outputs[] = {
-        {d_rowPtrZ, sizeof(int) * ((size_t)m + 1)}, {d_colIndZ, sizeof(int) * nz}, {d_valZ, sizeof(value_t) * nz},
-        {d_entryPtr, sizeof(int) * (nz + 1)}, {d_perm, sizeof(int) * nz}};
-    for (const auto& o : outputs)
-        for (const auto& x : inputs)
-            if (rd_overlap(o.p, o.bytes, x.p, x.bytes)) return BHS_ERR_INVALID_ARG;
-    for (int a = 0; a < 5; ++a)
-        for (int b = a + 1; b < 5; ++b)
-            if (rd_overlap(outputs[a].p, outputs[a].bytes, outputs[b].p, outputs[b].bytes)) return BHS_ERR_INVALID_ARG;
+    if (side_aliased({{d_rowPtrZ, sizeof(int) * ((size_t)m + 1)}, {d_colIndZ, sizeof(int) * nz}, {d_valZ, sizeof(value_t) * nz},
+                      {d_entryPtr, sizeof(int) * (nz + 1)}, {d_perm, sizeof(int) * nz}},
+                     {{d_rowInd, sizeof(int) * nz}, {d_colInd, sizeof(int) * nz}, {d_valIn, sizeof(value_t) * nz}}))
+        return BHS_ERR_INVALID_ARG;
     AsIn in;
     in.m = m; in.n = n; in.nnzIn = nnzIn; in.flags = flags;
     in.rows = d_rowInd; in.cols = d_colInd; in.vals = (const value_t*)d_valIn;
@@ -224,9 +215,8 @@ int bhs_coo_assemble_values_device(bhs_handle* h, int nnzIn, const bhs_value_t* 
     if (flags != kAsSum && flags != kAsFirst && flags != kAsLast) return BHS_ERR_INVALID_ARG;
     if ((nnzIn > 0 && (!d_valIn || !d_perm)) || (nnzZ > 0 && !d_valZ)) return BHS_ERR_INVALID_ARG;
     const size_t zBytes = sizeof(value_t) * (size_t)nnzZ;
-    if (rd_overlap(d_valZ, zBytes, d_valIn, sizeof(value_t) * (size_t)nnzIn) ||
-        rd_overlap(d_valZ, zBytes, d_entryPtr, sizeof(int) * ((size_t)nnzZ + 1)) ||
-        rd_overlap(d_valZ, zBytes, d_perm, sizeof(int) * (size_t)nnzIn))
+    if (side_aliased({{d_valZ, zBytes}}, {{d_valIn, sizeof(value_t) * (size_t)nnzIn}, {d_entryPtr, sizeof(int) * ((size_t)nnzZ + 1)},
+                                          {d_perm, sizeof(int) * (size_t)nnzIn}}))
         return BHS_ERR_INVALID_ARG;
     return guarded(h, [&] {
         return as_values_run(h, nnzIn, (const value_t*)d_valIn, nnzZ, d_entryPtr, d_perm, flags, (value_t*)d_valZ, ms_out);

@@ -1,13 +1,14 @@
 // bhs_host_color.inc.h -- greedy colouring of a pattern and multicolour Gauss-Seidel on top of it (bhs_csr_color_device,
 // bhs_csr_gs_device; kernels in bhs_color.hip.h and bhs_gs.hip.h)
-// (A part of bhsparse_hip.hip's translation unit: included there directly after bhs_host_aggregate.inc.h.)
+// (A part of bhsparse_hip.hip's translation unit, on the shared pieces of bhs_host_side.inc.h; co_order serves the level sets
+// of bhs_host_trsv.inc.h too, which is included after this file.)
 //
 // A workspace of its own (h->colWs), shared by both calls: the control block of bhs_color.hip.h; in its queue buffer the
 // second colour array of the rounds (an int a vertex; the first is the caller's d_color); in its count buffer the table of
 // vertices per (colour, 64 vertices), colour-major, scanned in place, the scanned offsets copied to h->colOff.
 // The colouring: a round is one launch and ONE round trip, for the error word, the count of uncoloured vertices and the
-// colours in use; the loop ends when the count is zero, and with BHS_ERR_INTERNAL when a round colours nothing or after
-// n + 1 rounds.  The order is three launches and a scan, whatever n.
+// colours in use (side_rounds: the loop ends when the count is zero, and with BHS_ERR_INTERNAL when a round colours nothing or
+// after n + 1 rounds).  The order is three launches and a scan, whatever n, and the call's close one more round trip.
 // The relaxation: a launch per non-empty colour and direction, ONE round trip at the end of the call.
 
 #include "bhs_color.hip.h"
@@ -26,35 +27,21 @@ struct CoIn {
     int* color; int* order; int* colorPtr;
 };
 
-// the rounds between `first` (the caller's d_color, all -1) and `second`: *last is the array the last round wrote
+// the rounds between `first` (the caller's d_color, all -1) and `second`: odd rounds read first and write second
 template <int L>
-int co_rounds(bhs_handle* h, const CoIn& in, int* first, int* second, int* ctl, int* rounds_out, int** last)
+int co_rounds(bhs_handle* h, const CoIn& in, int* first, int* second, int* ctl, int* rounds_out)
 {
     const AgDims& d = in.d;
-    SideWs& ws = h->colWs;
     const unsigned rows = (unsigned)(((long long)d.n + 256 / L - 1) / (256 / L));
     const unsigned grid = std::min<unsigned>(rows, (unsigned)h->numCU * 16);   // (a block loop: one add to the count a workgroup)
-    long long left = d.n;
-    int* from = first;
-    int* to = second;
-    for (long long round = 1;; ++round) {
-        if (round > (long long)d.n + 1) return BHS_ERR_INTERNAL;
-        BHS_HIP(hipMemsetAsync(ctl + AG_UNDEC, 0, sizeof(rd_u64), h->stream));
-        BHS_TRY(timed(h, "color_round", left, [&] {
-            hipLaunchKernelGGL(k_col_round<L>, dim3(grid), dim3(256), 0, h->stream, d, in.Sp, in.Sj, in.prio, (const int*)from, to, ctl);
+    return side_rounds(h, h->colWs, d.n, CO_INTS, rounds_out, [&](long long round, long long left) {
+        const int* from = (round & 1) ? first : second;
+        int* to = (round & 1) ? second : first;
+        return timed(h, "color_round", left, [&] {
+            hipLaunchKernelGGL(k_col_round<L>, dim3(grid), dim3(256), 0, h->stream, d, in.Sp, in.Sj, in.prio, from, to, ctl);
             return 1;
-        }));
-        BHS_TRY(side_read_ctl(h, ws, CO_INTS));                       // the error word, the count, the colours: the round's one round trip
-        if (ws.host[RD_ERR]) return BHS_ERR_INVALID_ARG;
-        long long now = 0;
-        memcpy(&now, ws.host + AG_UNDEC, sizeof(now));
-        *rounds_out = (int)round;
-        *last = to;
-        if (now == 0) return BHS_SUCCESS;
-        if (now >= left) return BHS_ERR_INTERNAL;                     // (the uncoloured vertex of greatest key always takes a colour)
-        left = now;
-        std::swap(from, to);
-    }
+        });
+    });
 }
 
 // The order of n vertices by (label, index) and every label's first place, for labels in [0, nlabels): the vertices per
@@ -93,26 +80,21 @@ int co_run(bhs_handle* h, const CoIn& in, int* ncolors_out, int* rounds_out, dou
     const AgDims& d = in.d;
     SideWs& ws = h->colWs;
     const size_t n = (size_t)d.n;
-    BHS_TRY(side_prepare(h, ws, CO_INTS, sizeof(int) * n, 0));
+    BHS_TRY(side_open(h, ws, CO_INTS, sizeof(int) * n, 0));
+    BHS_TRY(side_start(h, ws));
     int* ctl = (int*)ws.ctl.p;
-    BHS_HIP(hipMemsetAsync(ctl, 0, sizeof(int) * CO_INTS, h->stream));
-    side_reset_stats(h);
-    BHS_TRY(side_begin(h, ws));
     BHS_HIP(hipMemsetAsync(in.color, 0xFF, sizeof(int) * n, h->stream));   // -1: no colour
-    const int L = ag_lanes(d);
+    const int L = side_lanes(d.n, d.nnzS);
     int rounds = 0;
-    int* last = in.color;
     int* second = (int*)ws.queue.p;
-    BHS_TRY(L == 1 ? co_rounds<1>(h, in, in.color, second, ctl, &rounds, &last) : L == 4 ? co_rounds<4>(h, in, in.color, second, ctl, &rounds, &last)
-            : L == 16 ? co_rounds<16>(h, in, in.color, second, ctl, &rounds, &last) : co_rounds<64>(h, in, in.color, second, ctl, &rounds, &last));
-    if (last != in.color) BHS_HIP(hipMemcpyAsync(in.color, last, sizeof(int) * n, hipMemcpyDeviceToDevice, h->stream));
+    BHS_TRY(with_lanes(L, [&](auto l) { return co_rounds<l.value>(h, in, in.color, second, ctl, &rounds); }));
+    if (rounds & 1) BHS_HIP(hipMemcpyAsync(in.color, second, sizeof(int) * n, hipMemcpyDeviceToDevice, h->stream));   // (the last round wrote `second`)
     const long long ncolors = ws.host[CO_NCOL];
     if (ncolors < 1 || ncolors > (long long)d.n) return BHS_ERR_INTERNAL;
     BHS_TRY(co_order(h, ws, "color_order", CO_INTS, sizeof(int) * n, d.n, ncolors, in.color, in.order, in.colorPtr));
     BHS_TRY(side_end(h, ws));
     BHS_TRY(side_read_ctl(h, ws, CO_INTS));                           // the order's error word and total
-    BHS_TRY(side_elapsed(h, ws, ms_out));
-    BHS_TRY(side_collect(h, 0));
+    BHS_TRY(side_close(h, ws, ms_out));
     long long total = 0;
     memcpy(&total, ws.host + AG_TOTAL, sizeof(total));
     if (ws.host[RD_ERR] || total != (long long)d.n) return BHS_ERR_INTERNAL;   // (the colours were this call's own)
@@ -137,20 +119,16 @@ typedef void (*GsKernel)(GsDims, const int*, const int*, const value_t*, const v
 template <bool V>
 GsKernel gs_kernel(int L)
 {
-    return L == 1 ? k_gs_color<1, V> : L == 4 ? k_gs_color<4, V> : L == 16 ? k_gs_color<16, V> : k_gs_color<64, V>;
+    return with_lanes(L, [](auto l) -> GsKernel { return k_gs_color<l.value, V>; });
 }
 
 int gs_run(bhs_handle* h, const GsIn& in, double* ms_out)
 {
     SideWs& ws = h->colWs;
-    BHS_TRY(side_prepare(h, ws, CO_INTS, 0, 0));
+    BHS_TRY(side_open(h, ws, CO_INTS, 0, 0));
+    BHS_TRY(side_start(h, ws));
     int* ctl = (int*)ws.ctl.p;
-    BHS_HIP(hipMemsetAsync(ctl, 0, sizeof(int) * CO_INTS, h->stream));
-    side_reset_stats(h);
-    BHS_TRY(side_begin(h, ws));
-    AgDims mean;
-    mean.n = in.d.n; mean.nnzS = in.d.nnzA; mean.seed = 0; mean.hasPrio = 0;
-    const int L = ag_lanes(mean);
+    const int L = side_lanes(in.d.n, in.d.nnzA);
     const GsKernel kern = (in.flags & BHS_GS_VERIFY) ? gs_kernel<true>(L) : gs_kernel<false>(L);
     const long long listed = in.ncolors > 0 ? in.colorPtr[in.ncolors] : 0;
     auto pass = [&](const char* name, bool backward) {
@@ -175,8 +153,7 @@ int gs_run(bhs_handle* h, const GsIn& in, double* ms_out)
     }
     BHS_TRY(side_end(h, ws));
     BHS_TRY(side_read_ctl(h, ws, CO_INTS));                           // the call's one round trip
-    BHS_TRY(side_elapsed(h, ws, ms_out));
-    BHS_TRY(side_collect(h, 0));
+    BHS_TRY(side_close(h, ws, ms_out));
     return ws.host[RD_ERR] ? (int)BHS_ERR_INVALID_ARG : (int)BHS_SUCCESS;
 }
 
@@ -190,22 +167,10 @@ int bhs_csr_color_device(bhs_handle* h, int n, int nnzS, const int* d_rowPtrS, c
 {
     if (!h || h->ps.open || n < 0 || nnzS < 0 || flags != 0) return BHS_ERR_INVALID_ARG;
     if ((n > 0 && (!d_rowPtrS || !d_color || !d_order || !d_colorPtr)) || (nnzS > 0 && !d_colIndS)) return BHS_ERR_INVALID_ARG;
-    const struct { const void* p; size_t bytes; } inputs[] = {
-        {d_rowPtrS, sizeof(int) * ((size_t)n + 1)}, {d_colIndS, sizeof(int) * (size_t)nnzS}, {d_prio, sizeof(unsigned) * (size_t)n}};
-    const struct { const void* p; size_t bytes; } outputs[] = {
-        {d_color, sizeof(int) * (size_t)n}, {d_order, sizeof(int) * (size_t)n}, {d_colorPtr, sizeof(int) * ((size_t)n + 1)}};
-    for (const auto& o : outputs)
-        for (const auto& x : inputs)
-            if (rd_overlap(o.p, o.bytes, x.p, x.bytes)) return BHS_ERR_INVALID_ARG;
-    for (int a = 0; a < 3; ++a)
-        for (int b = a + 1; b < 3; ++b)
-            if (rd_overlap(outputs[a].p, outputs[a].bytes, outputs[b].p, outputs[b].bytes)) return BHS_ERR_INVALID_ARG;
-    if (n == 0) {                                                     // nothing to colour, nothing launched
-        if (ncolors_out) *ncolors_out = 0;
-        if (rounds_out) *rounds_out = 0;
-        if (ms_out) *ms_out = 0.0;
-        return BHS_SUCCESS;
-    }
+    if (side_aliased({{d_color, sizeof(int) * (size_t)n}, {d_order, sizeof(int) * (size_t)n}, {d_colorPtr, sizeof(int) * ((size_t)n + 1)}},
+                     {{d_rowPtrS, sizeof(int) * ((size_t)n + 1)}, {d_colIndS, sizeof(int) * (size_t)nnzS}, {d_prio, sizeof(unsigned) * (size_t)n}}))
+        return BHS_ERR_INVALID_ARG;
+    if (n == 0) return side_nothing(ncolors_out, rounds_out, ms_out);  // nothing to colour, nothing launched
     CoIn in;
     in.d.n = n; in.d.nnzS = nnzS; in.d.seed = seed; in.d.hasPrio = d_prio ? 1 : 0;
     in.Sp = d_rowPtrS; in.Sj = d_colIndS; in.prio = d_prio; in.color = d_color; in.order = d_order; in.colorPtr = d_colorPtr;
@@ -229,11 +194,10 @@ int bhs_csr_gs_device(bhs_handle* h, int n, int nnzA, const int* d_rowPtrA, cons
     if (listed > 0 && (!d_rowPtrA || !d_diag || !d_order || !d_b || !d_x)) return BHS_ERR_INVALID_ARG;
     if (nnzA > 0 && (!d_colIndA || !d_valA)) return BHS_ERR_INVALID_ARG;
     const size_t vec = sizeof(value_t) * (size_t)n;
-    const struct { const void* p; size_t bytes; } inputs[] = {
-        {d_rowPtrA, sizeof(int) * ((size_t)n + 1)}, {d_colIndA, sizeof(int) * (size_t)nnzA}, {d_valA, sizeof(value_t) * (size_t)nnzA},
-        {d_diag, vec}, {d_order, sizeof(int) * (size_t)listed}, {d_color, sizeof(int) * (size_t)n}, {d_b, vec}};
-    for (const auto& x : inputs)
-        if (rd_overlap(d_x, vec, x.p, x.bytes)) return BHS_ERR_INVALID_ARG;   // (x is the one array written)
+    if (side_aliased({{d_x, vec}},                                    // (x is the one array written)
+                     {{d_rowPtrA, sizeof(int) * ((size_t)n + 1)}, {d_colIndA, sizeof(int) * (size_t)nnzA}, {d_valA, sizeof(value_t) * (size_t)nnzA},
+                      {d_diag, vec}, {d_order, sizeof(int) * (size_t)listed}, {d_color, sizeof(int) * (size_t)n}, {d_b, vec}}))
+        return BHS_ERR_INVALID_ARG;
     if (listed == 0 || sweeps == 0) {                                 // nothing to relax, nothing launched
         if (ms_out) *ms_out = 0.0;
         return BHS_SUCCESS;

@@ -132,8 +132,7 @@ int ex_numeric_run(bhs_handle* h, const ExIn& in, int nnzZ, const int* Zp, int* 
     BHS_TRY(ex_fill(h, in, nnzZ, Zp, Zj, Zx, perm));
     BHS_TRY(side_end(h, h->exWs));
     BHS_TRY(side_read_ctl(h, h->exWs, EX_INTS));
-    BHS_TRY(side_elapsed(h, h->exWs, ms_out));
-    BHS_TRY(side_collect(h, 0));
+    BHS_TRY(side_close(h, h->exWs, ms_out));
     if (h->exWs.host[EX_ERR]) return BHS_ERR_INVALID_ARG;
     long long reordered = 0;
     for (int s = 0; s < kExReordSlots; ++s) reordered += h->exWs.host[EX_REORD + s * kExReordStride];

@@ -1,6 +1,6 @@
 // bhs_host_forest.inc.h -- the minimum or maximum spanning forest of a matrix's graph (bhs_csr_spanning_forest_device; kernels
 // in bhs_forest.hip.h)
-// (A part of bhsparse_hip.hip's translation unit: included there directly after bhs_host_match.inc.h.)
+// (A part of bhsparse_hip.hip's translation unit, on the shared pieces of bhs_host_side.inc.h.)
 //
 // A workspace of its own (h->sfWs): the control block of bhs_forest.hip.h; in its queue buffer the trees' picks (bestW and
 // bestE, a 64-bit word a vertex each), the slot bitmap (a word per 64 vertices), the slots' weights, then the ints: parent,
@@ -8,8 +8,9 @@
 // word, scanned in place.  The labels are the caller's d_label itself.
 // A round is 5 launches and ceil(log2 R) pointer jumps from R roots, R known from the round before, and ONE round trip: the
 // error words and the trees the round hooked.  The loop ends after a round that hooked nothing, or that left one tree, and
-// with BHS_ERR_INTERNAL where a 33rd hooking round would be needed (trees with a crossing edge at least halve a round).  The
-// edge list adds three launches, the scan among them, and one round trip, whatever n.
+// with BHS_ERR_INTERNAL where a 33rd hooking round would be needed (trees with a crossing edge at least halve a round): a
+// verdict of its own, so the loop is here, not side_rounds.  The edge list adds three launches, the scan among them; the
+// call's close is one more round trip, whatever n.
 
 #include "bhs_forest.hip.h"
 
@@ -90,7 +91,7 @@ int sf_run(bhs_handle* h, const SfIn& in, int* nedges_out, int* rounds_out, doub
     const AgDims& d = in.d;
     SideWs& ws = h->sfWs;
     const size_t n = (size_t)d.n, nWords = (n + 63) / 64;
-    BHS_TRY(side_prepare(h, ws, SF_INTS, sizeof(rd_u64) * (2 * n + nWords) + sizeof(value_t) * n + sizeof(int) * (3 * n + nWords + 1),
+    BHS_TRY(side_open(h, ws, SF_INTS, sizeof(rd_u64) * (2 * n + nWords) + sizeof(value_t) * n + sizeof(int) * (3 * n + nWords + 1),
                          nWords + 1));
     int* ctl = (int*)ws.ctl.p;
     SfWork w;
@@ -102,19 +103,16 @@ int sf_run(bhs_handle* h, const SfIn& in, int* nedges_out, int* rounds_out, doub
     w.slotLo = w.parent + n;
     w.slotHi = w.slotLo + n;
     w.off = w.slotHi + n;
-    BHS_HIP(hipMemsetAsync(ctl, 0, sizeof(int) * SF_INTS, h->stream));
-    side_reset_stats(h);
-    BHS_TRY(side_begin(h, ws));
+    BHS_TRY(side_start(h, ws));
     const unsigned gridN = (unsigned)((n + 255) / 256);
     BHS_TRY(timed(h, "forest_pick", 0, [&] {
         hipLaunchKernelGGL(k_sf_init, dim3(gridN), dim3(256), 0, h->stream, d, in.Ap, in.label, w.parent, w.slotLo, ctl);
         return 1;
     }));
-    const int L = ag_lanes(d);
+    const int L = side_lanes(d.n, d.nnzS);
     long long hooks = 0;
     int rounds = 0;
-    BHS_TRY(L == 1 ? sf_rounds<1>(h, in, w, ctl, &hooks, &rounds) : L == 4 ? sf_rounds<4>(h, in, w, ctl, &hooks, &rounds)
-            : L == 16 ? sf_rounds<16>(h, in, w, ctl, &hooks, &rounds) : sf_rounds<64>(h, in, w, ctl, &hooks, &rounds));
+    BHS_TRY(with_lanes(L, [&](auto l) { return sf_rounds<l.value>(h, in, w, ctl, &hooks, &rounds); }));
     int* cnt = (int*)ws.cnt.p;
     BHS_TRY(timed(h, "forest_list", d.n, [&] {
         hipLaunchKernelGGL(k_sf_flag, dim3(gridN), dim3(256), 0, h->stream, d.n, (const int*)w.slotLo, w.map, cnt);
@@ -128,8 +126,7 @@ int sf_run(bhs_handle* h, const SfIn& in, int* nedges_out, int* rounds_out, doub
     }));
     BHS_TRY(side_end(h, ws));
     BHS_TRY(side_read_ctl(h, ws, SF_INTS));                           // the write-out's error word and the scan's total
-    BHS_TRY(side_elapsed(h, ws, ms_out));
-    BHS_TRY(side_collect(h, 0));
+    BHS_TRY(side_close(h, ws, ms_out));
     long long total = 0;
     memcpy(&total, ws.host + AG_TOTAL, sizeof(total));
     if (ws.host[RD_ERR] || ws.host[SF_BROKEN] || total != hooks) return BHS_ERR_INTERNAL;   // (the slots were this call's own)
@@ -148,23 +145,11 @@ int bhs_csr_spanning_forest_device(bhs_handle* h, int n, int nnzA, const int* d_
 {
     if (!h || h->ps.open || n < 0 || nnzA < 0 || (flags & ~(BHS_FOREST_MAXIMUM | BHS_FOREST_ABS))) return BHS_ERR_INVALID_ARG;
     if ((n > 0 && (!d_rowPtrA || !d_label || !d_edgeLo || !d_edgeHi)) || (nnzA > 0 && !d_colIndA)) return BHS_ERR_INVALID_ARG;
-    const struct { const void* p; size_t bytes; } inputs[] = {
-        {d_rowPtrA, sizeof(int) * ((size_t)n + 1)}, {d_colIndA, sizeof(int) * (size_t)nnzA}, {d_valA, sizeof(value_t) * (size_t)nnzA}};
-    const struct { const void* p; size_t bytes; } outputs[] = {
-        {d_label, sizeof(int) * (size_t)n}, {d_edgeLo, sizeof(int) * (size_t)n}, {d_edgeHi, sizeof(int) * (size_t)n},
-        {d_edgeVal, sizeof(value_t) * (size_t)n}};
-    for (const auto& o : outputs)
-        for (const auto& x : inputs)
-            if (rd_overlap(o.p, o.bytes, x.p, x.bytes)) return BHS_ERR_INVALID_ARG;
-    for (int a = 0; a < 4; ++a)
-        for (int b = a + 1; b < 4; ++b)
-            if (rd_overlap(outputs[a].p, outputs[a].bytes, outputs[b].p, outputs[b].bytes)) return BHS_ERR_INVALID_ARG;
-    if (n == 0) {                                                     // no vertex, no edge, nothing launched
-        if (nedges_out) *nedges_out = 0;
-        if (rounds_out) *rounds_out = 0;
-        if (ms_out) *ms_out = 0.0;
-        return BHS_SUCCESS;
-    }
+    if (side_aliased({{d_label, sizeof(int) * (size_t)n}, {d_edgeLo, sizeof(int) * (size_t)n}, {d_edgeHi, sizeof(int) * (size_t)n},
+                      {d_edgeVal, sizeof(value_t) * (size_t)n}},
+                     {{d_rowPtrA, sizeof(int) * ((size_t)n + 1)}, {d_colIndA, sizeof(int) * (size_t)nnzA}, {d_valA, sizeof(value_t) * (size_t)nnzA}}))
+        return BHS_ERR_INVALID_ARG;
+    if (n == 0) return side_nothing(nedges_out, rounds_out, ms_out);   // no vertex, no edge, nothing launched
     SfIn in;
     in.d.n = n; in.d.nnzS = nnzA; in.d.seed = (unsigned)flags; in.d.hasPrio = d_valA ? 1 : 0;
     in.Ap = d_rowPtrA; in.Aj = d_colIndA; in.Ax = (const value_t*)d_valA; in.label = d_label;

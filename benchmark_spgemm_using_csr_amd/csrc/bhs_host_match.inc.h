@@ -1,13 +1,14 @@
 // bhs_host_match.inc.h -- heavy-edge matching of a matrix's vertices (bhs_csr_match_device; kernels in bhs_match.hip.h)
-// (A part of bhsparse_hip.hip's translation unit: included there directly after bhs_host_components.inc.h.)
+// (A part of bhsparse_hip.hip's translation unit, on the shared pieces of bhs_host_side.inc.h.)
 //
 // A workspace of its own (h->mtWs): the control block of bhs_match.hip.h; in its queue buffer the leader bitmap (a word per 64
 // vertices) and the scanned offsets behind it, where the aggregates are numbered, and the rounds' candidates (an int a
 // vertex); in its count buffer the leaders per bitmap word, scanned in place.  The mates are the caller's d_mate itself.
 // A round is two launches and ONE round trip, for the error word, the pairs the round made and the vertices it left
 // undecided; the loop ends after a round that matched nothing (the vertices it left become unmatched: k_mt_finish) or left
-// nobody, and with BHS_ERR_INTERNAL when more than n / 2 + 1 rounds would be needed.  The numbering adds three launches, the
-// scan among them, and one round trip, whatever n.
+// nobody, and with BHS_ERR_INTERNAL when more than n / 2 + 1 rounds would be needed (a verdict of its own: the loop is here,
+// not side_rounds).  The numbering adds three launches, the scan among them; the call's close is one more round trip,
+// whatever n.
 
 #include "bhs_match.hip.h"
 
@@ -67,24 +68,21 @@ int mt_run(bhs_handle* h, const MtIn& in, int* npairs_out, int* rounds_out, doub
     SideWs& ws = h->mtWs;
     const size_t n = (size_t)d.n, nWords = (n + 63) / 64;
     const bool number = in.agg != nullptr;
-    BHS_TRY(side_prepare(h, ws, MT_INTS, sizeof(rd_u64) * nWords + sizeof(int) * (nWords + 1 + n), number ? nWords + 1 : 0));
+    BHS_TRY(side_open(h, ws, MT_INTS, sizeof(rd_u64) * nWords + sizeof(int) * (nWords + 1 + n), number ? nWords + 1 : 0));
     int* ctl = (int*)ws.ctl.p;
     rd_u64* map = (rd_u64*)ws.queue.p;
     int* off = (int*)(map + nWords);
     int* cand = off + nWords + 1;
-    BHS_HIP(hipMemsetAsync(ctl, 0, sizeof(int) * MT_INTS, h->stream));
-    side_reset_stats(h);
-    BHS_TRY(side_begin(h, ws));
+    BHS_TRY(side_start(h, ws));
     const unsigned gridN = (unsigned)((n + 255) / 256);
     BHS_TRY(timed(h, "match_init", d.n, [&] {
         hipLaunchKernelGGL(k_mt_init, dim3(gridN), dim3(256), 0, h->stream, d, in.Ap, in.mate, ctl);
         return 1;
     }));
-    const int L = ag_lanes(d);
+    const int L = side_lanes(d.n, d.nnzS);
     long long npairs = 0;
     int rounds = 0;
-    BHS_TRY(L == 1 ? mt_rounds<1>(h, in, cand, ctl, &npairs, &rounds) : L == 4 ? mt_rounds<4>(h, in, cand, ctl, &npairs, &rounds)
-            : L == 16 ? mt_rounds<16>(h, in, cand, ctl, &npairs, &rounds) : mt_rounds<64>(h, in, cand, ctl, &npairs, &rounds));
+    BHS_TRY(with_lanes(L, [&](auto l) { return mt_rounds<l.value>(h, in, cand, ctl, &npairs, &rounds); }));
     if (2 * npairs > (long long)d.n) return BHS_ERR_INTERNAL;
     if (number) {
         int* cnt = (int*)ws.cnt.p;
@@ -101,8 +99,7 @@ int mt_run(bhs_handle* h, const MtIn& in, int* npairs_out, int* rounds_out, doub
     }
     BHS_TRY(side_end(h, ws));
     BHS_TRY(side_read_ctl(h, ws, MT_INTS));                           // the numbering's error word and total (the span's end in any case)
-    BHS_TRY(side_elapsed(h, ws, ms_out));
-    BHS_TRY(side_collect(h, 0));
+    BHS_TRY(side_close(h, ws, ms_out));
     if (number) {
         long long total = 0;
         memcpy(&total, ws.host + AG_TOTAL, sizeof(total));
@@ -122,18 +119,11 @@ int bhs_csr_match_device(bhs_handle* h, int n, int nnzA, const int* d_rowPtrA, c
 {
     if (!h || h->ps.open || n < 0 || nnzA < 0 || flags != 0) return BHS_ERR_INVALID_ARG;
     if ((n > 0 && (!d_rowPtrA || !d_mate)) || (nnzA > 0 && !d_colIndA)) return BHS_ERR_INVALID_ARG;
-    const struct { const void* p; size_t bytes; } inputs[] = {
-        {d_rowPtrA, sizeof(int) * ((size_t)n + 1)}, {d_colIndA, sizeof(int) * (size_t)nnzA}, {d_valA, sizeof(value_t) * (size_t)nnzA}};
     const size_t outBytes = sizeof(int) * (size_t)n;
-    for (const auto& x : inputs)
-        if (rd_overlap(d_mate, outBytes, x.p, x.bytes) || rd_overlap(d_agg, outBytes, x.p, x.bytes)) return BHS_ERR_INVALID_ARG;
-    if (rd_overlap(d_mate, outBytes, d_agg, outBytes)) return BHS_ERR_INVALID_ARG;
-    if (n == 0) {                                                     // no vertex, no pair, nothing launched
-        if (npairs_out) *npairs_out = 0;
-        if (rounds_out) *rounds_out = 0;
-        if (ms_out) *ms_out = 0.0;
-        return BHS_SUCCESS;
-    }
+    if (side_aliased({{d_mate, outBytes}, {d_agg, outBytes}},
+                     {{d_rowPtrA, sizeof(int) * ((size_t)n + 1)}, {d_colIndA, sizeof(int) * (size_t)nnzA}, {d_valA, sizeof(value_t) * (size_t)nnzA}}))
+        return BHS_ERR_INVALID_ARG;
+    if (n == 0) return side_nothing(npairs_out, rounds_out, ms_out);   // no vertex, no pair, nothing launched
     MtIn in;
     in.d.n = n; in.d.nnzS = nnzA; in.d.seed = seed; in.d.hasPrio = d_valA ? 1 : 0;
     in.Ap = d_rowPtrA; in.Aj = d_colIndA; in.Ax = (const value_t*)d_valA; in.mate = d_mate; in.agg = d_agg;

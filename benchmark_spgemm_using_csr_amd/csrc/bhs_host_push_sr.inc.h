@@ -33,17 +33,15 @@ int pu_run(bhs_handle* h, const PuIn& in, int* next_count_out, long long* change
     const size_t rowBytes = in.next ? sizeof(rd_u64) * nWords : 0;
     const size_t bitBytes = changed_out ? sizeof(unsigned) * (((size_t)d.n * (size_t)d.k + 31) / 32) : 0;
     const size_t scanned = std::max<size_t>((size_t)d.nf, in.next ? nWords : 0) + 1;
-    BHS_TRY(side_prepare(h, ws, PU_INTS, rowBytes + bitBytes, scanned));
+    BHS_TRY(side_open(h, ws, PU_INTS, rowBytes + bitBytes, scanned));
     BHS_TRY(ensure(h, h->pushOff, sizeof(int) * scanned));
     int* ctl = (int*)ws.ctl.p;
     int* cnt = (int*)ws.cnt.p;
     int* off = (int*)h->pushOff.p;
     rd_u64* rows = (rd_u64*)ws.queue.p;
     unsigned* bits = (unsigned*)((char*)ws.queue.p + rowBytes);
-    BHS_HIP(hipMemsetAsync(ctl, 0, sizeof(int) * PU_INTS, h->stream));
     if (rowBytes + bitBytes) BHS_HIP(hipMemsetAsync(ws.queue.p, 0, rowBytes + bitBytes, h->stream));
-    side_reset_stats(h);
-    BHS_TRY(side_begin(h, ws));
+    BHS_TRY(side_start(h, ws));
     if (d.nf > 0) {
         BHS_TRY(timed(h, "push_degrees", d.nf, [&] {
             hipLaunchKernelGGL(k_push_degrees, dim3((unsigned)(((long long)d.nf + 255) / 256)), dim3(256), 0, h->stream, d, in.fidx,
@@ -80,8 +78,7 @@ int pu_run(bhs_handle* h, const PuIn& in, int* next_count_out, long long* change
     }
     BHS_TRY(side_end(h, ws));
     BHS_TRY(side_read_ctl(h, ws, PU_INTS));                           // the error word and the two counts, one round trip
-    BHS_TRY(side_elapsed(h, ws, ms_out));
-    BHS_TRY(side_collect(h, 0));
+    BHS_TRY(side_close(h, ws, ms_out));
     if (ws.host[RD_ERR]) return BHS_ERR_INVALID_ARG;
     if (changed_out) memcpy(changed_out, ws.host + PU_CHANGED, sizeof(long long));
     if (next_count_out) {
@@ -111,13 +108,11 @@ int bhs_csr_push_semiring_device(bhs_handle* h, int semiring, int m, int n, int 
     if (!smv_rule(semiring, in.kind, in.d.mult, id) || semiring == BHS_SR_PLUS_TIMES) return BHS_ERR_INVALID_ARG;   // (a scattered sum has no fixed order)
     if (flags & ~BHS_MV_MASK_COMPLEMENT) return BHS_ERR_INVALID_ARG;
     if (d_M ? ldM < k : (flags & BHS_MV_MASK_COMPLEMENT) != 0) return BHS_ERR_INVALID_ARG;
-    const struct { const void* p; size_t bytes; } inputs[] = {
-        {d_rowPtrG, sizeof(int) * ((size_t)m + 1)}, {d_colIndG, sizeof(int) * (size_t)nnzG}, {d_valG, sizeof(value_t) * (size_t)nnzG},
-        {d_fidx, sizeof(int) * (size_t)nf}, {d_F, mv_bytes(nf, k, ldF)}, {d_M, d_M ? mv_bytes(n, k, ldM) : 0}};
     const size_t yBytes = mv_bytes(n, k, ldY), nextBytes = d_next ? sizeof(int) * (size_t)n : 0;
-    for (const auto& x : inputs)
-        if (rd_overlap(d_Y, yBytes, x.p, x.bytes) || rd_overlap(d_next, nextBytes, x.p, x.bytes)) return BHS_ERR_INVALID_ARG;
-    if (rd_overlap(d_Y, yBytes, d_next, nextBytes)) return BHS_ERR_INVALID_ARG;
+    if (side_aliased({{d_Y, yBytes}, {d_next, nextBytes}},
+                     {{d_rowPtrG, sizeof(int) * ((size_t)m + 1)}, {d_colIndG, sizeof(int) * (size_t)nnzG}, {d_valG, sizeof(value_t) * (size_t)nnzG},
+                      {d_fidx, sizeof(int) * (size_t)nf}, {d_F, mv_bytes(nf, k, ldF)}, {d_M, d_M ? mv_bytes(n, k, ldM) : 0}}))
+        return BHS_ERR_INVALID_ARG;
     int T = 1;
     while (T < k && T < 64) T *= 2;
     in.d.m = m; in.d.n = n; in.d.nnzG = nnzG; in.d.nf = nf; in.d.k = k; in.d.ldF = ldF; in.d.ldM = d_M ? ldM : 0; in.d.ldY = ldY;

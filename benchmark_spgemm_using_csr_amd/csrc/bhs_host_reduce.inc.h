@@ -122,8 +122,7 @@ int rd_run(bhs_handle* h, const RdIn& in, int axis, int op, int filt, value_t* o
     }));
     BHS_TRY(side_end(h, h->rdWs));
     BHS_TRY(side_read_ctl(h, h->rdWs, RD_INTS));
-    BHS_TRY(side_elapsed(h, h->rdWs, ms_out));
-    BHS_TRY(side_collect(h, 0));
+    BHS_TRY(side_close(h, h->rdWs, ms_out));
     return h->rdWs.host[RD_ERR] ? (int)BHS_ERR_INVALID_ARG : (int)BHS_SUCCESS;
 }
 
@@ -168,8 +167,7 @@ int sc_run(bhs_handle* h, const ScArgs& s, double* ms_out)
     }
     BHS_TRY(side_end(h, h->rdWs));
     BHS_TRY(side_read_ctl(h, h->rdWs, RD_INTS));
-    BHS_TRY(side_elapsed(h, h->rdWs, ms_out));
-    BHS_TRY(side_collect(h, 0));
+    BHS_TRY(side_close(h, h->rdWs, ms_out));
     return h->rdWs.host[RD_ERR] ? (int)BHS_ERR_INVALID_ARG : (int)BHS_SUCCESS;
 }
 
@@ -190,10 +188,9 @@ int bhs_csr_reduce_device(bhs_handle* h, int m, int n, int nnzX, const bhs_value
                       : axis == BHS_AXIS_DIAG ? (size_t)std::min(m, n) : 1;
     if (nOut && !d_out) return BHS_ERR_INVALID_ARG;
     const size_t outBytes = sizeof(value_t) * nOut;
-    if (rd_overlap(d_out, outBytes, d_rowPtrX, sizeof(int) * ((size_t)m + 1)) ||
-        rd_overlap(d_out, outBytes, d_colIndX, sizeof(int) * (size_t)nnzX) ||
-        rd_overlap(d_out, outBytes, d_valX, sizeof(value_t) * (size_t)nnzX))
-        return BHS_ERR_INVALID_ARG;                                  // (the output must not overlap an input)
+    if (side_aliased({{d_out, outBytes}}, {{d_rowPtrX, sizeof(int) * ((size_t)m + 1)}, {d_colIndX, sizeof(int) * (size_t)nnzX},
+                                           {d_valX, sizeof(value_t) * (size_t)nnzX}}))
+        return BHS_ERR_INVALID_ARG;
     RdIn in;
     in.m = m; in.n = n; in.nnzX = nnzX; in.Xp = d_rowPtrX; in.Xj = d_colIndX; in.Xx = (const value_t*)d_valX;
     if (op == BHS_RED_COUNT) { in.Xx = nullptr; op = BHS_RED_PLUS; } // (a sum of ones: no value is read)
@@ -213,12 +210,10 @@ int bhs_csr_scale_device(bhs_handle* h, int m, int n, int nnzX, const bhs_value_
     if (((flags & BHS_SCALE_LEFT_DIV) && !d_left) || ((flags & BHS_SCALE_RIGHT_DIV) && !d_right)) return BHS_ERR_INVALID_ARG;
     if (nnzX > 0 && (!d_valX || !d_valZ || (d_right && !d_colIndX))) return BHS_ERR_INVALID_ARG;
     const size_t zBytes = sizeof(value_t) * (size_t)nnzX;
-    if (rd_overlap(d_valZ, zBytes, d_rowPtrX, sizeof(int) * ((size_t)m + 1)) ||
-        rd_overlap(d_valZ, zBytes, d_colIndX, sizeof(int) * (size_t)nnzX) ||
-        rd_overlap(d_valZ, zBytes, d_left, sizeof(value_t) * (size_t)m) ||
-        rd_overlap(d_valZ, zBytes, d_right, sizeof(value_t) * (size_t)n) ||
-        ((const void*)d_valZ != (const void*)d_valX && rd_overlap(d_valZ, zBytes, d_valX, zBytes)))
-        return BHS_ERR_INVALID_ARG;                                  // (in place on valX exactly, or apart from every input)
+    const void* valX = (const void*)d_valZ == (const void*)d_valX ? nullptr : d_valX;   // (in place on valX exactly, or apart from every input)
+    if (side_aliased({{d_valZ, zBytes}}, {{d_rowPtrX, sizeof(int) * ((size_t)m + 1)}, {d_colIndX, sizeof(int) * (size_t)nnzX},
+                                          {d_left, sizeof(value_t) * (size_t)m}, {d_right, sizeof(value_t) * (size_t)n}, {valX, zBytes}}))
+        return BHS_ERR_INVALID_ARG;
     ScArgs s;
     s.m = m; s.n = n; s.nnzX = nnzX; s.Xp = d_rowPtrX; s.Xj = d_colIndX; s.Xx = (const value_t*)d_valX;
     s.left = (const value_t*)d_left; s.right = (const value_t*)d_right; s.alpha = alpha;

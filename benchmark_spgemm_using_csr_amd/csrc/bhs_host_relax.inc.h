@@ -29,10 +29,8 @@ int rx_run(bhs_handle* h, const RxIn& in, double* ms_out)
     const int n = in.n;
     const size_t qBytes = rx_pad(sizeof(int) * 2 * (size_t)std::max(n, 1));
     const size_t vBytes = rx_pad(sizeof(value_t) * (size_t)std::max(n, 1));
-    BHS_TRY(side_prepare(h, ws, RD_INTS, qBytes + 3 * vBytes, 0));
-    BHS_HIP(hipMemsetAsync(ws.ctl.p, 0, sizeof(int) * RD_INTS, h->stream));
-    side_reset_stats(h);
-    BHS_TRY(side_begin(h, ws));
+    BHS_TRY(side_open(h, ws, RD_INTS, qBytes + 3 * vBytes, 0));
+    BHS_TRY(side_start(h, ws));
     int* ctl = (int*)ws.ctl.p;
     int* queue = (int*)ws.queue.p;
     value_t* pool[2] = {(value_t*)((char*)ws.queue.p + qBytes), (value_t*)((char*)ws.queue.p + qBytes + vBytes)};
@@ -95,8 +93,7 @@ int rx_run(bhs_handle* h, const RxIn& in, double* ms_out)
     }
     BHS_TRY(side_end(h, ws));
     BHS_TRY(side_read_ctl(h, ws, RD_INTS));
-    BHS_TRY(side_elapsed(h, ws, ms_out));
-    BHS_TRY(side_collect(h, 0));
+    BHS_TRY(side_close(h, ws, ms_out));
     return ws.host[RD_ERR] ? (int)BHS_ERR_INVALID_ARG : (int)BHS_SUCCESS;
 }
 
@@ -110,10 +107,8 @@ int dots_run(bhs_handle* h, const MvIn& in, const value_t* yIn, const value_t* w
     SideWs& ws = h->dotWs;
     const int nPart = (int)std::max<long long>(1, ((long long)d.m + kDotPer - 1) / kDotPer);
     const size_t qBytes = rx_pad(sizeof(int) * 2 * (size_t)std::max(d.m, 1));
-    BHS_TRY(side_prepare(h, ws, DOT_INTS, qBytes + sizeof(double) * 2 * (size_t)nPart, 0));
-    BHS_HIP(hipMemsetAsync(ws.ctl.p, 0, sizeof(int) * DOT_INTS, h->stream));
-    side_reset_stats(h);
-    BHS_TRY(side_begin(h, ws));
+    BHS_TRY(side_open(h, ws, DOT_INTS, qBytes + sizeof(double) * 2 * (size_t)nPart, 0));
+    BHS_TRY(side_start(h, ws));
     int* ctl = (int*)ws.ctl.p;
     int* queue = (int*)ws.queue.p;
     double* part = (double*)((char*)ws.queue.p + qBytes);
@@ -153,8 +148,7 @@ int dots_run(bhs_handle* h, const MvIn& in, const value_t* yIn, const value_t* w
     }));
     BHS_TRY(side_end(h, ws));
     BHS_TRY(side_read_ctl(h, ws, DOT_INTS));
-    BHS_TRY(side_elapsed(h, ws, ms_out));
-    BHS_TRY(side_collect(h, 0));
+    BHS_TRY(side_close(h, ws, ms_out));
     if (ws.host[RD_ERR]) return BHS_ERR_INVALID_ARG;
     double out[2];
     memcpy(out, ws.host + DOT_OUT, sizeof(out));
@@ -197,14 +191,10 @@ int bhs_csr_relax_device(bhs_handle* h, int n, int nnzA, const bhs_value_t* d_va
     }
     if (needD && n > 0 && !d_d) return BHS_ERR_INVALID_ARG;
     const size_t vBytes = sizeof(value_t) * (size_t)n;
-    for (const void* out : {(const void*)d_x, (const void*)d_d}) {
-        if (rd_overlap(out, vBytes, d_rowPtrA, sizeof(int) * ((size_t)n + 1)) ||
-            rd_overlap(out, vBytes, d_colIndA, sizeof(int) * (size_t)nnzA) ||
-            rd_overlap(out, vBytes, d_valA, sizeof(value_t) * (size_t)nnzA) ||
-            rd_overlap(out, vBytes, d_diag, vBytes) || rd_overlap(out, vBytes, d_b, vBytes))
-            return BHS_ERR_INVALID_ARG;                              // (an output must not overlap an input)
-    }
-    if (rd_overlap(d_x, vBytes, d_d, vBytes)) return BHS_ERR_INVALID_ARG;
+    if (side_aliased({{d_x, vBytes}, {d_d, vBytes}},
+                     {{d_rowPtrA, sizeof(int) * ((size_t)n + 1)}, {d_colIndA, sizeof(int) * (size_t)nnzA}, {d_valA, sizeof(value_t) * (size_t)nnzA},
+                      {d_diag, vBytes}, {d_b, vBytes}}))
+        return BHS_ERR_INVALID_ARG;
     RxIn in;
     in.n = n; in.nnzA = nnzA; in.steps = steps; in.Ap = d_rowPtrA; in.Aj = d_colIndA; in.Ax = (const value_t*)d_valA;
     in.diag = (const value_t*)d_diag; in.b = (const value_t*)d_b; in.x = (value_t*)d_x; in.d = (value_t*)d_d; in.coef = coef;
@@ -220,12 +210,11 @@ int bhs_csr_spmv_dots_device(bhs_handle* h, int m, int n, int nnzA, const bhs_va
     if (nnzA > 0 && (!d_colIndA || !d_x)) return BHS_ERR_INVALID_ARG;
     if (m > 0 && (!d_z || (beta != 0.0 && !d_y))) return BHS_ERR_INVALID_ARG;
     const size_t zBytes = sizeof(value_t) * (size_t)m;
-    if (rd_overlap(d_z, zBytes, d_rowPtrA, sizeof(int) * ((size_t)m + 1)) ||
-        rd_overlap(d_z, zBytes, d_colIndA, sizeof(int) * (size_t)nnzA) ||
-        rd_overlap(d_z, zBytes, d_valA, sizeof(value_t) * (size_t)nnzA) ||
-        rd_overlap(d_z, zBytes, d_x, sizeof(value_t) * (size_t)n) || rd_overlap(d_z, zBytes, d_w, zBytes) ||
-        ((const void*)d_y != (const void*)d_z && rd_overlap(d_z, zBytes, d_y, zBytes)))
-        return BHS_ERR_INVALID_ARG;                                  // (z overlaps no input, except that it may be y itself)
+    const void* y = (const void*)d_y == (const void*)d_z ? nullptr : d_y;   // (z == y exactly: in place)
+    if (side_aliased({{d_z, zBytes}},                                // (z is the one array written)
+                     {{d_rowPtrA, sizeof(int) * ((size_t)m + 1)}, {d_colIndA, sizeof(int) * (size_t)nnzA}, {d_valA, sizeof(value_t) * (size_t)nnzA},
+                      {d_x, sizeof(value_t) * (size_t)n}, {d_w, zBytes}, {y, zBytes}}))
+        return BHS_ERR_INVALID_ARG;
     MvIn in;
     in.d.m = m; in.d.n = n; in.d.nnzA = nnzA; in.d.k = 1; in.d.ldX = 1; in.d.ldY = 1; in.d.alpha = alpha; in.d.beta = beta;
     in.Ap = d_rowPtrA; in.Aj = d_colIndA; in.Ax = (const value_t*)d_valA; in.X = (const value_t*)d_x; in.Y = (value_t*)d_z;

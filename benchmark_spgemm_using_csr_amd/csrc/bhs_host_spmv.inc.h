@@ -43,10 +43,8 @@ int mv_run(bhs_handle* h, const MvIn& in, double* ms_out)
 {
     const MvDims& d = in.d;
     SideWs& ws = h->mvWs;
-    BHS_TRY(side_prepare(h, ws, RD_INTS, sizeof(int) * 2 * (size_t)std::max(d.m, 1), 0));
-    BHS_HIP(hipMemsetAsync(ws.ctl.p, 0, sizeof(int) * RD_INTS, h->stream));
-    side_reset_stats(h);
-    BHS_TRY(side_begin(h, ws));
+    BHS_TRY(side_open(h, ws, RD_INTS, sizeof(int) * 2 * (size_t)std::max(d.m, 1), 0));
+    BHS_TRY(side_start(h, ws));
     int* ctl = (int*)ws.ctl.p;
     int* queue = (int*)ws.queue.p;
     const MvKernels kern = mv_kernels(d.k);
@@ -76,8 +74,7 @@ int mv_run(bhs_handle* h, const MvIn& in, double* ms_out)
     }
     BHS_TRY(side_end(h, ws));
     BHS_TRY(side_read_ctl(h, ws, RD_INTS));
-    BHS_TRY(side_elapsed(h, ws, ms_out));
-    BHS_TRY(side_collect(h, 0));
+    BHS_TRY(side_close(h, ws, ms_out));
     return ws.host[RD_ERR] ? (int)BHS_ERR_INVALID_ARG : (int)BHS_SUCCESS;
 }
 
@@ -95,11 +92,9 @@ int mv_call(bhs_handle* h, int m, int n, int nnzA, const bhs_value_t* d_valA, co
     if (nnzA > 0 && (!d_colIndA || !d_X)) return BHS_ERR_INVALID_ARG;
     if (m > 0 && !d_Y) return BHS_ERR_INVALID_ARG;
     const size_t yBytes = mv_bytes(m, k, ldY);
-    if (rd_overlap(d_Y, yBytes, d_rowPtrA, sizeof(int) * ((size_t)m + 1)) ||
-        rd_overlap(d_Y, yBytes, d_colIndA, sizeof(int) * (size_t)nnzA) ||
-        rd_overlap(d_Y, yBytes, d_valA, sizeof(value_t) * (size_t)nnzA) ||
-        rd_overlap(d_Y, yBytes, d_X, mv_bytes(n, k, ldX)))
-        return BHS_ERR_INVALID_ARG;                                  // (the output must not overlap an input)
+    if (side_aliased({{d_Y, yBytes}}, {{d_rowPtrA, sizeof(int) * ((size_t)m + 1)}, {d_colIndA, sizeof(int) * (size_t)nnzA},
+                                       {d_valA, sizeof(value_t) * (size_t)nnzA}, {d_X, mv_bytes(n, k, ldX)}}))
+        return BHS_ERR_INVALID_ARG;
     MvIn in;
     in.d.m = m; in.d.n = n; in.d.nnzA = nnzA; in.d.k = k; in.d.ldX = ldX; in.d.ldY = ldY; in.d.alpha = alpha; in.d.beta = beta;
     in.Ap = d_rowPtrA; in.Aj = d_colIndA; in.Ax = (const value_t*)d_valA; in.X = (const value_t*)d_X; in.Y = (value_t*)d_Y;

@@ -65,10 +65,8 @@ int smv_run(bhs_handle* h, const SmvIn& in, long long* changed_out, double* ms_o
 {
     const SmvDims& d = in.d;
     SideWs& ws = h->srmvWs;
-    BHS_TRY(side_prepare(h, ws, SMV_INTS, sizeof(int) * 2 * (size_t)std::max(d.m, 1), 0));
-    BHS_HIP(hipMemsetAsync(ws.ctl.p, 0, sizeof(int) * SMV_INTS, h->stream));
-    side_reset_stats(h);
-    BHS_TRY(side_begin(h, ws));
+    BHS_TRY(side_open(h, ws, SMV_INTS, sizeof(int) * 2 * (size_t)std::max(d.m, 1), 0));
+    BHS_TRY(side_start(h, ws));
     int* ctl = (int*)ws.ctl.p;
     int* queue = (int*)ws.queue.p;
     const SmvKernels kern = smv_kernels(in.kind, d.k);
@@ -97,8 +95,7 @@ int smv_run(bhs_handle* h, const SmvIn& in, long long* changed_out, double* ms_o
     }
     BHS_TRY(side_end(h, ws));
     BHS_TRY(side_read_ctl(h, ws, SMV_INTS));                          // the error word and the count, one round trip
-    BHS_TRY(side_elapsed(h, ws, ms_out));
-    BHS_TRY(side_collect(h, 0));
+    BHS_TRY(side_close(h, ws, ms_out));
     if (ws.host[RD_ERR]) return BHS_ERR_INVALID_ARG;
     if (changed_out) memcpy(changed_out, ws.host + SMV_CHANGED, sizeof(long long));
     return BHS_SUCCESS;
@@ -117,12 +114,10 @@ int smv_call(bhs_handle* h, int semiring, int m, int n, int nnzA, const bhs_valu
     if (flags & ~(BHS_MV_ACCUM | BHS_MV_MASK_COMPLEMENT)) return BHS_ERR_INVALID_ARG;
     if (d_M ? ldM < k : (flags & BHS_MV_MASK_COMPLEMENT) != 0) return BHS_ERR_INVALID_ARG;
     const size_t yBytes = mv_bytes(m, k, ldY);
-    if (rd_overlap(d_Y, yBytes, d_rowPtrA, sizeof(int) * ((size_t)m + 1)) ||
-        rd_overlap(d_Y, yBytes, d_colIndA, sizeof(int) * (size_t)nnzA) ||
-        rd_overlap(d_Y, yBytes, d_valA, sizeof(value_t) * (size_t)nnzA) ||
-        rd_overlap(d_Y, yBytes, d_X, mv_bytes(n, k, ldX)) ||
-        rd_overlap(d_Y, yBytes, d_M, d_M ? mv_bytes(m, k, ldM) : 0))
-        return BHS_ERR_INVALID_ARG;                                  // (the output must not overlap an input; M may overlap X)
+    if (side_aliased({{d_Y, yBytes}}, {{d_rowPtrA, sizeof(int) * ((size_t)m + 1)}, {d_colIndA, sizeof(int) * (size_t)nnzA},
+                                       {d_valA, sizeof(value_t) * (size_t)nnzA}, {d_X, mv_bytes(n, k, ldX)},
+                                       {d_M, d_M ? mv_bytes(m, k, ldM) : 0}}))
+        return BHS_ERR_INVALID_ARG;                                  // (M may overlap X: both are inputs)
     in.d.m = m; in.d.n = n; in.d.nnzA = nnzA; in.d.k = k; in.d.ldX = ldX; in.d.ldM = d_M ? ldM : 0; in.d.ldY = ldY;
     in.d.flags = flags | (changed_out ? kSmvCount : 0);              // (no count where nobody reads it)
     in.Ap = d_rowPtrA; in.Aj = d_colIndA; in.Ax = (const value_t*)d_valA; in.X = (const value_t*)d_X;

@@ -1,13 +1,14 @@
 // bhs_host_trsv.inc.h -- the level sets of a triangle, the sparse triangular solve and ILU(0) on them (bhs_csr_levels_device,
 // bhs_csr_trsv_device, bhs_csr_ilu0_device; kernels in bhs_trsv.hip.h and bhs_ilu0.hip.h)
-// (A part of bhsparse_hip.hip's translation unit: included there directly after bhs_host_color.inc.h.)
+// (A part of bhsparse_hip.hip's translation unit, on the shared pieces of bhs_host_side.inc.h; included there after
+// bhs_host_color.inc.h for its co_order.)
 //
 // A workspace of its own (h->trsvWs), shared by the three calls: the control block of bhs_trsv.hip.h and, in its count
 // buffer, the table of rows per (level, 64 rows) of the order, which is the colouring's (co_order, bhs_host_color.inc.h).
 // The analysis: kLvBatch passes of the relaxation a control round trip, for the error word, the rows the batch's last pass
-// raised and the levels in use; the loop ends after a batch whose last pass raised nothing, and with BHS_ERR_INTERNAL when
-// more than n + 1 passes would be needed.  The solve and the factorisation: a launch per non-empty level, ONE round trip at
-// the end of the call.
+// raised and the levels in use (side_passes: the loop ends after a batch whose last pass raised nothing, and with
+// BHS_ERR_INTERNAL when more than n + 1 passes would be needed), then the order and the call's close, one more round trip.
+// The solve and the factorisation: a launch per non-empty level, ONE round trip at the end of the call.
 
 #include "bhs_trsv.hip.h"
 #include "bhs_ilu0.hip.h"
@@ -27,50 +28,34 @@ template <int L>
 int lv_passes(bhs_handle* h, const LvIn& in, int* ctl, int* passes_out)
 {
     const AgDims& d = in.d;
-    SideWs& ws = h->trsvWs;
     const unsigned rows = (unsigned)(((long long)d.n + 256 / L - 1) / (256 / L));
     const unsigned grid = std::min<unsigned>(rows, (unsigned)h->numCU * 16);   // (a block loop: one add to the count a workgroup)
-    long long passes = 0;
-    for (;;) {
-        if (passes > (long long)d.n) return BHS_ERR_INTERNAL;         // (n levels at the most: n passes raise, one more finds nothing)
-        for (int p = 0; p < kLvBatch; ++p) {
-            if (p == kLvBatch - 1) BHS_HIP(hipMemsetAsync(ctl + AG_UNDEC, 0, sizeof(rd_u64), h->stream));   // the last pass's count alone
-            BHS_TRY(timed(h, "levels_pass", d.n, [&] {
-                hipLaunchKernelGGL(k_lev_pass<L>, dim3(grid), dim3(256), 0, h->stream, d, in.upper, in.Ap, in.Aj, in.level, ctl);
-                return 1;
-            }));
-        }
-        passes += kLvBatch;
-        BHS_TRY(side_read_ctl(h, ws, TS_INTS));                       // the error word, the count, the levels: the batch's one round trip
-        if (ws.host[RD_ERR]) return BHS_ERR_INVALID_ARG;
-        long long raised = 0;
-        memcpy(&raised, ws.host + AG_UNDEC, sizeof(raised));
-        *passes_out = (int)std::min<long long>(passes, 0x7fffffff);
-        if (raised == 0) return BHS_SUCCESS;
-    }
+    // (n levels at the most: n passes raise, one more finds nothing; the count is the last pass's alone)
+    return side_passes(h, h->trsvWs, d.n, kLvBatch, 2, TS_INTS, passes_out, [&] {
+        return timed(h, "levels_pass", d.n, [&] {
+            hipLaunchKernelGGL(k_lev_pass<L>, dim3(grid), dim3(256), 0, h->stream, d, in.upper, in.Ap, in.Aj, in.level, ctl);
+            return 1;
+        });
+    });
 }
 
 int lv_run(bhs_handle* h, const LvIn& in, int* nlevels_out, int* passes_out, double* ms_out)
 {
     const AgDims& d = in.d;
     SideWs& ws = h->trsvWs;
-    BHS_TRY(side_prepare(h, ws, TS_INTS, 0, 0));
+    BHS_TRY(side_open(h, ws, TS_INTS, 0, 0));
+    BHS_TRY(side_start(h, ws));
     int* ctl = (int*)ws.ctl.p;
-    BHS_HIP(hipMemsetAsync(ctl, 0, sizeof(int) * TS_INTS, h->stream));
-    side_reset_stats(h);
-    BHS_TRY(side_begin(h, ws));
     BHS_HIP(hipMemsetAsync(in.level, 0, sizeof(int) * (size_t)d.n, h->stream));
-    const int L = ag_lanes(d);
+    const int L = side_lanes(d.n, d.nnzS);
     int passes = 0;
-    BHS_TRY(L == 1 ? lv_passes<1>(h, in, ctl, &passes) : L == 4 ? lv_passes<4>(h, in, ctl, &passes)
-            : L == 16 ? lv_passes<16>(h, in, ctl, &passes) : lv_passes<64>(h, in, ctl, &passes));
+    BHS_TRY(with_lanes(L, [&](auto l) { return lv_passes<l.value>(h, in, ctl, &passes); }));
     const long long nlevels = ws.host[CO_NCOL];
     if (nlevels < 1 || nlevels > (long long)d.n) return BHS_ERR_INTERNAL;
     BHS_TRY(co_order(h, ws, "levels_order", TS_INTS, 0, d.n, nlevels, in.level, in.order, in.levelPtr));
     BHS_TRY(side_end(h, ws));
     BHS_TRY(side_read_ctl(h, ws, TS_INTS));                           // the order's error word and total
-    BHS_TRY(side_elapsed(h, ws, ms_out));
-    BHS_TRY(side_collect(h, 0));
+    BHS_TRY(side_close(h, ws, ms_out));
     long long total = 0;
     memcpy(&total, ws.host + AG_TOTAL, sizeof(total));
     if (ws.host[RD_ERR] || total != (long long)d.n) return BHS_ERR_INTERNAL;   // (the levels were this call's own)
@@ -102,9 +87,7 @@ struct TsIn {
 template <typename F>
 int ts_levels(bhs_handle* h, const char* name, TsDims d, int nlevels, const int* levelPtr, F&& launch)
 {
-    AgDims mean;
-    mean.n = d.n; mean.nnzS = d.nnzA; mean.seed = 0; mean.hasPrio = 0;
-    const int L = ag_lanes(mean);
+    const int L = side_lanes(d.n, d.nnzA);
     return timed(h, name, levelPtr[nlevels], [&] {
         int launches = 0;
         for (int c = 0; c < nlevels; ++c) {
@@ -117,23 +100,20 @@ int ts_levels(bhs_handle* h, const char* name, TsDims d, int nlevels, const int*
     });
 }
 
-// what the solve and the factorisation share around their launches: the control block (the pivot word at its identity),
-// the span, the call's one round trip
+// the shared frame as the solve and the factorisation have it: the pivot word at its identity ahead of the span, the
+// launches of enqueue(ctl), the call's one round trip
 template <typename F>
 int ts_call(bhs_handle* h, double* ms_out, F&& enqueue)
 {
     SideWs& ws = h->trsvWs;
-    BHS_TRY(side_prepare(h, ws, TS_INTS, 0, 0));
+    BHS_TRY(side_open(h, ws, TS_INTS, 0, 0));
     int* ctl = (int*)ws.ctl.p;
-    BHS_HIP(hipMemsetAsync(ctl, 0, sizeof(int) * TS_INTS, h->stream));
     BHS_HIP(hipMemsetD32Async((hipDeviceptr_t)(ctl + TS_PIVOT), 0x7fffffff, 1, h->stream));
-    side_reset_stats(h);
-    BHS_TRY(side_begin(h, ws));
+    BHS_TRY(side_start(h, ws));
     BHS_TRY(enqueue(ctl));
     BHS_TRY(side_end(h, ws));
     BHS_TRY(side_read_ctl(h, ws, TS_INTS));                           // the call's one round trip
-    BHS_TRY(side_elapsed(h, ws, ms_out));
-    BHS_TRY(side_collect(h, 0));
+    BHS_TRY(side_close(h, ws, ms_out));
     return ws.host[RD_ERR] ? (int)BHS_ERR_INVALID_ARG : (int)BHS_SUCCESS;
 }
 
@@ -144,7 +124,7 @@ int ts_run(bhs_handle* h, const TsIn& in, double* ms_out)
 {
     return ts_call(h, ms_out, [&](int* ctl) {
         return ts_levels(h, "trsv_level", in.d, in.nlevels, in.levelPtr, [&](int L, const TsDims& d, unsigned grid) {
-            const TsKernel kern = L == 1 ? k_trsv_level<1> : L == 4 ? k_trsv_level<4> : L == 16 ? k_trsv_level<16> : k_trsv_level<64>;
+            const TsKernel kern = with_lanes(L, [](auto l) -> TsKernel { return k_trsv_level<l.value>; });
             hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, h->stream, d, in.Ap, in.Aj, in.Ax, in.order, in.b, in.x, ctl);
         });
     });
@@ -154,7 +134,7 @@ int il_run(bhs_handle* h, const TsIn& in, value_t* Ax, int* pivot_out, double* m
 {
     BHS_TRY(ts_call(h, ms_out, [&](int* ctl) {
         return ts_levels(h, "ilu0_level", in.d, in.nlevels, in.levelPtr, [&](int L, const TsDims& d, unsigned grid) {
-            const IlKernel kern = L == 1 ? k_ilu0_level<1> : L == 4 ? k_ilu0_level<4> : L == 16 ? k_ilu0_level<16> : k_ilu0_level<64>;
+            const IlKernel kern = with_lanes(L, [](auto l) -> IlKernel { return k_ilu0_level<l.value>; });
             hipLaunchKernelGGL(kern, dim3(grid), dim3(256), 0, h->stream, d, in.Ap, in.Aj, Ax, in.order, ctl);
         });
     }));
@@ -173,22 +153,10 @@ int bhs_csr_levels_device(bhs_handle* h, int n, int nnzA, const int* d_rowPtrA, 
     if (!h || h->ps.open || n < 0 || nnzA < 0) return BHS_ERR_INVALID_ARG;
     if (flags != BHS_TRI_LOWER && flags != BHS_TRI_UPPER) return BHS_ERR_INVALID_ARG;   // exactly one triangle, nothing else
     if ((n > 0 && (!d_rowPtrA || !d_level || !d_order || !d_levelPtr)) || (nnzA > 0 && !d_colIndA)) return BHS_ERR_INVALID_ARG;
-    const struct { const void* p; size_t bytes; } inputs[] = {
-        {d_rowPtrA, sizeof(int) * ((size_t)n + 1)}, {d_colIndA, sizeof(int) * (size_t)nnzA}};
-    const struct { const void* p; size_t bytes; } outputs[] = {
-        {d_level, sizeof(int) * (size_t)n}, {d_order, sizeof(int) * (size_t)n}, {d_levelPtr, sizeof(int) * ((size_t)n + 1)}};
-    for (const auto& o : outputs)
-        for (const auto& x : inputs)
-            if (rd_overlap(o.p, o.bytes, x.p, x.bytes)) return BHS_ERR_INVALID_ARG;
-    for (int a = 0; a < 3; ++a)
-        for (int b = a + 1; b < 3; ++b)
-            if (rd_overlap(outputs[a].p, outputs[a].bytes, outputs[b].p, outputs[b].bytes)) return BHS_ERR_INVALID_ARG;
-    if (n == 0) {                                                     // no row, no level, nothing launched
-        if (nlevels_out) *nlevels_out = 0;
-        if (passes_out) *passes_out = 0;
-        if (ms_out) *ms_out = 0.0;
-        return BHS_SUCCESS;
-    }
+    if (side_aliased({{d_level, sizeof(int) * (size_t)n}, {d_order, sizeof(int) * (size_t)n}, {d_levelPtr, sizeof(int) * ((size_t)n + 1)}},
+                     {{d_rowPtrA, sizeof(int) * ((size_t)n + 1)}, {d_colIndA, sizeof(int) * (size_t)nnzA}}))
+        return BHS_ERR_INVALID_ARG;
+    if (n == 0) return side_nothing(nlevels_out, passes_out, ms_out);  // no row, no level, nothing launched
     LvIn in;
     in.d.n = n; in.d.nnzS = nnzA; in.d.seed = 0; in.d.hasPrio = 0;
     in.upper = flags == BHS_TRI_UPPER ? 1 : 0;
@@ -209,11 +177,11 @@ int bhs_csr_trsv_device(bhs_handle* h, int n, int nnzA, const int* d_rowPtrA, co
     if (listed > 0 && (!d_rowPtrA || !d_order || !d_b || !d_x)) return BHS_ERR_INVALID_ARG;
     if (nnzA > 0 && (!d_colIndA || !d_valA)) return BHS_ERR_INVALID_ARG;
     const size_t vec = sizeof(value_t) * (size_t)n;
-    const struct { const void* p; size_t bytes; } inputs[] = {
-        {d_rowPtrA, sizeof(int) * ((size_t)n + 1)}, {d_colIndA, sizeof(int) * (size_t)nnzA}, {d_valA, sizeof(value_t) * (size_t)nnzA},
-        {d_order, sizeof(int) * (size_t)listed}, {(const void*)d_b == (const void*)d_x ? nullptr : d_b, vec}};   // (x == b exactly: in place)
-    for (const auto& x : inputs)
-        if (rd_overlap(d_x, vec, x.p, x.bytes)) return BHS_ERR_INVALID_ARG;   // (x is the one array written)
+    const void* b = (const void*)d_b == (const void*)d_x ? nullptr : d_b;   // (x == b exactly: in place)
+    if (side_aliased({{d_x, vec}},                                    // (x is the one array written)
+                     {{d_rowPtrA, sizeof(int) * ((size_t)n + 1)}, {d_colIndA, sizeof(int) * (size_t)nnzA}, {d_valA, sizeof(value_t) * (size_t)nnzA},
+                      {d_order, sizeof(int) * (size_t)listed}, {b, vec}}))
+        return BHS_ERR_INVALID_ARG;
     if (listed == 0) {                                                // no row to solve for, nothing launched
         if (ms_out) *ms_out = 0.0;
         return BHS_SUCCESS;
@@ -235,10 +203,9 @@ int bhs_csr_ilu0_device(bhs_handle* h, int n, int nnzA, const int* d_rowPtrA, co
     const int listed = nlevels > 0 ? h_levelPtr[nlevels] : 0;
     if (listed > 0 && (!d_rowPtrA || !d_order)) return BHS_ERR_INVALID_ARG;
     if (nnzA > 0 && (!d_colIndA || !d_valA)) return BHS_ERR_INVALID_ARG;
-    const struct { const void* p; size_t bytes; } inputs[] = {
-        {d_rowPtrA, sizeof(int) * ((size_t)n + 1)}, {d_colIndA, sizeof(int) * (size_t)nnzA}, {d_order, sizeof(int) * (size_t)listed}};
-    for (const auto& x : inputs)
-        if (rd_overlap(d_valA, sizeof(value_t) * (size_t)nnzA, x.p, x.bytes)) return BHS_ERR_INVALID_ARG;   // (the values are the one array written)
+    if (side_aliased({{d_valA, sizeof(value_t) * (size_t)nnzA}},      // (the values are the one array written)
+                     {{d_rowPtrA, sizeof(int) * ((size_t)n + 1)}, {d_colIndA, sizeof(int) * (size_t)nnzA}, {d_order, sizeof(int) * (size_t)listed}}))
+        return BHS_ERR_INVALID_ARG;
     if (listed == 0) {                                                // no row to factorise, nothing launched
         if (pivot_out) *pivot_out = -1;
         if (ms_out) *ms_out = 0.0;

@@ -46,6 +46,7 @@
 #include "bhs_masked.hip.h"
 #include "bhs_add.hip.h"
 #include "bhs_select.hip.h"
+#include "bhs_aggregate.hip.h"    // (the control words of the graph and solver families: bhs_host_side.inc.h loops on them)
 #include "bhs_transpose.hip.h"
 
 #include <algorithm>
@@ -53,9 +54,11 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <map>
 #include <new>
 #include <tuple>
+#include <type_traits>
 #include <unordered_map>
 #include <vector>
 

@@ -258,6 +258,19 @@ class bhsparse(object):
             setattr(self, ms_attr, float(ms.value))
         return err
 
+    def _counted(self, name, family, count, turns, *args):
+        """A graph call of the C-ABI, `name`(handle, *args, count, turns, ms): the status code, BHS_ERR_NOT_READY without
+        a platform; sets <family>_ms (device time), <family>_<count> and <family>_<turns> (rounds or passes) on success."""
+        if self._h is None:
+            return _lib.BHS_ERR_NOT_READY
+        n, t, ms = C.c_int(0), C.c_int(0), C.c_double(0)
+        err = getattr(self._lib, name)(self._h, *args, C.byref(n), C.byref(t), C.byref(ms))
+        if err == BHSPARSE_SUCCESS:
+            setattr(self, family + "_ms", float(ms.value))
+            setattr(self, family + "_" + count, int(n.value))
+            setattr(self, family + "_" + turns, int(t.value))
+        return err
+
     def _symbolic_numeric(self, family, rows, device, vdtype, perm, symbolic, numeric):
         """The two calls of `family` (add, select, extract) on arrays made here: symbolic(Zp) -> (status, nnzZ, ...) fills
         the row pointer of rows + 1 ints, then numeric(nnzZ, Zp, Zj, Zx, pm) -> status fills arrays of nnzZ entries (Zx only

@@ -254,14 +254,8 @@ def components_raw_device(bh, n, nnz, dAp, dAj, flags, root, comp, size):
     """bhs_csr_components_device on caller-given arrays, the C arguments in order (comp and size may be None): the status
     code; sets bh.components_ncomp, bh.components_passes (the passes depend on timing) and bh.components_ms on success
     only."""
-    if bh._h is None:
-        return _lib.BHS_ERR_NOT_READY
-    ncomp, passes, ms = C.c_int(0), C.c_int(0), C.c_double(0)
-    err = bh._lib.bhs_csr_components_device(bh._h, int(n), int(nnz), _ptr(dAp), _ptr(dAj), int(flags), _ptr(root), _ptr(comp),
-                                            _ptr(size), C.byref(ncomp), C.byref(passes), C.byref(ms))
-    if err == _lib.BHS_SUCCESS:
-        bh.components_ncomp, bh.components_passes, bh.components_ms = int(ncomp.value), int(passes.value), float(ms.value)
-    return err
+    return bh._counted("bhs_csr_components_device", "components", "ncomp", "passes", int(n), int(nnz), _ptr(dAp), _ptr(dAj),
+                       int(flags), _ptr(root), _ptr(comp), _ptr(size))
 
 
 def components_device(bh, n, A):
@@ -314,15 +308,8 @@ def largest_component_csr(n, Ap, Aj, Ax, value_dtype=np.float64, device=0):
 def spanning_forest_raw_device(bh, n, nnzA, d_rowPtrA, d_colIndA, d_valA, flags, d_label, d_edgeLo, d_edgeHi, d_edgeVal):
     """bhs_csr_spanning_forest_device on caller-given arrays, the C arguments in order (d_valA and d_edgeVal may be None): the
     status code; sets bh.forest_nedges, bh.forest_rounds and bh.forest_ms on success only."""
-    if bh._h is None:
-        return _lib.BHS_ERR_NOT_READY
-    nedges, rounds, ms = C.c_int(0), C.c_int(0), C.c_double(0)
-    err = bh._lib.bhs_csr_spanning_forest_device(bh._h, int(n), int(nnzA), _ptr(d_rowPtrA), _ptr(d_colIndA), _ptr(d_valA),
-                                                 int(flags), _ptr(d_label), _ptr(d_edgeLo), _ptr(d_edgeHi), _ptr(d_edgeVal),
-                                                 C.byref(nedges), C.byref(rounds), C.byref(ms))
-    if err == _lib.BHS_SUCCESS:
-        bh.forest_nedges, bh.forest_rounds, bh.forest_ms = int(nedges.value), int(rounds.value), float(ms.value)
-    return err
+    return bh._counted("bhs_csr_spanning_forest_device", "forest", "nedges", "rounds", int(n), int(nnzA), _ptr(d_rowPtrA),
+                       _ptr(d_colIndA), _ptr(d_valA), int(flags), _ptr(d_label), _ptr(d_edgeLo), _ptr(d_edgeHi), _ptr(d_edgeVal))
 
 
 def spanning_forest_device(bh, n, A, maximum=False, absolute=False):

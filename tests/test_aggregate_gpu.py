@@ -230,6 +230,16 @@ def test_refusals(hd):
     torch.cuda.synchronize()
     assert amg.aggregate_raw_device(bh, n, nnz, dSp, dSj, None, 0, 0, dSj, None) == INV
     assert np.array_equal(dSj.cpu().numpy(), Sj)
+    # d_roots overlapping d_agg: a path of 8 vertices, two views into one tensor shifted by one element
+    Pp = np.array([0, 1, 3, 5, 7, 9, 11, 13, 14], np.int32)
+    Pj = np.array([1, 0, 2, 1, 3, 2, 4, 3, 5, 4, 6, 5, 7, 6], np.int32)
+    assert ar.invalid(8, 14, Pp, Pj) is None
+    dPp, dPj = up(Pp, np.int32), up(Pj, np.int32)
+    both = torch.full((9,), SENT_AGG, dtype=torch.int32).cuda()
+    torch.cuda.synchronize()
+    assert amg.aggregate_raw_device(bh, 8, 14, dPp, dPj, None, 0, 0, both[:8], both[1:]) == INV
+    assert amg.aggregate_raw_device(bh, 8, 14, dPp, dPj, None, 0, 0, both[:8], both[:8]) == INV
+    assert bool((both == SENT_AGG).all())
     # the next valid call on the same handle is correct
     check(run(bh, n, Sp, Sj, 0, what="after the refusals"), reference("poisson5pt_33", 0), "after the refusals")
 

@@ -516,6 +516,20 @@ def test_ilu0_refusals(hd):
     ilu_run(bh, T, want=INV, what="an order entry equal to n", order=o)
     torch.cuda.synchronize()
     assert amg.ilu0_raw_device(bh, n, T.nnz, T.A[0], T.A[1], T.A[2].clone(), nlevels, ptr, dorder, 1) == INV       # flags must be 0
+    # the values overlapping an input: the lower bidiagonal of a path of 8 vertices, its columns and its values two views into
+    # one tensor, the values shifted by one element
+    Pp = np.array([0, 1, 3, 5, 7, 9, 11, 13, 15], np.int32)
+    Pj = np.array([0, 0, 1, 1, 2, 2, 3, 3, 4, 4, 5, 5, 6, 6, 7], np.int32)
+    both = torch.zeros(16, dtype=tdt(dtype)).cuda()
+    cols = both.view(torch.int32)[:15]
+    cols.copy_(up(Pj, np.int32))
+    before = both.clone()
+    rows8 = np.arange(9, dtype=np.int32)                             # (row i is level i: the level pointer, and the order)
+    dPp, do8 = up(Pp, np.int32), up(rows8[:8], np.int32)
+    torch.cuda.synchronize()
+    bh.ilu0_pivot = -2
+    assert amg.ilu0_raw_device(bh, 8, 15, dPp, cols, both[1:], 8, rows8, do8, 0) == INV and bh.ilu0_pivot == -2
+    assert torch.equal(both.view(torch.uint8), before.view(torch.uint8))
     got, pivot = ilu_run(bh, T, what="after the refusals")
     assert pivot == -1 and ir.identity_error(n, Ap, Aj, Ax, got)[0] <= unit(dtype)
 
