@@ -423,6 +423,44 @@ def strength_device(bh, n, A, theta):
     return Sp, Sj
 
 
+def affinity_strength_device(bh, n, A, theta=0.5, vectors=16, sweeps=8, omega=2.0 / 3.0, seed=0):
+    """The symmetric pattern of strong connections of the n x n matrix A (rows strictly ascending, a non-zero diagonal) by
+    the affinity of relaxed test vectors (Livne and Brandt's lean AMG; also "algebraic distance"), which a symmetric
+    diagonal scaling of A does not defeat as it defeats strength_device's |a_ij| >= theta max: column c of X (n x vectors)
+    starts as _start_vector(n, seed + c) and takes `sweeps` weighted Jacobi sweeps on A x = 0, X <- X - omega D^-1 (A X)
+    (csr_spmm_device; the diagonal from csr_reduce_device); then, on pattern(A),
+        c_ij = (x_i . x_j)^2 / ((x_i . x_i) (x_j . x_j))
+    from three sampled products (dense.csr_sddmm_device: g on pattern(A), g^2 by a second call with times_m on g, the
+    x_i . x_i on the identity's pattern) and csr_scale_device with both divisions; strength_device's rule on c -- the
+    diagonal and every c_ij unless c_ij < theta max_{k != i} c_ik, united with its transpose -- ends it.  Returns
+    (rowPtr, colInd), what aggregate_device, cfsplit_device and match_device take; bh.affinity_ms is the calls' device
+    time."""
+    import torch
+    from .dense import csr_sddmm_device, csr_spmm_device
+    Ap, Aj, _ = A
+    dev, tdt = Ap.device, _tdt(bh)
+    X = torch.from_numpy(np.stack([_start_vector(n, seed + c) for c in range(int(vectors))], axis=1))
+    X = X.to(device=dev, dtype=tdt).contiguous()
+    diag = bh.csr_reduce_device(n, n, A, _lib.BHS_AXIS_DIAG, _lib.BHS_RED_PLUS)
+    ms = bh.reduce_ms
+    for _ in range(int(sweeps)):
+        AX = csr_spmm_device(bh, n, n, A, X)
+        ms += bh.spmv_ms
+        X = X - float(omega) * (AX / diag[:, None])
+    g = csr_sddmm_device(bh, n, n, (Ap, Aj, None), X, X)
+    ms += bh.sddmm_ms
+    g2 = csr_sddmm_device(bh, n, n, (Ap, Aj, g), X, X, times_m=True)
+    ms += bh.sddmm_ms
+    eye = (torch.arange(n + 1, dtype=torch.int32, device=dev), torch.arange(n, dtype=torch.int32, device=dev), None)
+    dd = csr_sddmm_device(bh, n, n, eye, X, X)
+    ms += bh.sddmm_ms
+    c = bh.csr_scale_device(n, n, (Ap, Aj, g2), 1.0, left=dd, right=dd, left_div=True, right_div=True)
+    ms += bh.scale_ms
+    Sp, Sj = strength_device(bh, n, (Ap, Aj, c), theta)
+    bh.affinity_ms = ms + bh.strength_ms
+    return Sp, Sj
+
+
 def tentative_device(bh, n, agg, nagg, cand=None):
     """The tentative prolongator T (n x nagg) of the aggregates `agg` and one candidate vector (ones when None):
     T(i, agg[i]) = cand[i] / ||cand over the aggregate||_2.  The column norms come from the stable transpose of T with its

@@ -94,6 +94,56 @@ def residual_csr(m, n, Ap, Aj, Ax, x, b, value_dtype=np.float64, device=0):
     return spmv_csr(m, n, Ap, Aj, Ax, x, alpha=-1.0, beta=1.0, y=b, value_dtype=value_dtype, device=device)
 
 
+# ---------------------------------------------------------------- the sampled dense-dense product
+def csr_sddmm_raw_device(bh, m, n, nnzM, d_valM, d_rowPtrM, d_colIndM, k, alpha, d_X, ldX, d_Y, ldY, beta, d_valZ, flags):
+    """bhs_csr_sddmm_device on caller-given arrays, the C arguments in order (include/bhsparse_hip.h, "sampled dense-dense
+    product"; X: m x k, Y: n x k, row-major with leading dimensions ldX, ldY; d_valM may be None without
+    BHS_SDDMM_TIMES_M; d_valZ may be d_valM itself): the status code; sets bh.sddmm_ms."""
+    if bh._h is None:
+        return _lib.BHS_ERR_NOT_READY
+    return bh._timed(bh._lib.bhs_csr_sddmm_device, "sddmm_ms", int(m), int(n), int(nnzM), _ptr(d_valM), _ptr(d_rowPtrM),
+                     _ptr(d_colIndM), int(k), float(alpha), _ptr(d_X), int(ldX), _ptr(d_Y), int(ldY), float(beta), _ptr(d_valZ),
+                     int(flags))
+
+
+def csr_sddmm_device(bh, m, n, M, X, Y, alpha=1.0, beta=0.0, Z=None, times_m=False):
+    """Z(i, j) = alpha (X(i, :) . Y(j, :)) [M(i, j)] + beta Z(i, j) on the entries of M: M = (rowPtr, colInd, val or None)
+    torch tensors on the handle's GPU (val is read with times_m only), X (m x k) and Y (n x k) 2-D torch tensors there whose
+    rows are contiguous -- stride(0) is the leading dimension; Y may be X itself.  Z (nnz values) is written in place -- it
+    may be M's val itself --, or made here when None (beta == 0 never reads it).  Returns Z's values; sets bh.sddmm_ms;
+    raises BhsparseError on failure."""
+    import torch
+    Mp, Mj, Mx = M
+    nnz = Mj.numel()
+    k = X.shape[1] if X.dim() == 2 else 0
+    for name, T, rows in (("X", X, m), ("Y", Y, n)):
+        if not k or T.dim() != 2 or tuple(T.shape) != (rows, k) or (k > 1 and T.stride(1) != 1):
+            raise ValueError("%s is a row-major %d x k tensor, k >= 1" % (name, rows))
+    if times_m and Mx is None:
+        raise ValueError("times_m wants M's values")
+    if Z is None:
+        Z = _alloc(nnz, X.dtype, X.device)[:nnz]
+    ld = lambda T: max(int(T.stride(0)), k) if T.shape[0] > 1 else k   # noqa: E731  (one row or none: any ld will do)
+    torch.cuda.synchronize()                           # the library works on its own stream (see facade.initData_device)
+    _check(csr_sddmm_raw_device(bh, m, n, nnz, Mx if times_m else None, Mp, Mj, k, alpha, X, ld(X), Y, ld(Y), beta, Z,
+                                _lib.BHS_SDDMM_TIMES_M if times_m else 0), "bhs_csr_sddmm_device")
+    return Z
+
+
+def sddmm_csr(m, n, Mp, Mj, Mx, X, Y, alpha=1.0, beta=0.0, Z=None, times_m=False, value_dtype=np.float64, device=0):
+    """Convenience: the sampled product once on host arrays (M: m x n CSR, rows in any order, duplicates each get their own
+    value, Mx may be None without times_m; X: m x k, Y: n x k; Z: nnz values or None), staged as torch tensors on the
+    handle's device.  Returns (Z's values value_dtype[nnz], info) with info["kernels"], info["ms"].  Needs no multiply
+    data."""
+    M = _device_csr(Mp, Mj, Mx, value_dtype, device)
+    dX = _upload(np.asarray(X).reshape(m, -1), value_dtype, device)
+    dY = _upload(np.asarray(Y).reshape(n, -1), value_dtype, device)
+    dZ = None if Z is None else _upload(np.asarray(Z).reshape(-1), value_dtype, device)
+    with _handle(value_dtype, device, None) as bh:
+        out = csr_sddmm_device(bh, m, n, M, dX, dY, alpha, beta, dZ, times_m)
+        return out.cpu().numpy(), {"kernels": bh.kernel_stats(), "ms": bh.sddmm_ms}
+
+
 # ---------------------------------------------------------------- the product with its reductions
 def csr_spmv_dots_raw_device(bh, m, n, nnzA, d_valA, d_rowPtrA, d_colIndA, alpha, d_x, beta, d_y, d_z, d_w, dots):
     """bhs_csr_spmv_dots_device on caller-given arrays, the C arguments in order (include/bhsparse_hip.h, "relaxation and

@@ -95,6 +95,16 @@ public:
                         const index_type *d_colIndA, int k, double alpha, const value_type *d_X, long long ldX, double beta,
                         value_type *d_Y, long long ldY);
 
+    // EXTENSION, not part of the reference's API: the sampled dense-dense product (bhs_csr_sddmm_device,
+    // include/bhsparse_hip.h, "sampled dense-dense product") on DEVICE arrays: Z(i, j) = alpha (X(i, :) . Y(j, :)) [M(i, j)]
+    // + beta Z(i, j) on the entries of the m x n pattern M; X m x k and Y n x k row-major with leading dimensions ldX,
+    // ldY >= k (d_Y may be d_X); d_valM is read under BHS_SDDMM_TIMES_M only (else it may be 0); d_valZ, nnzM values, may be
+    // d_valM.  The bits of an entry are those of a host loop in the rule's order.  Needs initPlatform only; does not disturb
+    // the data of initData or get_C's result.
+    int csr_sddmm_device(int m, int n, int nnzM, const value_type *d_valM, const index_type *d_rowPtrM,
+                         const index_type *d_colIndM, int k, double alpha, const value_type *d_X, long long ldX,
+                         const value_type *d_Y, long long ldY, double beta, value_type *d_valZ, unsigned flags);
+
     // EXTENSION, not part of the reference's API: polynomial relaxation and the product with its reductions
     // (bhs_csr_relax_device, bhs_csr_spmv_dots_device, bhs_chebyshev_coefficients; include/bhsparse_hip.h, "relaxation and
     // fused products") on DEVICE arrays.  csr_relax_device: `steps` sweeps on the n x n matrix A in one call, coef a HOST
@@ -387,6 +397,14 @@ inline int bhsparse::csr_spmm_device(int m, int n, int nnzA, const value_type *d
 {
     if (!_h) return BHS_ERR_NOT_READY;
     return bhs_csr_spmm_device(_h, m, n, nnzA, d_valA, d_rowPtrA, d_colIndA, k, alpha, d_X, ldX, beta, d_Y, ldY, 0);
+}
+
+inline int bhsparse::csr_sddmm_device(int m, int n, int nnzM, const value_type *d_valM, const index_type *d_rowPtrM,
+                                      const index_type *d_colIndM, int k, double alpha, const value_type *d_X, long long ldX,
+                                      const value_type *d_Y, long long ldY, double beta, value_type *d_valZ, unsigned flags)
+{
+    if (!_h) return BHS_ERR_NOT_READY;
+    return bhs_csr_sddmm_device(_h, m, n, nnzM, d_valM, d_rowPtrM, d_colIndM, k, alpha, d_X, ldX, d_Y, ldY, beta, d_valZ, flags, 0);
 }
 
 inline int bhsparse::csr_relax_device(int n, int nnzA, const value_type *d_valA, const index_type *d_rowPtrA,

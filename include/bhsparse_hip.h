@@ -680,6 +680,60 @@ BHS_API int bhs_csr_spmm_device(bhs_handle *h, int m, int n, int nnzA,
         int k, double alpha, const bhs_value_t *d_X /* n x k */, long long ldX /* >= k */,
         double beta, bhs_value_t *d_Y /* m x k, in/out */, long long ldY /* >= k */, double *ms_out /* may be NULL */);
 
+/* ---- sampled dense-dense product -------------------------------------------
+ * The product of two dense matrices evaluated only at the entries of a sparse pattern (SDDMM, the third of the usual
+ * sparse-dense trio beside "CSR x dense"):
+ *     Z(i, j) = alpha (X(i, :) . Y(j, :)) [M(i, j)] + beta Z_old(i, j)     for (i, j) in pattern(M)
+ * -- scores on the edges of a graph (cosine similarity, attention logits that bhs_csr_spmm_device then applies), the
+ * residual of a factorisation on its observed entries, the affinity of relaxed test vectors as an AMG strength of
+ * connection; no reference counterpart; bhs_sddmm.hip.h.
+ * M: m x n, 0-based int32 CSR; rows need NOT be ascending, duplicate (row, column) pairs are legal and every stored entry
+ * gets its own value.  m, n and nnzM may be 0; k >= 1.  d_valM is read under BHS_SDDMM_TIMES_M only and may be NULL
+ * without it.  X is m x k, Y is n x k, both row-major with leading dimensions ldX, ldY >= k: element (i, c) sits at
+ * i * ld + c, indexed in 64 bits; the gap columns c in [k, ld) are never read.  d_X == d_Y is legal.  Z lives on M's
+ * pattern: d_valZ holds nnzM values, the pattern arrays are not copied.
+ * The call is synchronous on the handle's stream, needs no bound data (it works on a handle straight after bhs_create),
+ * returns BHS_ERR_INVALID_ARG between bhs_spgemm_symbolic and bhs_spgemm_finish, and leaves the handle as it was:
+ * counters, queues (2 m ints), events and the pinned mirror are buffers of its own from the grow-only pool; C of the last
+ * multiply (whose device arrays from bhs_get_C_device may be passed straight in as M), a served sum or selection,
+ * "class_state", the speculative-launch figures and every option stay.  ms_out (may be NULL): device time of the call,
+ * validation included.
+ * Arithmetic: all of it in double with FMA contraction OFF, so that a host loop (or numpy) restates it bit for bit.  Let
+ *   T = min(64, the smallest power of two >= k).  Lane l in [0, T) holds s_l, starting from +0.  For tiles t = 0, 1, .. in
+ *   ascending order lane l does s_l = s_l + double(X(i, tT + l)) * double(Y(j, tT + l)) where tT + l < k (the product is
+ *   rounded, then the sum; a lane past k adds nothing).  The lanes then meet in the butterfly xor 1, 2, 4, .. T / 2, in
+ *   that order: s_l = s_l + s_(l xor w), both partners the same bits.  Under BHS_SDDMM_TIMES_M s = s * double(m_ij).
+ *   t = alpha * s; if beta != 0, t = t + beta * double(z_old); ONE rounding to bhs_value_t.
+ *   beta == 0 never reads d_valZ: it may hold NaN or be uninitialised.  alpha == 0 takes no shortcut: Inf and NaN in X, Y
+ *   or M propagate by IEEE.  In the float build the products are exact and the rule is the same.
+ * Reproducibility: the bits of Z(i, j) are a function of X(i, :), Y(j, :), k, alpha, beta, m_ij and z_old alone -- not of
+ *   the row's length, the entry's place in it, the kernel family that served it, the handle or the run.  No atomics.
+ * Aliasing: d_valZ may be exactly d_valM (in place; under TIMES_M with beta != 0 both read the same old number).  Any
+ *   other overlap of d_valZ[0, nnzM) with an input returns BHS_ERR_INVALID_ARG on the host with d_valZ untouched.
+ * Validation: on the device.  rowPtrM[0] != 0, a decreasing rowPtrM, rowPtrM[m] != nnzM, or a column outside [0, n)
+ *   return BHS_ERR_INVALID_ARG.  The check comes before the dependent read: a refused row pointer is never used to
+ *   address colIndM, valM or valZ, a refused column never to address Y.  Z is an in/out array, so a refused call may leave
+ *   d_valZ[0, nnzM) partly written; nothing is ever written outside it.
+ *   On the host: a NULL handle, negative sizes, k < 1, ldX < k, ldY < k, a NULL d_rowPtrM, a NULL d_colIndM, d_X, d_Y or
+ *   d_valZ with nnzM > 0, a NULL d_valM under TIMES_M with nnzM > 0, or unknown flag bits return BHS_ERR_INVALID_ARG with
+ *   nothing written.
+ * Rows are binned by length as the reductions bin them -- for load balance alone, no sum crosses entries --;
+ *   bhs_get_kernel_stats then reports the families sddmm_short (every row in order: the row pointer's check, the rows of
+ *   up to 32 entries), sddmm_wave (up to 1024 entries, a wave each) and sddmm_long (a workgroup each).  One round trip for
+ *   the queues' lengths, and only when nnzM > 32.  The T lanes of an entry lie along k: one entry's gather is one
+ *   contiguous read of Y's row, X's row piece stays in a register across the row's entries (k > 64 loops over tiles of 64
+ *   and reads it again per tile).  Compulsory traffic: 4 bytes an entry and one value written (one more read under
+ *   TIMES_M, one more where beta != 0), 4 (m + 1), X once, and a row of Y per entry wherever the cache does not hold it.  */
+#define BHS_SDDMM_TIMES_M 1u
+BHS_API int bhs_csr_sddmm_device(bhs_handle *h, int m, int n, int nnzM,
+        const bhs_value_t *d_valM /* may be NULL without TIMES_M */,
+        const int *d_rowPtrM, const int *d_colIndM,
+        int k, double alpha,
+        const bhs_value_t *d_X /* m x k */, long long ldX /* >= k */,
+        const bhs_value_t *d_Y /* n x k */, long long ldY /* >= k */,
+        double beta, bhs_value_t *d_valZ /* nnzM, in/out */,
+        unsigned flags /* BHS_SDDMM_TIMES_M or 0 */, double *ms_out /* may be NULL */);
+
 /* ---- relaxation and fused products ----------------------------------------
  * What a multigrid cycle and a Krylov iteration do between two setups, as library calls with every array on the device
  * (no reference counterpart; bhs_relax.hip.h): `steps` sweeps of a polynomial smoother in one call -- weighted Jacobi, or
