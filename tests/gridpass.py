@@ -9,11 +9,17 @@ lengths 3, 5, 17, 67); where the restatement is a Python loop over the vertices 
 seconds (the colouring at L = 1 and 4, the levels at L = 1) they are scantiles.cliques(q, c) with q = 3, 5 and a closed form.
 
 B. The long-row kernels take one workgroup a row of more than 1024 entries and cap the grid at 8 workgroups a CU:
-`long_rows(numCU)` is a matrix with 8 numCU + 37 such rows.
+`long_rows(numCU)` is a matrix with 8 numCU + 37 such rows.  The sampled dense-dense product takes it as its pattern at the
+widths SDDMM_KS (restated SDDMM_SLICE rows at a time), the relaxation runs RELAX_CASES on `long_square`, the matrix with empty
+rows behind its own, and the fused product's two reductions are those of `long_dots`.
+
+C. k_dot_finish, one workgroup, adds the partials of the fused product's reductions DOT_TURN a turn: `dots_case(DOTS_M)` has
+DOT_TURN + 1 of them, the last from a partial workgroup, and `dots_case(DOTS_M_AFTER)` two.
 
 Everything is made once per session (`cached`, scantiles' own cache) and shared by both builds: the values are small integers
 or dyadic numbers that both value types hold exactly.  `SECONDS` (scantiles') books the CPU time of the references per
-family."""
+family: at 256 CUs "sddmm" 2.1 to 5.8 s (1.8 s of it each at k = 64, k = 65 and k = 65 in place on the slower machine),
+"relax" 1.5 to 3 s (five cases, each restated in both value types), "dots" under 0.1 s."""
 import numpy as np
 import scipy.sparse as sp
 
@@ -25,7 +31,9 @@ import gsref as gr
 import iluref as ir
 import matchref as mr
 import reduceref as rr
+import relaxref as rx
 import scantiles as st
+import sddmmref as sd
 import selectref as sr
 import spmvref
 import spmvsrref
@@ -46,6 +54,20 @@ LONG = 1024                                        # kSpmvWaveL, kRdWaveL, kTrWa
 LDS_KEYS = 4096                                    # kTrLdsMax, kExLdsMax: a longer row sorts in global memory
 N_COLS = 6007                                      # columns of the long-row matrix
 EXTRA = 37                                         # long rows beyond the cap
+SDDMM_KS = (1, 2, 3, 16, 64, 65)                   # tiles 1, 2, 4 (sd_owner's three cases), 16 and 64, and a second tile in a lane
+SDDMM_IN_PLACE_KS = (3, 65)                        # ... of them under TIMES_M in place on M's values, with
+SDDMM_IN_PLACE = (2.0, -1.0)                       # alpha, beta: a row done twice gives m, done once 2 s m - m
+SDDMM_GAP = 3                                      # columns of NaN behind X's and Y's k
+SDDMM_SLICE = 64                                   # rows of M a call of the restatement
+DOT_PER = 4096                                     # kDotPer: elements a workgroup of k_dot_part, one partial each
+DOT_TURN = 256                                     # partials a turn of k_dot_finish's loop: its one workgroup's threads
+DOTS_M = (DOT_TURN + 1) * DOT_PER - 1000           # 257 partials, the last of a partial workgroup
+DOTS_M_AFTER = DOT_PER + 1                         # two partials, with the stale ones of DOTS_M behind them
+RELAX_COEF = ((0.0, 1.0), (0.5, 0.5), (0.25, 2.0), (0.5, 1.0))      # test_relax_gpu.COEF
+# name: (sparse values, the steps' (a, c), is d kept, BHS_RELAX_ZERO_GUESS)
+RELAX_CASES = {"one step": (False, ((0.5, 2.0),), True, False), "one step, no d": (False, ((0.0, 1.0),), False, False),
+               "four steps": (True, RELAX_COEF, True, False), "four steps, zero guess": (True, RELAX_COEF, True, True),
+               "jacobi": (True, ((0.0, 0.5),) * 4, False, False)}
 # per L the weight makers of the matching, and (maker, flags) of the forest: every maker and both flag words are met, and the
 # inputs of a million vertices twice each
 MATCH_MAKERS = {1: ("ties", "specials"), 4: ("asymmetric",), 16: ("ties",), 64: ("specials",)}
@@ -370,3 +392,123 @@ def long_select(numCU, which, dtype=np.float64):
     m, n, (Ap, Aj, Ax) = long_rows(numCU)
     return cached(("gp long select", numCU, which, np.dtype(dtype).name),
                   lambda: select_vectorised(m, n, Ap, Aj, np.ascontiguousarray(Ax, dtype), SELECT_SPECS[which]), "long rows")
+
+
+# ---------------------------------------------------------------- B: the sampled dense-dense product on the long rows
+def sddmm_dense(numCU, k):
+    """(X, Y): m x k and N_COLS x k, integers in [-4, 4], drawn per k"""
+    def make():
+        m, n, _ = long_rows(numCU)
+        rng = np.random.default_rng(7500 + 100 * k + numCU)
+        return rng.integers(-4, 5, (m, k)).astype(np.float64), rng.integers(-4, 5, (n, k)).astype(np.float64)
+    return cached(("gp sddmm dense", numCU, k), make)
+
+
+def sddmm_sliced(m, n, M, X, Y, alpha=1.0, beta=0.0, times_m=False, rows=SDDMM_SLICE):
+    """sddmmref.sddmm with Z = M's values (in place), `rows` rows of M at a time: its temporaries are entries x T doubles"""
+    Mp, Mj, Mx = M
+    out = [np.zeros(0)]
+    for r0 in range(0, m, rows):
+        r1 = min(m, r0 + rows)
+        a, b = int(Mp[r0]), int(Mp[r1])
+        out.append(sd.sddmm(r1 - r0, n, np.asarray(Mp[r0:r1 + 1], np.int64) - a, Mj[a:b], Mx[a:b], X[r0:r1], Y, alpha, beta, Mx[a:b],
+                            times_m))
+    return np.concatenate(out)
+
+
+def sddmm_reference(numCU, k, in_place=False):
+    """Z in float64 -- integers below 2^24 in magnitude (asserted), so both builds hold it, and the rule's bits are the
+    same in both: X Y^T on M's pattern, or under in_place 2 (X Y^T) .* M - M"""
+    m, n, M = long_rows(numCU)
+    X, Y = sddmm_dense(numCU, k)
+
+    def make():
+        alpha, beta = SDDMM_IN_PLACE if in_place else (1.0, 0.0)
+        Z = sddmm_sliced(m, n, M, X, Y, alpha, beta, in_place)
+        assert np.array_equal(Z, np.round(Z)) and np.abs(Z).max() < 2.0 ** 24 and len(Z) == len(M[1])
+        return Z
+    return cached(("gp sddmm", numCU, k, in_place), make, "sddmm")
+
+
+# ---------------------------------------------------------------- B: the relaxation on the long rows
+def long_square(numCU, sparse_values):
+    """(n, (Ap, Aj, Ax), diag): the long-row matrix made square by N_COLS - m empty rows behind its own, diag = 1, 2 or 4;
+    sparse_values: all but four values a row are zero, the rest +-1 (what test_relax_gpu.square does), so that the row sums
+    of several steps stay exact"""
+    def make():
+        m, n, (Ap, Aj, Ax) = long_rows(numCU)
+        assert m <= n
+        Sp = np.concatenate([Ap, np.full(n - m, Ap[-1], np.int32)])
+        rng = np.random.default_rng(74 + numCU)
+        diag = 2.0 ** rng.integers(0, 3, n)
+        vals = Ax
+        if sparse_values:
+            rows = np.repeat(np.arange(m), np.diff(Ap))
+            order = np.lexsort((rng.random(len(Aj)), rows))           # every row's entries in a random order
+            rank = np.arange(len(Aj)) - np.repeat(Ap[:-1].astype(np.int64), np.diff(Ap))
+            keep = np.zeros(len(Aj), bool)
+            keep[order[rank < 4]] = True
+            vals = np.where(keep, np.sign(Ax) + (Ax == 0), 0.0)
+        return n, (Sp, Aj, vals), diag
+    return cached(("gp long square", numCU, sparse_values), make)
+
+
+def relax_vectors(numCU):
+    """(b, x, d): integers in [-3, 3], as test_relax_gpu.vectors draws them"""
+    def make():
+        rng = np.random.default_rng(75 + numCU)
+        return tuple(rng.integers(-3, 4, N_COLS).astype(np.float64) for _ in range(3))
+    return cached(("gp relax vectors", numCU), make)
+
+
+def relax_reference(numCU, case):
+    """(x, d) of RELAX_CASES[case] in float64 (d None where none is kept).  The restatement run in float32 gives the same
+    numbers (asserted): no step's x or d rounds in either build, so the sums are exact in whatever order the device adds"""
+    sparse, coef, with_d, zero = RELAX_CASES[case]
+    n, (Ap, Aj, Ax), diag = long_square(numCU, sparse)
+    b, x, d = relax_vectors(numCU)
+
+    def make():
+        both = [rx.relax(n, Ap, Aj, Ax, diag, coef, b, x, d if with_d else None, zero_guess=zero, dtype=t)[:2]
+                for t in (np.float64, np.float32)]
+        for wide, narrow in zip(*both):
+            assert (wide is None and narrow is None) or np.array_equal(wide, narrow.astype(np.float64)), case
+        assert not np.array_equal(both[0][0], x)
+        return both[0]
+    return cached(("gp relax", numCU, case), make, "relax")
+
+
+# ---------------------------------------------------------------- B and C: the reductions beside a product
+def exact_dots(z, w):
+    """(z.z, w.z) in integer arithmetic; every sum of magnitudes stays below `2^53`: any order of additions is exact"""
+    assert np.array_equal(z, np.round(z)) and np.array_equal(w, np.round(w))
+    zi, wi = z.astype(np.int64), w.astype(np.int64)
+    assert int((zi * zi).sum()) < 2 ** 53 and int(np.abs(wi * zi).sum()) < 2 ** 53
+    return int((zi * zi).sum()), int((wi * zi).sum())
+
+
+def long_dots(numCU):
+    """(w, z.z, w.z) for z = long_references()["spmv"] = 2 A x - y: w integers in [-9, 9]"""
+    def make():
+        m, _, _ = long_rows(numCU)
+        w = np.random.default_rng(76 + numCU).integers(-9, 10, m).astype(np.float64)
+        return (w,) + exact_dots(long_references(numCU)["spmv"][:, 0], w)
+    return cached(("gp long dots", numCU), make, "long rows")
+
+
+def dots_case(m):
+    """(A, x, y, w, z, z.z, w.z) for section C: A is m x m with one entry a row, its columns a permutation, its values in
+    {-2, -1, 1, 2}; x, y and w integers in [-3, 3]; z = A x + y, so |z| <= 9 and both sums stay below 2^27; the last
+    workgroup of k_dot_part has a share in both sums that is not zero"""
+    def make():
+        rng = np.random.default_rng(77)
+        Aj = rng.permutation(m).astype(np.int32)
+        Ax = rng.choice([-2.0, -1.0, 1.0, 2.0], m)
+        x, y, w = (rng.integers(-3, 4, m).astype(np.float64) for _ in range(3))
+        z = Ax * x[Aj] + y
+        zz, wz = exact_dots(z, w)
+        assert np.abs(z).max() <= 9 and zz < 2 ** 27 and int(np.abs(w * z).sum()) < 2 ** 27
+        last = (-(-m // DOT_PER) - 1) * DOT_PER
+        assert exact_dots(z[last:], w[last:])[0] != 0 and exact_dots(z[last:], w[last:])[1] != 0
+        return (np.arange(m + 1, dtype=np.int32), Aj, Ax), x, y, w, z, zz, wz
+    return cached(("gp dots", m), make, "dots")

@@ -19,7 +19,18 @@ CUs); every other combination is run here, L = 4 of the components, the matching
 B. The long-row queues (one workgroup a row of more than 1024 entries, the grid capped at 8 workgroups a CU): spmv, spmm,
 the semiring products, the row reductions, the scaling, the transpose, the extraction and the selection on one matrix with
 8 numCU + 37 long rows, about every 200th of them beyond the 4096 keys a workgroup sorts in LDS; integer values, so every
-result is compared exactly.
+result is compared exactly.  On the same matrix the kernels whose second turn carries state: k_sd_long<T> (it keeps `bad`
+across rows) at the tiles T = 1, 2, 4, 16 and 64 and at k = 65, also in place with beta != 0, where a row done twice is wrong;
+k_rx_long (sW behind a trailing barrier, ctl[RD_ERR] read once a workgroup) once per product pass of one and of four steps
+on the matrix made square by empty rows, where a skipped row keeps the x of two steps before; and spmv_long as the fused
+product launches it, on its own workspace's queues, with both reductions exact.
+
+C. The partials of the fused reductions: k_dot_finish, one workgroup, adds them 256 a turn.  m = 257 x 4096 - 1000 gives 257
+(whatever the CU count: k_dot_part's grid has no cap), the last from a partial workgroup, so thread 0 adds two; m = 4097
+afterwards leaves 255 stale partials behind the two that count.
+
+The references of these families took 3.7 s of CPU a session beside a 256-CU device (the sampled product 2.1 s, most of it
+at k = 64 and 65; the relaxation 1.5 s for its five cases in both value types; section C's 0.02 s), on a slower CPU 9 s.
 
 Before a call the test asserts that its block count exceeds the cap, after it that the kernel record books the rows n
 implies, and prints both: it cannot pass without reaching the second turn."""
@@ -31,6 +42,7 @@ import forestref as fr
 import gridpass as gp
 import reduceref as rr
 import scantiles as st
+import sddmmref as sd
 import test_aggregate_gpu as aggt
 import test_components_gpu as cct
 import test_extract_gpu as ext
@@ -38,14 +50,18 @@ import test_forest_gpu as ft
 import test_gs_gpu as gst
 import test_match_gpu as mt
 import test_reduce_gpu as rdt
+import test_relax_gpu as rxt
 import test_scan_tiles_gpu as tiles
+import test_sddmm_gpu as sdt
 import test_select_gpu as selt
+import test_spmv_dots_gpu as dt
 import test_spmv_gpu as spmvt
 import test_spmv_sr_gpu as srt
 import test_transpose_gpu as trt
 import test_trsv_gpu as trsvt
 
 from benchmark_spgemm_using_csr_amd import _lib, amg
+from benchmark_spgemm_using_csr_amd import dense as bhdense
 from benchmark_spgemm_using_csr_amd import facade as bhmod
 
 pytestmark = pytest.mark.gpu
@@ -341,3 +357,100 @@ def test_long_rows_select(hd, which):
     ref = gp.long_select(num_cu(), which, dtype)
     selt.check_select(bh, m, n, A, gp.SELECT_SPECS[which], dtype, what=("long rows", which), ref=ref)
     long_reached(bh, build, "select_long")
+
+
+def test_long_rows_sddmm(hd):
+    """k_sd_long<T> at T = 1, 2, 4, 16 and 64 and, at k = 65, with a second tile in a lane: X Y^T on the long-row pattern over
+    a Z of NaN; at k = 3 and 65 also 2 (X Y^T) .* M - M in place on M's values, where a row done twice would end as M"""
+    bh, dtype, build = hd
+    m, n, M = gp.long_rows(num_cu())
+    for k in gp.SDDMM_KS:
+        X, Y = gp.sddmm_dense(num_cu(), k)
+        cases = [(1.0, 0.0, False)] + ([gp.SDDMM_IN_PLACE + (True,)] if k in gp.SDDMM_IN_PLACE_KS else [])
+        for alpha, beta, in_place in cases:
+            want = np.ascontiguousarray(gp.sddmm_reference(num_cu(), k, in_place), dtype)
+            got = sdt.run(bh, dtype, m, n, M, X, Y, alpha, beta, times_m=in_place, in_place=in_place, gap=gp.SDDMM_GAP)
+            assert sd.same_bits(got, want), (k, in_place, np.argwhere(got != want)[:5])
+            assert sdt.families(bh) == {"sddmm_short", "sddmm_wave", "sddmm_long"}
+            print("k = %d%s:" % (k, " in place" if in_place else ""), end=" ")
+            long_reached(bh, build, "sddmm_long")
+
+
+@pytest.mark.parametrize("case", sorted(gp.RELAX_CASES))
+def test_long_rows_relax(hd, case):
+    """k_rx_long once per product pass on the square long-row pattern: one step on full integer values (the call ends in
+    relax_finish), four steps on sparse values from the caller's x and from the zero guess over an x of NaN (the queues of
+    k_rx_short<true> and of k_rx_zero, the ping-pong of the two scratch x and the caller's, d from scratch to the
+    caller's), and four Jacobi steps without d.  A row that a pass skipped keeps an x that is two steps old."""
+    bh, dtype, build = hd
+    sparse, coef, with_d, zero = gp.RELAX_CASES[case]
+    n, A, diag = gp.long_square(num_cu(), sparse)
+    b, x, d = gp.relax_vectors(num_cu())
+    wx, wd = gp.relax_reference(num_cu(), case)
+    coef = np.array(coef)
+    assert case != "four steps" or np.array_equal(coef, rxt.COEF)
+    gx, gd = rxt.call(bh, dtype, n, A, diag, coef, b, x, d if with_d else None, zero=zero, nan_x=zero)
+    exactly(gx, wx, (case, "x"))
+    assert (gd is None) == (wd is None)
+    if with_d:
+        exactly(gd, wd, (case, "d"))
+    passes = len(coef) - (1 if zero else 0)
+    lens = np.diff(A[0])
+    nq, nq_wave, cap = gp.sizes(num_cu())["long"], int(((lens > 32) & (lens <= gp.LONG)).sum()), gp.CAP_B * num_cu()
+    got = stats(bh)
+    assert got["relax_long"]["launches"] == passes == got["relax_wave"]["launches"], (case, got)
+    assert got["relax_wave"]["rows"] == nq_wave * passes and got["relax_short"]["rows"] == n * passes, (case, got)
+    assert got["relax_long"]["rows"] == nq * passes and nq > cap, (case, got["relax_long"], nq, passes, cap)
+    print("%s relax %s: %d rows over a grid of %d in each of %d launches" % (build, case, nq, cap, passes))
+
+
+def fused_records(bh, D, x, alpha, beta, y, w, z, dots, what):
+    """tests/test_spmv_dots_gpu.py's call ends in the plain product, whose records replace the fused call's: the fused call
+    once more, out of place -- the same bits in z and in both reductions --, and ITS records"""
+    dx, dy, dw = up(x, D.dtype), up(y, D.dtype), up(w, D.dtype)
+    dz = padded(np.full(D.m, np.nan), D.dtype)
+    again = np.full(2, dt.UNTOUCHED)
+    torch.cuda.synchronize()
+    err = bhdense.csr_spmv_dots_raw_device(bh, D.m, D.n, D.nnz, D.d[2], D.d[0], D.d[1], alpha, dx, beta, dy, dz, dw, again)
+    assert err == 0, (what, err)
+    assert bool((dz[D.m:] == tiles.XSENT).all()), (what, "written past the end of z")
+    assert np.array_equal(spmvt.bits(dz[:D.m].cpu().numpy()), spmvt.bits(z)) and np.array_equal(spmvt.bits(again), spmvt.bits(dots)), what
+    return stats(bh)
+
+
+def test_long_rows_spmv_dots(hd):
+    """spmv_long as dots_run launches it, on the queues of its own workspace: z = 2 A x - y out of place and in place, with
+    the bits of the plain product, and both reductions exact"""
+    bh, dtype, build = hd
+    m, n, A = gp.long_rows(num_cu())
+    x, _, y, _, _ = gp.long_vectors(num_cu())
+    w, zz, wz = gp.long_dots(num_cu())
+    want = gp.long_references(num_cu())["spmv"][:, 0]
+    D = spmvt.Dev(m, n, A, dtype)
+    for in_place in (False, True):
+        z, dots, plain = dt.call(bh, D, x[:, 0], 2.0, -1.0, y[:, 0], w, in_place)
+        assert np.array_equal(spmvt.bits(z), spmvt.bits(plain)), in_place
+        exactly(z, want, ("2 A x - y beside its reductions", in_place))
+        assert dots[0] == zz and dots[1] == wz, (in_place, dots, zz, wz)
+        long_reached(bh, build, "spmv_long")                          # (the plain product's)
+    got = fused_records(bh, D, x[:, 0], 2.0, -1.0, y[:, 0], w, z, dots, "long rows")
+    assert got["dots_part"]["rows"] == m and got["dots_finish"]["rows"] == -(-m // gp.DOT_PER)
+    long_reached(bh, build, "spmv_long")                              # (the fused call's)
+
+
+# ---------------------------------------------------------------- C: the partials of the fused reductions
+def test_dots_finish_second_turn(hd):
+    """k_dot_finish adds 257 partials, thread 0 those of workgroups 0 and 256, the last from a partial workgroup whose share
+    in both sums is not zero; then two partials on the same handle, with the 255 stale ones behind them"""
+    bh, dtype, build = hd
+    for m, nparts in ((gp.DOTS_M, gp.DOT_TURN + 1), (gp.DOTS_M_AFTER, 2)):
+        A, x, y, w, want, zz, wz = gp.dots_case(m)
+        assert -(-m // gp.DOT_PER) == nparts and m % gp.DOT_PER != 0
+        D = spmvt.Dev(m, m, A, dtype)
+        z, dots, plain = dt.call(bh, D, x, 1.0, 1.0, y, w)
+        assert np.array_equal(spmvt.bits(z), spmvt.bits(plain)), m
+        exactly(z, want, ("A x + y", m))
+        assert dots[0] == zz and dots[1] == wz, (m, dots, zz, wz)
+        got = fused_records(bh, D, x, 1.0, 1.0, y, w, z, dots, ("dots", m))
+        assert got["dots_finish"]["rows"] == nparts and got["dots_part"]["rows"] == m, (m, got["dots_finish"], got["dots_part"])
+        print("%s dots_finish: %d partials over %d threads" % (build, got["dots_finish"]["rows"], gp.DOT_TURN))

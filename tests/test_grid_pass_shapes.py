@@ -2,8 +2,10 @@
 graph input gets the lanes a row it is listed under and a block count between 1.25 and 2 times the cap of 16 workgroups a CU
 with a partial last block, has several components, and its references take several rounds and levels -- so that what a
 second turn of a block loop computes depends on the turn before; the long-row matrix has more long rows than 8 workgroups a
-CU, rows beyond the keys a workgroup sorts in LDS among them, and sums that both value types hold exactly.  The closed forms
-that stand in for a slow restatement are compared with it at a small size."""
+CU, rows beyond the keys a workgroup sorts in LDS among them, and sums that both value types hold exactly -- those of the
+relaxation's steps on its square pattern, of the sampled dense-dense product (whose sliced restatement is the unsliced one)
+and of the fused product's reductions too; the input of k_dot_finish's second turn has 257 partials, the last from a partial
+workgroup.  The closed forms that stand in for a slow restatement are compared with it at a small size."""
 import numpy as np
 import pytest
 
@@ -12,6 +14,7 @@ import gridpass as gp
 import gsref as gr
 import iluref as ir
 import scantiles as st
+import sddmmref as sd
 import selectref as sr
 
 CUS = (256, 64, 304)
@@ -101,6 +104,75 @@ def test_long_rows(numCU):
         assert np.array_equal(got[1][:want[0][-1]], want[1]) and np.array_equal(got[2][:want[0][-1]], want[2]), which
         kept = np.diff(got[0])[lens > gp.LONG]
         assert np.all(kept > 0.8 * lens[lens > gp.LONG]) if which == "most" else np.all(kept == spec.top_k), which
+
+
+def test_the_thresholds_of_the_relaxation_the_sampled_product_and_the_fused_dots():
+    """k_rx_long and k_sd_long get min(nq, 8 numCU) workgroups (rx_run, sd_run), as spmv_long does in dots_run; k_dot_part
+    makes a partial per 4096 elements and k_dot_finish's 256 threads add them 256 a turn: a second turn needs m > 1 048 576"""
+    assert (gp.CAP_B, gp.DOT_PER, gp.DOT_TURN, gp.DOT_TURN * gp.DOT_PER) == (8, 4096, 256, 1048576)
+    assert gp.DOTS_M == 1051672 and -(-gp.DOTS_M // gp.DOT_PER) == 257 == gp.DOT_TURN + 1 and gp.DOTS_M % gp.DOT_PER != 0
+    assert -(-gp.DOTS_M_AFTER // gp.DOT_PER) == 2
+    assert sorted({sd.tile(k) for k in gp.SDDMM_KS}) == [1, 2, 4, 16, 64] and max(gp.SDDMM_KS) > 64
+    assert set(gp.SDDMM_IN_PLACE_KS) <= set(gp.SDDMM_KS) and gp.SDDMM_IN_PLACE[1] != 0.0
+    for numCU in CUS:
+        assert gp.sizes(numCU)["long"] > gp.CAP_B * numCU
+
+
+@pytest.mark.parametrize("numCU", CUS)
+def test_long_rows_relaxation(numCU):
+    """the square pattern keeps every long row; no step of any case rounds in float32, x and d alike"""
+    m, _, (Ap, Aj, Ax) = gp.long_rows(numCU)
+    b, x, d = gp.relax_vectors(numCU)
+    for sparse in (False, True):
+        n, (Sp, Sj, Sx), diag = gp.long_square(numCU, sparse)
+        lens = np.diff(Sp)
+        assert n == gp.N_COLS == len(lens) == len(diag) and Sp[-1] == len(Sj) == len(Sx) and Sj is Aj
+        assert np.array_equal(lens[:m], np.diff(Ap)) and not lens[m:].any() and n > m
+        assert int((lens > gp.LONG).sum()) == gp.sizes(numCU)["long"] > gp.CAP_B * numCU
+        assert set(np.unique(diag).tolist()) == {1.0, 2.0, 4.0}
+        if sparse:
+            rows = np.repeat(np.arange(n), lens)
+            assert np.array_equal(np.bincount(rows[Sx != 0], minlength=n), np.minimum(lens, 4)) and set(np.unique(Sx).tolist()) == {-1.0, 0.0, 1.0}
+        else:
+            assert Sx is Ax
+    for case, (sparse, coef, with_d, zero) in gp.RELAX_CASES.items():
+        gx, gd = gp.relax_reference(numCU, case)
+        assert (gd is not None) == with_d and len(coef) in (1, 4) and sparse == (len(coef) > 1)
+        for v in (gx,) + ((gd,) if with_d else ()):
+            assert v.dtype == np.float64 and np.isfinite(v).all() and np.array_equal(v, v.astype(np.float32).astype(np.float64)), (numCU, case)
+        assert not np.array_equal(gx[m:], x[m:])                     # an empty row's x moves by c b / diag
+    assert np.array_equal(np.array(gp.RELAX_CASES["four steps"][1]), np.array(gp.RELAX_COEF))
+    print("%d CUs: max |x| %.1f after the full step, %.1f after the four sparse ones" % (
+        numCU, np.abs(gp.relax_reference(numCU, "one step")[0]).max(), np.abs(gp.relax_reference(numCU, "four steps")[0]).max()))
+
+
+@pytest.mark.parametrize("numCU", CUS)
+def test_long_rows_sampled_product_and_reductions(numCU):
+    m, n, (Ap, Aj, Ax) = gp.long_rows(numCU)
+    k, rows = 65, 40
+    X, Y = gp.sddmm_dense(numCU, k)
+    assert X.shape == (m, k) and Y.shape == (n, k) and np.abs(np.r_[X.ravel(), Y.ravel()]).max() == 4
+    alpha, beta = gp.SDDMM_IN_PLACE
+    head = (Ap[:rows + 1], Aj[:Ap[rows]], Ax[:Ap[rows]])
+    assert int((np.diff(head[0]) > gp.LONG).sum()) >= 20
+    sliced = gp.sddmm_sliced(rows, n, head, X[:rows], Y, alpha, beta, True, rows=16)      # 16 + 16 + 8 rows
+    whole = sd.sddmm(rows, n, head[0], head[1], head[2], X[:rows], Y, alpha, beta, head[2], True)
+    assert sd.same_bits(sliced, whole) and np.abs(whole).max() < 2.0 ** 24 and np.array_equal(whole, np.round(whole))
+    r = np.repeat(np.arange(rows), np.diff(head[0]))
+    s = np.einsum("ij,ij->i", X[r], Y[head[1]])
+    assert np.array_equal(whole, 2.0 * s * head[2] - head[2]) and np.mean(whole != head[2]) > 0.5   # (a row done twice: m instead)
+    assert k * 16 * 4 * 2 + 4 < 2 ** 24                              # the bound of any entry at any of the widths
+    # the reductions of the fused product: z = 2 A x - y on the long rows, and section C's
+    w, zz, wz = gp.long_dots(numCU)
+    z = gp.long_references(numCU)["spmv"][:, 0]
+    assert len(w) == m == len(z) and np.abs(w).max() == 9 and np.abs(z).max() < 2 ** 19
+    assert 0 < zz < 2 ** 53 and abs(wz) < 2 ** 53 and zz == int((z * z).sum()) and wz == int((w * z).sum())
+    if numCU == CUS[0]:                                              # (it does not depend on the CU count)
+        for mm in (gp.DOTS_M, gp.DOTS_M_AFTER):
+            A, x, y, w, z, zz, wz = gp.dots_case(mm)
+            assert len(z) == mm and np.array_equal(np.sort(A[1]), np.arange(mm)) and np.abs(z).max() <= 9 and 0 < zz < 2 ** 27
+            assert wz == int((w * z).sum()) and zz == int((z * z).sum())
+    print("%d CUs, reference CPU seconds: %s" % (numCU, {k_: round(v, 2) for k_, v in sorted(gp.SECONDS.items())}))
 
 
 def test_closed_forms_are_the_restatements():
