@@ -55,6 +55,9 @@ BHS_SCALE_LEFT_DIV, BHS_SCALE_RIGHT_DIV = 1, 2
 # bhs_csr_sddmm_device (include/bhsparse_hip.h, "sampled dense-dense product")
 BHS_SDDMM_TIMES_M = 1
 
+# bhs_csr_fsai_device (include/bhsparse_hip.h, "approximate inverse")
+BHS_FSAI_MAX_ROW = 128
+
 # bhs_csr_spmv_semiring_device / bhs_csr_spmm_semiring_device (include/bhsparse_hip.h, "semiring CSR x dense")
 BHS_MV_ACCUM, BHS_MV_MASK_COMPLEMENT = 1, 2
 
@@ -132,6 +135,7 @@ SYMBOLS = {
                                  C.POINTER(C.c_double)]),
     "bhs_csr_sddmm_device": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _i, C.c_double, _vp, C.c_longlong, _vp, C.c_longlong, C.c_double,
                                   _vp, C.c_uint, C.POINTER(C.c_double)]),
+    "bhs_csr_fsai_device": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, C.POINTER(_i), C.POINTER(C.c_double)]),
     "bhs_csr_spmv_semiring_device": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, C.POINTER(C.c_longlong),
                                           C.POINTER(C.c_double)]),
     "bhs_csr_spmm_semiring_device": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp, C.c_longlong, _i, _vp, C.c_longlong, _vp,

@@ -17,6 +17,9 @@ of rho(D^-1 A) (spectral_radius_device, cheby_setup_device), and the cycle and P
 profiles/relax_case.md).
 Beside it: the level sets of a triangle, the sparse triangular solve and ILU(0) in place (bhs_csr_levels_device, bhs_csr_trsv_device, bhs_csr_ilu0_device; "triangular solve and ILU(0)") and CG
 preconditioned with that factorisation in natural or colour order (ilu0_pcg_device).
+And a preconditioner without any sequential dependence: the factorised sparse approximate inverse G on tril(A) or a caller's
+pattern (bhs_csr_fsai_device; "approximate inverse": fsai_device, fsai_setup_device), applied as two products z = G^T (G r)
+(fsai_apply_device), and CG with it (fsai_pcg_device; profiles/fsai_case.md).
 
 Everything is a torch tensor on the handle's GPU: a matrix is (rowPtr int32, colInd int32, val), a pattern the first two.
 Functions of handles, not methods.  Every step is a thin call into the C-ABI; a missing library raises, nothing is computed
@@ -951,19 +954,18 @@ def ilu0_apply_device(bh, M, r, z):
     return z
 
 
-def ilu0_pcg_device(bh, A, b, tol=1e-8, maxiter=100, ordering="colour"):
-    """Conjugate gradients for A x = b from x = 0, preconditioned with ILU(0) of A in the given ordering
-    (ilu0_setup_device, ilu0_apply_device), until ||r|| <= tol ||b|| or maxiter iterations.  The products with A are
-    csr_spmv_device, the dot products and updates torch's.  Returns (x, iterations, residual norms) as pcg_device does."""
+def _pcg_with(bh, A, b, tol, maxiter, apply):
+    """Conjugate gradients for A x = b from x = 0 with z = apply(r, z) as the preconditioner, until ||r|| <= tol ||b|| or
+    maxiter iterations: the loop ilu0_pcg_device and fsai_pcg_device share.  The products with A are csr_spmv_device, the
+    dot products and updates torch's.  Returns (x, iterations, residual norms)."""
     import torch
     n = _rows(A)
-    M = ilu0_setup_device(bh, A, ordering)
     x = torch.zeros_like(b)
     r = b.clone()
     res = [float(torch.linalg.norm(r))]
     p, rz, its = None, 0.0, 0
     while res[-1] > tol * res[0] and its < maxiter:
-        z = ilu0_apply_device(bh, M, r, torch.empty_like(r))
+        z = apply(r, torch.empty_like(r))
         rz_new = float(torch.dot(r, z))
         p = z if p is None else z + (rz_new / rz) * p
         rz = rz_new
@@ -974,3 +976,70 @@ def ilu0_pcg_device(bh, A, b, tol=1e-8, maxiter=100, ordering="colour"):
         res.append(float(torch.linalg.norm(r)))
         its += 1
     return x, its, res
+
+
+def ilu0_pcg_device(bh, A, b, tol=1e-8, maxiter=100, ordering="colour"):
+    """Conjugate gradients for A x = b from x = 0, preconditioned with ILU(0) of A in the given ordering
+    (ilu0_setup_device, ilu0_apply_device), until ||r|| <= tol ||b|| or maxiter iterations.  The products with A are
+    csr_spmv_device, the dot products and updates torch's.  Returns (x, iterations, residual norms) as pcg_device does."""
+    M = ilu0_setup_device(bh, A, ordering)
+    return _pcg_with(bh, A, b, tol, maxiter, lambda r, z: ilu0_apply_device(bh, M, r, z))
+
+
+# ---------------------------------------------------------------- approximate inverse
+def fsai_raw_device(bh, n, nnzA, d_rowPtrA, d_colIndA, d_valA, nnzG, d_rowPtrG, d_colIndG, d_valG, flags):
+    """bhs_csr_fsai_device on caller-given arrays, the C arguments in order (include/bhsparse_hip.h, "approximate inverse"):
+    the status code; sets bh.fsai_ms and bh.fsai_bad_row (the smallest row with a pivot that is not positive and finite, or
+    -1) on success."""
+    if bh._h is None:
+        return _lib.BHS_ERR_NOT_READY
+    bad, ms = C.c_int(-1), C.c_double(0)
+    err = bh._lib.bhs_csr_fsai_device(bh._h, int(n), int(nnzA), _ptr(d_rowPtrA), _ptr(d_colIndA), _ptr(d_valA), int(nnzG),
+                                      _ptr(d_rowPtrG), _ptr(d_colIndG), _ptr(d_valG), int(flags), C.byref(bad), C.byref(ms))
+    if err == _lib.BHS_SUCCESS:
+        bh.fsai_ms, bh.fsai_bad_row = float(ms.value), int(bad.value)
+    return err
+
+
+def fsai_device(bh, A, pattern=None):
+    """The factorised sparse approximate inverse of the SPD matrix A = (rowPtr, colInd, val), rows strictly ascending: the
+    lower-triangular G with G A G^T ~ I on `pattern` = (rowPtr, colInd) -- rows strictly ascending, each ending in its
+    diagonal, at most BHS_FSAI_MAX_ROW entries --, by default the pattern of tril(A) (csr_select_device with the band
+    col - row <= 0, no values).  Returns (rowPtrG, colIndG, valG); bh.fsai_bad_row is the smallest row with a bad pivot or
+    -1, bh.fsai_ms the device time.  Raises BhsparseError on failure."""
+    import torch
+    n = _rows(A)
+    if pattern is None:
+        Gp, Gj, _ = bh.csr_select_device(n, n, A, select_spec(band=(None, 0)), values=False)
+    else:
+        Gp, Gj = pattern[0], pattern[1]
+    nnzG = Gj.numel()
+    Gx = _alloc(nnzG, A[2].dtype, A[0].device)
+    torch.cuda.synchronize()                           # the library works on its own stream (see facade.initData_device)
+    _check(fsai_raw_device(bh, n, A[1].numel(), A[0], A[1], A[2], nnzG, Gp, Gj, Gx, 0), "bhs_csr_fsai_device")
+    return Gp, Gj, Gx[:nnzG]
+
+
+def fsai_setup_device(bh, A, pattern=None):
+    """The FSAI preconditioner of A (fsai_device) with its transpose (csr_transpose_device).  Returns what fsai_apply_device
+    needs: a dict with "G" and "Gt" (rowPtr, colInd, val) and "bad_row"."""
+    n = _rows(A)
+    G = fsai_device(bh, A, pattern)
+    bad_row = bh.fsai_bad_row
+    Tp, Tj, Tx, _ = bh.csr_transpose_device(n, n, G)
+    return {"G": G, "Gt": (Tp, Tj, Tx), "bad_row": bad_row}
+
+
+def fsai_apply_device(bh, M, r, z):
+    """z = G^T (G r) for M of fsai_setup_device: two products (csr_spmv_device), nothing sequential.  Returns z."""
+    n = r.numel()
+    y = csr_spmv_device(bh, n, n, M["G"], r)
+    return csr_spmv_device(bh, n, n, M["Gt"], y, y=z)
+
+
+def fsai_pcg_device(bh, A, b, tol=1e-8, maxiter=100, pattern=None):
+    """Conjugate gradients for A x = b from x = 0, preconditioned with the factorised sparse approximate inverse of A on
+    `pattern` (fsai_setup_device, fsai_apply_device; None: tril(A)), until ||r|| <= tol ||b|| or maxiter iterations.
+    Returns (x, iterations, residual norms) as ilu0_pcg_device does."""
+    M = fsai_setup_device(bh, A, pattern)
+    return _pcg_with(bh, A, b, tol, maxiter, lambda r, z: fsai_apply_device(bh, M, r, z))

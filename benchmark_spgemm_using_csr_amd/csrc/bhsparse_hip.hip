@@ -412,6 +412,8 @@ struct bhs_handle {
     SideWs mvWs;
     // the sampled dense-dense product (bhs_host_sddmm.inc.h): the same queues (2 x m ints), no counts
     SideWs sdWs;
+    // the approximate inverse (bhs_host_fsai.inc.h): the queues of the rows beyond its short bin (2 x n ints), no counts
+    SideWs fsWs;
     // semiring CSR x dense (bhs_host_spmv_sr.inc.h): the same queues; its control block also holds the 64-bit count of changed elements
     SideWs srmvWs;
     // sparse frontier x CSR (bhs_host_push_sr.inc.h): the row map and the changed elements' bits in its queue buffer, the
@@ -624,6 +626,7 @@ inline int one_launch(int rc) { return rc != BHS_SUCCESS ? rc : 1; }
 #include "bhs_host_assemble.inc.h"
 #include "bhs_host_relax.inc.h"
 #include "bhs_host_sddmm.inc.h"
+#include "bhs_host_fsai.inc.h"
 #include "bhs_host_transpose.inc.h"
 #include "bhs_host_reduce.inc.h"
 #include "bhs_host_semiring.inc.h"

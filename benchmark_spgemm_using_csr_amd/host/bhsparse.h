@@ -105,6 +105,16 @@ public:
                          const index_type *d_colIndM, int k, double alpha, const value_type *d_X, long long ldX,
                          const value_type *d_Y, long long ldY, double beta, value_type *d_valZ, unsigned flags);
 
+    // EXTENSION, not part of the reference's API: the factorised sparse approximate inverse (bhs_csr_fsai_device,
+    // include/bhsparse_hip.h, "approximate inverse") on DEVICE arrays: the values of the lower-triangular G on the caller's
+    // pattern (rows strictly ascending, ending in the diagonal, at most BHS_FSAI_MAX_ROW entries) with (G A G^T)_ii = 1 for
+    // the n x n matrix A, of which the lower triangle is read; d_valG, nnzG values, overlaps no input.  *bad_row (may be 0):
+    // the smallest row with a pivot that is not positive and finite, or -1.  The bits of a value are those of a host loop
+    // in the rule's order.  Needs initPlatform only; does not disturb the data of initData or get_C's result.
+    int csr_fsai_device(int n, int nnzA, const index_type *d_rowPtrA, const index_type *d_colIndA, const value_type *d_valA,
+                        int nnzG, const index_type *d_rowPtrG, const index_type *d_colIndG, value_type *d_valG, int flags,
+                        int *bad_row);
+
     // EXTENSION, not part of the reference's API: polynomial relaxation and the product with its reductions
     // (bhs_csr_relax_device, bhs_csr_spmv_dots_device, bhs_chebyshev_coefficients; include/bhsparse_hip.h, "relaxation and
     // fused products") on DEVICE arrays.  csr_relax_device: `steps` sweeps on the n x n matrix A in one call, coef a HOST
@@ -405,6 +415,14 @@ inline int bhsparse::csr_sddmm_device(int m, int n, int nnzM, const value_type *
 {
     if (!_h) return BHS_ERR_NOT_READY;
     return bhs_csr_sddmm_device(_h, m, n, nnzM, d_valM, d_rowPtrM, d_colIndM, k, alpha, d_X, ldX, d_Y, ldY, beta, d_valZ, flags, 0);
+}
+
+inline int bhsparse::csr_fsai_device(int n, int nnzA, const index_type *d_rowPtrA, const index_type *d_colIndA,
+                                     const value_type *d_valA, int nnzG, const index_type *d_rowPtrG,
+                                     const index_type *d_colIndG, value_type *d_valG, int flags, int *bad_row)
+{
+    if (!_h) return BHS_ERR_NOT_READY;
+    return bhs_csr_fsai_device(_h, n, nnzA, d_rowPtrA, d_colIndA, d_valA, nnzG, d_rowPtrG, d_colIndG, d_valG, flags, bad_row, 0);
 }
 
 inline int bhsparse::csr_relax_device(int n, int nnzA, const value_type *d_valA, const index_type *d_rowPtrA,

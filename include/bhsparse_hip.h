@@ -734,6 +734,56 @@ BHS_API int bhs_csr_sddmm_device(bhs_handle *h, int m, int n, int nnzM,
         double beta, bhs_value_t *d_valZ /* nnzM, in/out */,
         unsigned flags /* BHS_SDDMM_TIMES_M or 0 */, double *ms_out /* may be NULL */);
 
+/* ---- approximate inverse --------------------------------------------------
+ * The factorised sparse approximate inverse of a symmetric positive definite matrix (FSAI, Kolotilina and Yeremin): the
+ * values of a lower-triangular G on a pattern the caller gives, with G A G^T ~ I and (G A G^T)_ii = 1 -- a preconditioner
+ * that is applied as z = G^T (G r), two calls of bhs_csr_spmv_device, without levels, colours or any other sequential
+ * dependence, and is symmetric for CG; no reference counterpart; bhs_fsai.hip.h.  G^T comes from
+ * bhs_csr_transpose_device, the patterns tril(A) or a band of it from the entry selection.
+ * A: n x n, 0-based int32 CSR.  Entries of A with column > row are never used: the caller may pass A or tril(A).  Of a row
+ *   of A that is read, the entries up to and including the first whose column is >= the row must be strictly ascending
+ *   with columns in [0, n); what lies behind that entry is not looked at.
+ * The pattern of G (the caller's; n rows, nnzG entries): row i has d_i >= 1 entries J = (j_0 < .. < j_(d-1)), strictly
+ *   ascending, with j_(d-1) = i and d_i <= BHS_FSAI_MAX_ROW.  It need not lie inside A's.
+ * The matrix of a row, M (d x d, its lower triangle only): for q <= p, M_pq = double(the entry of A's row j_p with column
+ *   j_q), +0 where row j_p holds none.
+ * Arithmetic: all of it in double with FMA contraction OFF and true divisions (no reciprocal), so that a host loop (or
+ *   numpy) restates it bit for bit.  This order is the contract:
+ *   1. For c = 0 .. d-1: l_cc = sqrt(m_cc); l_rc = m_rc / l_cc for r > c; m_rc' = m_rc' - l_rc * l_c'c for every
+ *      c < c' <= r (the product rounded, then the difference).  Every element takes its updates in ascending c.
+ *   2. t = e_(d-1), the unit vector of the last position.  For q = d-1 .. 0: g_q = t_q / l_qq; t_p = t_p - l_qp * g_q for
+ *      every p < q (the product rounded, then the difference).
+ *   3. valG[rowPtrG[i] + p] = bhs_value_t(g_p): ONE rounding.
+ *   So L^T g = e_d: row i of G is the last row of the inverse Cholesky factor of A(J, J).
+ * Pivots: *bad_row_out (may be NULL) is the smallest row in which some m_cc is not > 0 or not finite when its root is
+ *   taken, or -1.  The call still returns BHS_SUCCESS and the values follow IEEE, as with pivot_out of
+ *   bhs_csr_ilu0_device; other rows are unaffected.
+ * The call is synchronous on the handle's stream, needs no bound data (it works on a handle straight after bhs_create),
+ * returns BHS_ERR_INVALID_ARG between bhs_spgemm_symbolic and bhs_spgemm_finish, and leaves the handle as it was:
+ * counters, queues (2 n ints), events and the pinned mirror are buffers of its own from the grow-only pool; C of the last
+ * multiply, a served sum or selection, "class_state", the speculative-launch figures and every option stay.  ms_out (may
+ * be NULL): device time of the call, validation included.  n == 0 succeeds and launches nothing.
+ * Reproducibility: the values are a function of the arguments -- the same bits from call to call and from handle to
+ *   handle, whatever kernel family serves a row.  No atomics on an output.
+ * Validation: on the device, each check ahead of the dependent read.  rowPtrG[0] != 0, a decreasing rowPtrG,
+ *   rowPtrG[n] != nnzG; a row of G that is empty, longer than BHS_FSAI_MAX_ROW, not strictly ascending, with a column
+ *   outside [0, i] or not ending in i; bounds of a row of A that is read outside [0, nnzA] or decreasing; an entry of the
+ *   examined part of such a row that is not above its predecessor or outside [0, n): BHS_ERR_INVALID_ARG, after which
+ *   d_valG[0, nnzG) is unspecified.  Nothing is ever written outside it.
+ *   On the host: a NULL handle, negative sizes, flags != 0, a NULL array with n > 0, nnzG < n, or d_valG's nnzG values
+ *   overlapping an input return BHS_ERR_INVALID_ARG with d_valG untouched.
+ * Rows are binned by d; bhs_get_kernel_stats then reports the families fsai_short (every row in order: the validation of
+ *   G, the rows of d <= 16, 16 lanes each), fsai_wave (17 <= d <= 64, a wave each) and fsai_long (65 <= d <= 128, a
+ *   workgroup each); a family without rows is not launched.  One round trip for the queues' lengths, and only when
+ *   nnzG > 16.  M lies packed in LDS (136, 2080 or 8256 doubles a row); grids are not capped: a row's work is bounded by
+ *   its 128 unknowns.                                                                                                  */
+#define BHS_FSAI_MAX_ROW 128
+BHS_API int bhs_csr_fsai_device(bhs_handle *h, int n, int nnzA,
+        const int *d_rowPtrA, const int *d_colIndA, const bhs_value_t *d_valA,
+        int nnzG, const int *d_rowPtrG, const int *d_colIndG /* the pattern of G, the caller's */,
+        bhs_value_t *d_valG /* out: nnzG values */,
+        int flags /* must be 0 */, int *bad_row_out /* may be NULL */, double *ms_out /* may be NULL */);
+
 /* ---- relaxation and fused products ----------------------------------------
  * What a multigrid cycle and a Krylov iteration do between two setups, as library calls with every array on the device
  * (no reference counterpart; bhs_relax.hip.h): `steps` sweeps of a polynomial smoother in one call -- weighted Jacobi, or
