@@ -433,6 +433,9 @@ struct bhs_handle {
     // the connected components (bhs_host_components.inc.h): the root bitmap and the scanned offsets in its queue buffer, the
     // roots per bitmap word in its count buffer
     SideWs ccWs;
+    // the strongly connected components (bhs_host_scc.inc.h): part, stamp and reach, then the root bitmap and the scanned
+    // offsets in its queue buffer, the roots per bitmap word in its count buffer
+    SideWs sccWs;
     // the matching (bhs_host_match.inc.h): the leader bitmap, the scanned offsets and the rounds' candidates in its queue
     // buffer, the leaders per bitmap word in its count buffer
     SideWs mtWs;
@@ -627,6 +630,7 @@ inline int one_launch(int rc) { return rc != BHS_SUCCESS ? rc : 1; }
 #include "bhs_host_relax.inc.h"
 #include "bhs_host_sddmm.inc.h"
 #include "bhs_host_fsai.inc.h"
+#include "bhs_host_scc.inc.h"
 #include "bhs_host_transpose.inc.h"
 #include "bhs_host_reduce.inc.h"
 #include "bhs_host_semiring.inc.h"

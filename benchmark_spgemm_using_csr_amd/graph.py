@@ -15,6 +15,10 @@ components_* answer which vertices belong together, for all components at once a
 (bhs_csr_components_device; "connected components"): the passes grow like the logarithm of the diameter, not like the
 diameter.
 
+scc_* answer the question about the DIRECTION of the entries: the strongly connected components (bhs_csr_scc_device;
+"strongly connected components"), by trimming and forward-backward rounds; condensation_device is the DAG of the SCCs,
+largest_scc_csr the submatrix of the largest one.
+
 spanning_forest_* give the minimum or maximum spanning forest of the weighted graph (bhs_csr_spanning_forest_device;
 "spanning forest"), unique for any input, in at most log2 n Boruvka rounds; single_linkage_device cuts its heaviest edges
 and calls the components on the rest."""
@@ -296,12 +300,79 @@ def largest_component_csr(n, Ap, Aj, Ax, value_dtype=np.float64, device=0):
     size, ties to the smaller root.  Returns (vertices int32[size] ascending, (Zp, Zj, Zx)): Z = A(vertices, vertices)
     through facade.extract_csr."""
     _, comp, sizes = components_csr(n, Ap, Aj, device=device)
+    return _largest_csr(n, Ap, Aj, Ax, comp, sizes, value_dtype, device)
+
+
+def _largest_csr(n, Ap, Aj, Ax, comp, sizes, value_dtype, device):
+    """(vertices, (Zp, Zj, Zx)) of the component of greatest size, numbered as comp and sizes have them"""
     if n == 0:
         return np.zeros(0, np.int32), (np.zeros(1, np.int32), np.zeros(0, np.int32), np.zeros(0, value_dtype))
     c = int(np.argmax(sizes))                                         # (the first of equal sizes: components are numbered by ascending root)
     vertices = np.flatnonzero(comp == c).astype(np.int32)
     Zp, Zj, Zx, _ = extract_csr(n, n, Ap, Aj, Ax, rows=vertices, cols=vertices, value_dtype=value_dtype, device=device)
     return vertices, (Zp, Zj, Zx)
+
+
+# ---------------------------------------------------------------- strongly connected components
+def scc_raw_device(bh, n, nnz, dAp, dAj, flags, root, comp, size):
+    """bhs_csr_scc_device on caller-given arrays, the C arguments in order (comp and size may be None): the status code,
+    BHS_ERR_NOT_READY without a platform; sets bh.scc_nscc, bh.scc_rounds (a function of the pattern), bh.scc_passes (the
+    passes depend on timing) and bh.scc_ms on success only."""
+    if bh._h is None:
+        return _lib.BHS_ERR_NOT_READY
+    nscc, rounds, passes, ms = C.c_int(0), C.c_int(0), C.c_int(0), C.c_double(0)
+    err = bh._lib.bhs_csr_scc_device(bh._h, int(n), int(nnz), _ptr(dAp), _ptr(dAj), int(flags), _ptr(root), _ptr(comp), _ptr(size),
+                                     C.byref(nscc), C.byref(rounds), C.byref(passes), C.byref(ms))
+    if err == _lib.BHS_SUCCESS:
+        bh.scc_nscc, bh.scc_rounds, bh.scc_passes, bh.scc_ms = int(nscc.value), int(rounds.value), int(passes.value), float(ms.value)
+    return err
+
+
+def scc_device(bh, n, A):
+    """The strongly connected components of the n-vertex pattern A = (rowPtr, colInd[, anything]), torch tensors on the
+    handle's GPU: an entry (i, j) is a directed edge (which way it points does not matter: a graph and its reverse have the
+    same SCCs); values are not taken.  Returns (root int32[n], comp int32[n], sizes int32[nscc]) as device tensors: the
+    smallest vertex of i's SCC, the SCC's number by ascending root, and the SCCs' sizes.  bh.scc_nscc, bh.scc_rounds,
+    bh.scc_passes and bh.scc_ms hold the count, the rounds, the passes and the device time.  Raises BhsparseError on failure."""
+    import torch
+    Ap, Aj = A[0], A[1]
+    root, comp, size = (_alloc(n, torch.int32, Ap.device) for _ in range(3))
+    torch.cuda.synchronize()                           # the library works on its own stream (see facade.initData_device)
+    _check(scc_raw_device(bh, n, Aj.numel(), Ap, Aj if Aj.numel() else None, 0, root, comp, size), "bhs_csr_scc_device")
+    return root[:n], comp[:n], size[:bh.scc_nscc]
+
+
+def scc_csr(n, Ap, Aj, device=0):
+    """Convenience: scc_device once on host CSR arrays.  Returns numpy (root int32[n], comp int32[n], sizes int32[nscc])."""
+    A = _device_csr(Ap, Aj, None, np.float64, device)
+    with _handle(np.float64, device, None) as bh:
+        return _host(*scc_device(bh, n, A))
+
+
+def condensation_device(bh, n, A, comp, nscc):
+    """The condensation of the n-vertex pattern A = (rowPtr, colInd[, anything]) under scc_device's comp: the DAG of the
+    SCCs as a device CSR (rowPtr int32[nscc + 1], colInd, val) of nscc x nscc.  Its triplets are (comp[i], comp[j]) over the
+    entries (i, j) whose ends have different numbers, assembled by assemble.coo_assemble_device with "sum" on values of 1
+    in the handle's type: a value counts the entries of A between two SCCs.  The vertex lists of the SCCs are
+    component_lists_device(bh, n, comp, nscc)."""
+    import torch
+    from .assemble import coo_assemble_device
+    Ap, Aj = A[0], A[1]
+    lens = (Ap[1:n + 1] - Ap[:n]).to(torch.int64)
+    rows = torch.repeat_interleave(torch.arange(n, dtype=torch.int64, device=Ap.device), lens, output_size=Aj.numel())
+    ci, cj = comp[rows], comp[Aj.to(torch.int64)]
+    keep = ci != cj
+    ci, cj = ci[keep].contiguous(), cj[keep].contiguous()
+    vals = torch.ones(ci.numel(), dtype=torch.float32 if bh._vdt == np.dtype(np.float32) else torch.float64, device=Ap.device)
+    return coo_assemble_device(bh, nscc, nscc, ci, cj, vals, "sum")
+
+
+def largest_scc_csr(n, Ap, Aj, Ax, value_dtype=np.float64, device=0):
+    """Convenience: the largest strongly connected component of the n x n matrix (Ap, Aj, Ax) on host CSR arrays -- of the
+    greatest size, ties to the smaller root.  Returns (vertices int32[size] ascending, (Zp, Zj, Zx)): Z = A(vertices,
+    vertices) through facade.extract_csr."""
+    _, comp, sizes = scc_csr(n, Ap, Aj, device=device)
+    return _largest_csr(n, Ap, Aj, Ax, comp, sizes, value_dtype, device)
 
 
 # ---------------------------------------------------------------- spanning forest

@@ -199,6 +199,16 @@ public:
     int csr_components_device(int n, int nnzS, const index_type *d_rowPtrS, const index_type *d_colIndS, int flags,
                               index_type *d_root, index_type *d_comp, index_type *d_compSize, int *ncomp_out, int *passes_out);
 
+    // EXTENSION, not part of the reference's API: the strongly connected components of an n x n pattern S on DEVICE arrays
+    // (bhs_csr_scc_device; include/bhsparse_hip.h, "strongly connected components"); an entry (i, j) is a directed edge, and
+    // which way it points does not matter.  d_root (n ints) receives the smallest vertex of every vertex's SCC, d_comp (n
+    // ints, may be null) the SCC's number by ascending root, d_compSize (room for n ints, may be null, needs d_comp) the
+    // *nscc_out sizes; *rounds_out is a function of the pattern, *passes_out depends on timing.  flags must be 0.  Needs
+    // initPlatform only.
+    int csr_scc_device(int n, int nnzS, const index_type *d_rowPtrS, const index_type *d_colIndS, int flags,
+                       index_type *d_root, index_type *d_comp, index_type *d_compSize, int *nscc_out, int *rounds_out,
+                       int *passes_out);
+
     // EXTENSION, not part of the reference's API: heavy-edge matching of the vertices of an n x n matrix A on DEVICE arrays
     // (bhs_csr_match_device; include/bhsparse_hip.h, "matching").  d_valA may be null: every weight 1.  d_mate (n ints)
     // receives every vertex's partner, the vertex itself where it is unmatched; d_agg (n ints, may be null) the number of its
@@ -533,6 +543,14 @@ inline int bhsparse::csr_components_device(int n, int nnzS, const index_type *d_
 {
     if (!_h) return BHS_ERR_NOT_READY;
     return bhs_csr_components_device(_h, n, nnzS, d_rowPtrS, d_colIndS, flags, d_root, d_comp, d_compSize, ncomp_out, passes_out, 0);
+}
+
+inline int bhsparse::csr_scc_device(int n, int nnzS, const index_type *d_rowPtrS, const index_type *d_colIndS, int flags,
+                                    index_type *d_root, index_type *d_comp, index_type *d_compSize, int *nscc_out, int *rounds_out,
+                                    int *passes_out)
+{
+    if (!_h) return BHS_ERR_NOT_READY;
+    return bhs_csr_scc_device(_h, n, nnzS, d_rowPtrS, d_colIndS, flags, d_root, d_comp, d_compSize, nscc_out, rounds_out, passes_out, 0);
 }
 
 inline int bhsparse::csr_match_device(int n, int nnzA, const index_type *d_rowPtrA, const index_type *d_colIndA,

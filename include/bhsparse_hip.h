@@ -1033,6 +1033,70 @@ BHS_API int bhs_csr_interp_numeric_device(bhs_handle *h, int n, int nnzA,
         int *d_colIndP /* out: nnzP ints */, bhs_value_t *d_valP /* out: nnzP values */,
         int flags /* must be 0 */, double *ms_out /* may be NULL */);
 
+/* ---- strongly connected components ------------------------------------------
+ * Which vertices of a DIRECTED graph reach one another: i and j are in one strongly connected component (SCC) where a path
+ * leads from i to j and one from j to i -- irreducibility, the condensation DAG, the diagonal blocks of a block triangular
+ * form, "the giant component" (no reference counterpart; bhs_scc.hip.h).  bhs_csr_components_device joins i and j whichever way
+ * the entry points; this one answers the question about direction.
+ * S is an n x n pattern, 0-based int32 CSR; values are NOT TAKEN, so the double and the float library run the same code and
+ * give the same bits.  An entry (i, j) with j != i is a directed edge between i and j.  The SCCs of a graph and of its
+ * reverse are the same, so which way the edge points does not matter: the call needs no transpose, and S and its
+ * transpose give the same outputs.  Rows need not be sorted; repeated columns and self-loops change nothing.
+ * Definition.  root[i] is the smallest vertex index of i's SCC.  comp[i] is the rank of root[i] among the roots, of which
+ *   there are nscc: SCCs are numbered by ascending smallest vertex.  compSize[c] is the number of vertices with comp == c.
+ *   d_root, d_comp, d_compSize, *nscc_out AND *rounds_out are a function of the pattern alone: the same bits from run to
+ *   run, from handle to handle, and in the double and the float library.
+ * Rounds (trim, forward-backward).  Per vertex: part, the colour class the previous round left it in, -1 once it is
+ *   decided; a label, kept in d_root itself; a stamp and a reach flag.  An edge i -> j is valid in a round where j != i,
+ *   both ends are live and part[i] == part[j].  A round runs four phases, each to ITS FIXED POINT, which is unique --
+ *   that is why the rounds are a function of the pattern:
+ *   1. Trim.  A live vertex with no valid out-edge or no valid in-edge is an SCC by itself.  A pass is two launches: the
+ *      first stores the pass's stamp to stamp[j] over the valid edges (plain stores of one value: nothing is cleared, no
+ *      atomic), the second looks for a valid out-edge in the row and for the stamp, and decides in place.  Liveness only
+ *      falls.
+ *   2. Forward labels.  label[v] = v on the live vertices; then passes in place over the live rows: label[j] is lowered to
+ *      label[i] over the valid edges.  A word only ever falls: after the start every write is an atomic minimum, issued
+ *      only where the value read is greater, the shortcut label[i] <- label[label[i]] included (once a row; sound because
+ *      label[i] = u says that u reaches i inside the class).  At the fixed point label[v] is the smallest live vertex of
+ *      v's class that reaches v.
+ *   3. Backward reach.  The vertices with label[v] == v are reached; a pass pulls over the rows: a live i becomes reached
+ *      where some valid edge i -> j has label[j] == label[i] and j reached.  Flags only rise.
+ *   4. Decide.  A reached v is final with root[v] = label[v]: every member reaches the root and the root every member.
+ *      Every other live v goes to the class part[v] = label[v].
+ *   The smallest live vertex is always decided.  A round whose trim leaves no live vertex ends there and counts.
+ *   *rounds_out is the number of rounds; a round that decides nothing, or more than n + 1 rounds, is BHS_ERR_INTERNAL.
+ *   One-way rings that feed one another in ascending order take a round each; most inputs take one.
+ * Passes.  The host launches 8 passes of a phase per control round trip and ends the phase after a batch whose last pass
+ *   changed nothing; BHS_ERR_INTERNAL where a phase would need more than n + 1 passes.  *passes_out, the total of passes
+ *   launched, DEPENDS ON TIMING -- a pass in place sees what other workgroups wrote during it; nothing else does.
+ *   Nothing spins on the device, nothing waits for another workgroup.  The trim and the backward reach move one hop a
+ *   synchronous pass: deep symmetric grids and long one-way chains are where this call loses (profiles/scc_case.md).
+ * Outputs.  d_root: n ints.  d_comp (may be NULL): n ints in [0, nscc).  d_compSize (may be NULL, needs d_comp): CAPACITY n
+ *   ints, of which nscc are written.  *nscc_out is counted as the SCCs are decided: it is written with or without d_comp.
+ *   The numbering is the connected components': the root flags, the library's one-pass scan per 64 vertices, the ranks,
+ *   the sizes by integer atomic adds.  The vertices sorted by SCC are the stable transpose of the n x nscc membership
+ *   pattern, as there.
+ * Validation, on the device, each check ahead of the dependent read: rowPtrS[i] > rowPtrS[i+1] or either outside
+ *   [0, nnzS] (the row is taken as empty); a column outside [0, n) (never used as an index).  On the host: a NULL handle,
+ *   negative n or nnzS, flags != 0, a NULL d_rowPtrS or d_root with n > 0, NULL d_colIndS with nnzS > 0,
+ *   d_compSize without d_comp, an output's footprint overlapping S or another output, and a call between
+ *   bhs_spgemm_symbolic and bhs_spgemm_finish.  Each returns BHS_ERR_INVALID_ARG.  After a refusal by the device the
+ *   outputs are unspecified; nothing beyond their stated sizes is ever written, and nothing stays queued.
+ * n == 0 succeeds with *nscc_out = 0, *rounds_out = 0 and *passes_out = 0 and launches nothing.
+ * Synchronous on the handle's stream, needs no bound data, leaves the handle as it was (a workspace of its own).  ms_out
+ *   (may be NULL): device time of the call, the round trips included.  bhs_get_kernel_stats then reports scc_trim (two
+ *   launches a pass), scc_forward and scc_backward (a start and the passes, a round), scc_decide (one a round) and, where
+ *   d_comp is given, scc_number; a row is spread over 1, 4, 16 or 64 lanes by the pattern's mean row length.           */
+BHS_API int bhs_csr_scc_device(bhs_handle *h, int n, int nnzS,
+        const int *d_rowPtrS, const int *d_colIndS /* n x n pattern; values are not taken */,
+        int flags /* must be 0 */,
+        int *d_root     /* out: n ints: the smallest vertex of i's SCC */,
+        int *d_comp     /* out, may be NULL: n ints in [0, nscc), SCCs numbered by ascending root */,
+        int *d_compSize /* out, may be NULL, needs d_comp: CAPACITY n, nscc written */,
+        int *nscc_out /* may be NULL */, int *rounds_out /* may be NULL */,
+        int *passes_out /* may be NULL; depends on timing */,
+        double *ms_out /* may be NULL */);
+
 /* ---- spanning forest --------------------------------------------------------
  * The minimum (or maximum) spanning forest of the graph that an n x n matrix A stores, by Boruvka rounds on the device: for
  * network design, as the spanning tree under a support-graph or tree preconditioner (the MAXIMUM forest of |a_ij| is the
