@@ -940,6 +940,19 @@ def ilu0_setup_device(bh, A, ordering="natural", seed=0):
     return {"LU": LU, "lower": lower, "upper": upper, "perm": perm, "ncolors": ncolors, "pivot": getattr(bh, "ilu0_pivot", -1)}
 
 
+def ilu0_setup_permuted_device(bh, A, perm):
+    """The ILU(0) preconditioner of A(perm, perm) for A = (rowPtr, colInd, val), rows strictly ascending, and a caller's
+    permutation (an int32 device tensor: perm[k] is the old index of new row k -- ordering.rcm_device's, for one).  The
+    same dict that ilu0_setup_device returns, so ilu0_apply_device serves unchanged; "ncolors" is 0."""
+    n = _rows(A)
+    A = _permuted_device(bh, n, A, perm)
+    LU = (A[0], A[1], A[2].clone())
+    lower = levels_device(bh, n, LU)
+    upper = levels_device(bh, n, LU, upper=True)
+    ilu0_device(bh, LU, lower)
+    return {"LU": LU, "lower": lower, "upper": upper, "perm": perm.long(), "ncolors": 0, "pivot": getattr(bh, "ilu0_pivot", -1)}
+
+
 def ilu0_apply_device(bh, M, r, z):
     """z = (L U)^-1 r for M of ilu0_setup_device: r permuted where M has a permutation, the unit lower solve, the upper solve
     in place, the result scattered back into z.  Returns z."""
@@ -983,6 +996,15 @@ def ilu0_pcg_device(bh, A, b, tol=1e-8, maxiter=100, ordering="colour"):
     (ilu0_setup_device, ilu0_apply_device), until ||r|| <= tol ||b|| or maxiter iterations.  The products with A are
     csr_spmv_device, the dot products and updates torch's.  Returns (x, iterations, residual norms) as pcg_device does."""
     M = ilu0_setup_device(bh, A, ordering)
+    return _pcg_with(bh, A, b, tol, maxiter, lambda r, z: ilu0_apply_device(bh, M, r, z))
+
+
+def ilu0_pcg_rcm_device(bh, A, b, tol=1e-8, maxiter=100):
+    """ilu0_pcg_device with ILU(0) of A in reverse Cuthill-McKee order: ordering.rcm_device (pseudo-peripheral starts) on
+    ordering.symmetric_pattern_device(A), ilu0_setup_permuted_device.  Returns (x, iterations, residual norms)."""
+    from .ordering import rcm_device, symmetric_pattern_device
+    n = _rows(A)
+    M = ilu0_setup_permuted_device(bh, A, rcm_device(bh, n, symmetric_pattern_device(bh, n, A)))
     return _pcg_with(bh, A, b, tol, maxiter, lambda r, z: ilu0_apply_device(bh, M, r, z))
 
 

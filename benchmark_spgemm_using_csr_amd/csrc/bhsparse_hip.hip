@@ -436,6 +436,10 @@ struct bhs_handle {
     // the strongly connected components (bhs_host_scc.inc.h): part, stamp and reach, then the root bitmap and the scanned
     // offsets in its queue buffer, the roots per bitmap word in its count buffer
     SideWs sccWs;
+    // the reverse Cuthill-McKee ordering (bhs_host_rcm.inc.h): the slots per root, the root bitmap and the call's int arrays in
+    // its queue buffer; the roots per bitmap word, the level order's table, a level's child counts and the components' sizes
+    // in its count buffer
+    SideWs rcmWs;
     // the matching (bhs_host_match.inc.h): the leader bitmap, the scanned offsets and the rounds' candidates in its queue
     // buffer, the leaders per bitmap word in its count buffer
     SideWs mtWs;
@@ -631,6 +635,7 @@ inline int one_launch(int rc) { return rc != BHS_SUCCESS ? rc : 1; }
 #include "bhs_host_sddmm.inc.h"
 #include "bhs_host_fsai.inc.h"
 #include "bhs_host_scc.inc.h"
+#include "bhs_host_rcm.inc.h"
 #include "bhs_host_transpose.inc.h"
 #include "bhs_host_reduce.inc.h"
 #include "bhs_host_semiring.inc.h"

@@ -209,6 +209,16 @@ public:
                        index_type *d_root, index_type *d_comp, index_type *d_compSize, int *nscc_out, int *rounds_out,
                        int *passes_out);
 
+    // EXTENSION, not part of the reference's API: the reverse Cuthill-McKee ordering of an n x n pattern S on DEVICE arrays
+    // (bhs_csr_rcm_device; include/bhsparse_hip.h, "bandwidth-reducing ordering").  S has strictly ascending rows and a
+    // symmetric structure, checked on the device.  d_perm (n ints) receives the old index of every new row; d_level (n ints,
+    // may be null) the final sweep's levels; d_start (room for n ints, may be null) the *ncomp_out starts.  *depth_out and
+    // *sweeps_out are functions of the pattern, *passes_out is a multiple of the batch and depends on timing.  flags:
+    // BHS_RCM_PERIPHERAL | BHS_RCM_NO_REVERSE.  Needs initPlatform only.
+    int csr_rcm_device(int n, int nnzS, const index_type *d_rowPtrS, const index_type *d_colIndS, int flags,
+                       index_type *d_perm, index_type *d_level, index_type *d_start, int *ncomp_out, int *depth_out,
+                       int *sweeps_out, int *passes_out);
+
     // EXTENSION, not part of the reference's API: heavy-edge matching of the vertices of an n x n matrix A on DEVICE arrays
     // (bhs_csr_match_device; include/bhsparse_hip.h, "matching").  d_valA may be null: every weight 1.  d_mate (n ints)
     // receives every vertex's partner, the vertex itself where it is unmatched; d_agg (n ints, may be null) the number of its
@@ -551,6 +561,15 @@ inline int bhsparse::csr_scc_device(int n, int nnzS, const index_type *d_rowPtrS
 {
     if (!_h) return BHS_ERR_NOT_READY;
     return bhs_csr_scc_device(_h, n, nnzS, d_rowPtrS, d_colIndS, flags, d_root, d_comp, d_compSize, nscc_out, rounds_out, passes_out, 0);
+}
+
+inline int bhsparse::csr_rcm_device(int n, int nnzS, const index_type *d_rowPtrS, const index_type *d_colIndS, int flags,
+                                    index_type *d_perm, index_type *d_level, index_type *d_start, int *ncomp_out, int *depth_out,
+                                    int *sweeps_out, int *passes_out)
+{
+    if (!_h) return BHS_ERR_NOT_READY;
+    return bhs_csr_rcm_device(_h, n, nnzS, d_rowPtrS, d_colIndS, flags, d_perm, d_level, d_start, ncomp_out, depth_out, sweeps_out,
+                              passes_out, 0);
 }
 
 inline int bhsparse::csr_match_device(int n, int nnzA, const index_type *d_rowPtrA, const index_type *d_colIndA,

@@ -1097,6 +1097,69 @@ BHS_API int bhs_csr_scc_device(bhs_handle *h, int n, int nnzS,
         int *passes_out /* may be NULL; depends on timing */,
         double *ms_out /* may be NULL */);
 
+/* ---- bandwidth-reducing ordering --------------------------------------------
+ * The reverse Cuthill-McKee (RCM) ordering of a symmetric pattern: a permutation that makes the matrix narrow -- ahead of
+ * ILU(0), of band and profile solvers, and to make SpMV on a shuffled mesh cache-friendly (symrcm, SPARSPAK's GENRCM; no
+ * reference counterpart; bhs_rcm.hip.h).
+ * S is an n x n pattern on the device, 0-based int32 CSR, rows STRICTLY ASCENDING, STRUCTURALLY SYMMETRIC.  Values are NOT
+ * TAKEN, so the double and the float library run the same code and give the same bits.  A diagonal entry is allowed and
+ * ignored.  deg(i) is the number of entries of row i with j != i; key(i) = (deg(i), i), compared lexicographically.
+ * Refusals by the device, each BHS_ERR_INVALID_ARG, found by the first kernel and read before anything else runs: a falling
+ *   row pointer, or nnzS != rowPtr[n]; a column outside [0, n); a row that is not strictly ascending (a repeated entry
+ *   included); an entry (i, j) without (j, i), found by a binary search in row j.  After a refusal nothing stays queued,
+ *   no output is promised, and nothing beyond the outputs' stated sizes is ever written.
+ * Refusals by the host, each BHS_ERR_INVALID_ARG: a NULL handle, a call between bhs_spgemm_symbolic and bhs_spgemm_finish,
+ *   negative n or nnzS, flags beyond BHS_RCM_PERIPHERAL | BHS_RCM_NO_REVERSE, a NULL d_rowPtrS or d_perm with n > 0, NULL
+ *   d_colIndS with nnzS > 0, an output's footprint overlapping S or another output.
+ * n == 0 succeeds with every count 0 and launches nothing.
+ * Components.  root(i) is the smallest vertex of i's connected component, comp(i) the component's number by ascending root
+ *   (the kernels of bhs_csr_components_device, under this call's own kernel record).
+ * Start of a component: s0, its vertex of smallest key.  With BHS_RCM_PERIPHERAL the George-Liu refinement runs as SPARSPAK's
+ *   FNROOT has it, for all components in lockstep.  A SWEEP is one breadth-first search from every component's current
+ *   start at once: it gives every vertex its level, and every component e, its greatest level, and x, the vertex of
+ *   smallest key on that level.  After sweep 0 every component's start moves to x.  After every later sweep a component
+ *   whose new e does not exceed its old e is DONE: it keeps the start the sweep ran from and this sweep's levels; any
+ *   other takes the new e, moves its start to x and sweeps again.  A done component's start no longer moves, so later
+ *   sweeps give it the same levels.  Without the flag there is one sweep.  *sweeps_out is the number of sweeps (with the flag
+ *   at least 2); BHS_ERR_INTERNAL after n + 1 sweeps.
+ * Cuthill-McKee, level by level.  pos of a start is its component's number.  A vertex v on level l >= 1 has the parent
+ *   p(v), its neighbour on level l - 1 of smallest pos.  Level l is ordered by (pos(p(v)), deg(v), v) and follows level
+ *   l - 1: the FOREST ORDER.  The CM order is the forest order stably regrouped by comp: components are contiguous and ascend
+ *   by root, and inside a component it is exactly the order of the serial queue algorithm in which a dequeued vertex
+ *   appends its unnumbered neighbours by ascending (deg, index).
+ * Outputs.  d_perm[k] is the OLD index of new row k: the CM order reversed as a whole, or the CM order itself under
+ *   BHS_RCM_NO_REVERSE; it is what bhs_csr_extract_device takes as rows and cols.  d_level (may be NULL): n ints, the final
+ *   sweep's levels.  d_start (may be NULL): CAPACITY n ints, d_start[c] the start of component c, ncomp written.
+ *   *depth_out is the greatest number of levels of a component.  d_perm, d_level, d_start, *ncomp_out, *depth_out and
+ *   *sweeps_out are a function of the pattern alone: the same bits from run to run, from handle to handle, and in the
+ *   double and the float library.  Only *passes_out is exempt: the passes launched, of the components' relaxation (which
+ *   DEPENDS ON TIMING) and of the sweeps, always A MULTIPLE OF THE BATCH of 8 passes a control round trip.
+ * How.  rcm_check: the degrees and the refusals.  rcm_components: the components.  rcm_level: a sweep's passes -- a pull:
+ *   an unvisited vertex with a neighbour on level cur takes cur + 1; a pass stores cur + 1 alone, so a racing read sees
+ *   "unvisited" or cur + 1, never cur: plain stores, unique levels; a sweep ends after a batch whose last pass reached
+ *   nothing.  rcm_far: per root a 64-bit atomic maximum of the level, a 64-bit atomic minimum of the key on that level,
+ *   the decision; one round trip a sweep.  rcm_order: the vertices by (level, index) and levelPtr, copied to the host once
+ *   (the colouring's order step; its table of depth x ceil(n / 64) counts is limited to 2^26: very deep AND very large
+ *   graphs return BHS_ERR_ALLOC).  rcm_number: a launch sequence per level over that level's slice only -- the parents and
+ *   their child counts, the library's one-pass scan of them, the places -- so the total work is O(nnz) with no round trip
+ *   inside; the rank among siblings walks the parent's row, deg(parent) a child: quadratic in a hub's degree
+ *   (profiles/rcm_case.md).  rcm_group: the regrouping by the scan of the components' sizes, and the reversal.
+ *   Nothing spins on the device, nothing waits for another workgroup.  A row is spread over 1, 4, 16 or 64 lanes by the
+ *   pattern's mean row length.
+ * Synchronous on the handle's stream, needs no bound data, leaves the handle as it was (a workspace of its own).  ms_out
+ *   (may be NULL): device time of the call, the round trips included.                                                  */
+#define BHS_RCM_PERIPHERAL 1   /* the George-Liu pseudo-peripheral start of every component */
+#define BHS_RCM_NO_REVERSE 2   /* the Cuthill-McKee order itself, not its reverse */
+BHS_API int bhs_csr_rcm_device(bhs_handle *h, int n, int nnzS,
+        const int *d_rowPtrS, const int *d_colIndS /* n x n pattern, rows ascending, symmetric; values are not taken */,
+        int flags /* BHS_RCM_PERIPHERAL | BHS_RCM_NO_REVERSE */,
+        int *d_perm  /* out: n ints: the old index of new row k */,
+        int *d_level /* out, may be NULL: n ints: the final sweep's levels */,
+        int *d_start /* out, may be NULL: CAPACITY n, ncomp written: the start of component c */,
+        int *ncomp_out /* may be NULL */, int *depth_out /* may be NULL */, int *sweeps_out /* may be NULL */,
+        int *passes_out /* may be NULL; a multiple of the batch, depends on timing */,
+        double *ms_out /* may be NULL */);
+
 /* ---- spanning forest --------------------------------------------------------
  * The minimum (or maximum) spanning forest of the graph that an n x n matrix A stores, by Boruvka rounds on the device: for
  * network design, as the spanning tree under a support-graph or tree preconditioner (the MAXIMUM forest of |a_ij| is the
