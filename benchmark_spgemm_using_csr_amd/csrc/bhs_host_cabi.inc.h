@@ -115,7 +115,7 @@ int bhs_destroy(bhs_handle* h)
     release(h->bWin); release(h->bWinTab); release(h->bWinSpill);
     release(h->hubBits); release(h->hubRank); release(h->hubItems); release(h->hubSeg); release(h->hubCtl);
     release(h->spaBits);
-    release(h->maskWs); release(h->addWs); release(h->selWs); release(h->trWs); release(h->exWs); release(h->rdWs); release(h->mvWs); release(h->sdWs); release(h->fsWs); release(h->srmvWs); release(h->pushWs); release(h->aggWs); release(h->colWs); release(h->trsvWs); release(h->ccWs); release(h->sccWs); release(h->rcmWs); release(h->mtWs); release(h->sfWs); release(h->cfWs); release(h->asWs); release(h->rxWs); release(h->dotWs);
+    release(h->maskWs); release(h->addWs); release(h->selWs); release(h->trWs); release(h->exWs); release(h->rdWs); release(h->mvWs); release(h->sdWs); release(h->fsWs); release(h->srmvWs); release(h->pushWs); release(h->aggWs); release(h->colWs); release(h->trsvWs); release(h->ccWs); release(h->sccWs); release(h->rcmWs); release(h->coreWs); release(h->mtWs); release(h->sfWs); release(h->cfWs); release(h->asWs); release(h->rxWs); release(h->dotWs);
     for (DevBuf& b : h->asBuf) release(b);
     for (int i = 0; i < 3; ++i) { release(h->maskM[i]); release(h->addD[i]); }
     release(h->addPos); release(h->sumCp);

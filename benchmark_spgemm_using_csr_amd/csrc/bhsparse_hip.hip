@@ -440,6 +440,8 @@ struct bhs_handle {
     // its queue buffer; the roots per bitmap word, the level order's table, a level's child counts and the components' sizes
     // in its count buffer
     SideWs rcmWs;
+    // the k-core decomposition (bhs_host_kcore.inc.h): the degrees and the queue in its queue buffer, no counts
+    SideWs coreWs;
     // the matching (bhs_host_match.inc.h): the leader bitmap, the scanned offsets and the rounds' candidates in its queue
     // buffer, the leaders per bitmap word in its count buffer
     SideWs mtWs;
@@ -636,6 +638,7 @@ inline int one_launch(int rc) { return rc != BHS_SUCCESS ? rc : 1; }
 #include "bhs_host_fsai.inc.h"
 #include "bhs_host_scc.inc.h"
 #include "bhs_host_rcm.inc.h"
+#include "bhs_host_kcore.inc.h"
 #include "bhs_host_transpose.inc.h"
 #include "bhs_host_reduce.inc.h"
 #include "bhs_host_semiring.inc.h"

@@ -19,6 +19,10 @@ scc_* answer the question about the DIRECTION of the entries: the strongly conne
 "strongly connected components"), by trimming and forward-backward rounds; condensation_device is the DAG of the SCCs,
 largest_scc_csr the submatrix of the largest one.
 
+kcore_* give the core number of every vertex of an undirected graph and the round of the synchronous peeling in which it
+leaves (bhs_csr_kcore_device; "k-core decomposition"): the degeneracy, a degeneracy ordering, the k-core as a submatrix;
+ktruss_device is the k-truss on top of the masked PLUS_PAIR product and the entry selection.
+
 spanning_forest_* give the minimum or maximum spanning forest of the weighted graph (bhs_csr_spanning_forest_device;
 "spanning forest"), unique for any input, in at most log2 n Boruvka rounds; single_linkage_device cuts its heaviest edges
 and calls the components on the rest."""
@@ -373,6 +377,103 @@ def largest_scc_csr(n, Ap, Aj, Ax, value_dtype=np.float64, device=0):
     vertices) through facade.extract_csr."""
     _, comp, sizes = scc_csr(n, Ap, Aj, device=device)
     return _largest_csr(n, Ap, Aj, Ax, comp, sizes, value_dtype, device)
+
+
+# ---------------------------------------------------------------- k-core and k-truss
+def kcore_raw_device(bh, n, nnz, dAp, dAj, flags, core, round):
+    """bhs_csr_kcore_device on caller-given arrays, the C arguments in order (round may be None): the status code,
+    BHS_ERR_NOT_READY without a platform; sets bh.kcore_kmax, bh.kcore_rounds (functions of the pattern) and bh.kcore_ms on
+    success only."""
+    return bh._counted("bhs_csr_kcore_device", "kcore", "kmax", "rounds", int(n), int(nnz), _ptr(dAp), _ptr(dAj), int(flags),
+                       _ptr(core), _ptr(round))
+
+
+def kcore_device(bh, n, A):
+    """The k-core decomposition of the n-vertex pattern A = (rowPtr, colInd[, anything]), torch tensors on the handle's GPU:
+    rows strictly ascending, structurally symmetric (ordering.symmetric_pattern_device and assemble.canonical_csr_device make
+    one of any matrix); the diagonal is ignored, values are not taken.  Returns (core int32[n], round int32[n], kmax,
+    rounds): every vertex's core number, the round of the synchronous peeling in which it leaves (from 1), the degeneracy and
+    the number of rounds.  bh.kcore_ms holds the device time.  Raises BhsparseError on failure -- BHS_ERR_INVALID_ARG for a
+    pattern that is not ascending or not symmetric."""
+    import torch
+    Ap, Aj = A[0], A[1]
+    core, rnd = (_alloc(n, torch.int32, Ap.device) for _ in range(2))
+    torch.cuda.synchronize()                           # the library works on its own stream (see facade.initData_device)
+    _check(kcore_raw_device(bh, n, Aj.numel(), Ap, Aj if Aj.numel() else None, 0, core, rnd), "bhs_csr_kcore_device")
+    return core[:n], rnd[:n], bh.kcore_kmax, bh.kcore_rounds
+
+
+def kcore_csr(n, Ap, Aj, device=0):
+    """Convenience: kcore_device once on host CSR arrays.  Returns (core int32[n], round int32[n], kmax, rounds), the arrays
+    as numpy."""
+    A = _device_csr(Ap, Aj, None, np.float64, device)
+    with _handle(np.float64, device, None) as bh:
+        core, rnd, kmax, rounds = kcore_device(bh, n, A)
+        return _host(core, rnd) + (kmax, rounds)
+
+
+def degeneracy_order_device(round):
+    """The vertices by (round, index) from kcore_device's round, through torch's stable sort: int32[n] on the device.  Every
+    vertex has at most core[v] <= kmax neighbours behind it in this order: those of its own round and of later ones were
+    present when it left with a degree of at most its core number."""
+    import torch
+    return torch.sort(round, stable=True)[1].to(torch.int32)
+
+
+def kcore_subgraph_device(bh, n, A, core, k):
+    """The k-core of A = (rowPtr, colInd, val or None) from kcore_device's core: (V int32 ascending, (Zp, Zj, Zx)) with
+    V = {v: core[v] >= k} and Z = A(V, V) through the handle's extraction (Zx None where A has no values).  Off the diagonal
+    every row of Z has at least k entries."""
+    import torch
+    V = torch.nonzero(core >= k).flatten().to(torch.int32)
+    if V.numel() == 0:
+        Ax = A[2] if len(A) > 2 else None
+        return V, (torch.zeros(1, dtype=torch.int32, device=core.device), torch.zeros(0, dtype=torch.int32, device=core.device),
+                   None if Ax is None else Ax[:0])
+    Zp, Zj, Zx, _ = bh.csr_extract_device(n, n, (A[0], A[1], A[2] if len(A) > 2 else None), rows=V, cols=V)
+    return V, (Zp, Zj, Zx)
+
+
+def ktruss_device(bh, n, A, k):
+    """The k-truss of the n-vertex pattern A = (rowPtr, colInd[, anything]) (rows strictly ascending, structurally
+    symmetric; the diagonal is dropped first): the maximal subgraph T in which every edge lies in at least k - 2 triangles
+    of T.  Returns ((rowPtr, colInd, support), iterations): T as a symmetric device CSR whose values, in the handle's type,
+    are the supports -- the triangles of T an edge lies in.  An iteration is one masked PLUS_PAIR product T.T on T's own
+    pattern (bhsparse.spgemm_semiring_masked_device: the common neighbours of an edge's ends) and one entry selection that
+    keeps support > k - 2.5 (bhsparse.csr_select_device; supports are exact small integers); it is repeated until nnz stops
+    falling, so the last product's values are the supports inside T.  k <= 2 keeps every edge: one product."""
+    import torch
+    dt = torch.float32 if bh._vdt == np.dtype(np.float32) else torch.float64
+    off = _lib.Select(flags=_lib.BHS_SEL_DROP_DIAG)
+    Tp, Tj, _ = bh.csr_select_device(n, n, (A[0], A[1], None), off, values=False)
+    keep = _lib.Select(flags=_lib.BHS_SEL_DROP_DIAG | _lib.BHS_SEL_ABS, abs_tol=float(k) - 2.5) if k > 2 else None
+    iterations = 0
+    while True:
+        nnz = Tj.numel()
+        if nnz == 0:
+            return (Tp, Tj, torch.zeros(0, dtype=dt, device=Tp.device)), iterations
+        ones = torch.ones(nnz, dtype=dt, device=Tp.device)
+        support = torch.zeros(nnz, dtype=dt, device=Tp.device)
+        _check(bh.initData_device(n, n, n, nnz, ones, Tp, Tj, nnz, ones, Tp, Tj), "initData_device")
+        try:
+            _check(bh.spgemm_semiring_masked_device(_lib.BHS_SR_PLUS_PAIR, Tp, Tj, nnz, support), "bhs_spgemm_semiring_masked_device")
+        finally:
+            bh.free_mem()
+        iterations += 1
+        if keep is None:
+            return (Tp, Tj, support), iterations
+        Zp, Zj, _ = bh.csr_select_device(n, n, (Tp, Tj, support), keep, values=False)
+        if Zj.numel() == nnz:
+            return (Tp, Tj, support), iterations
+        Tp, Tj = Zp, Zj
+
+
+def ktruss_csr(n, Ap, Aj, k, value_dtype=np.float64, device=0):
+    """Convenience: ktruss_device once on host CSR arrays.  Returns ((Tp, Tj, support) as numpy, iterations)."""
+    A = _device_csr(Ap, Aj, None, value_dtype, device)
+    with _handle(value_dtype, device, None) as bh:
+        T, iterations = ktruss_device(bh, n, A, k)
+        return _host(*T), iterations
 
 
 # ---------------------------------------------------------------- spanning forest

@@ -219,6 +219,14 @@ public:
                        index_type *d_perm, index_type *d_level, index_type *d_start, int *ncomp_out, int *depth_out,
                        int *sweeps_out, int *passes_out);
 
+    // EXTENSION, not part of the reference's API: the k-core decomposition of an n x n pattern S on DEVICE arrays
+    // (bhs_csr_kcore_device; include/bhsparse_hip.h, "k-core decomposition").  S has strictly ascending rows and a symmetric
+    // structure, checked on the device; the diagonal is ignored.  d_core (n ints) receives every vertex's core number,
+    // d_round (n ints, may be null) the round of the synchronous peeling in which it leaves, from 1.  *kmax_out (the
+    // degeneracy) and *rounds_out are functions of the pattern.  flags must be 0.  Needs initPlatform only.
+    int csr_kcore_device(int n, int nnzS, const index_type *d_rowPtrS, const index_type *d_colIndS, int flags,
+                         index_type *d_core, index_type *d_round, int *kmax_out, int *rounds_out);
+
     // EXTENSION, not part of the reference's API: heavy-edge matching of the vertices of an n x n matrix A on DEVICE arrays
     // (bhs_csr_match_device; include/bhsparse_hip.h, "matching").  d_valA may be null: every weight 1.  d_mate (n ints)
     // receives every vertex's partner, the vertex itself where it is unmatched; d_agg (n ints, may be null) the number of its
@@ -570,6 +578,13 @@ inline int bhsparse::csr_rcm_device(int n, int nnzS, const index_type *d_rowPtrS
     if (!_h) return BHS_ERR_NOT_READY;
     return bhs_csr_rcm_device(_h, n, nnzS, d_rowPtrS, d_colIndS, flags, d_perm, d_level, d_start, ncomp_out, depth_out, sweeps_out,
                               passes_out, 0);
+}
+
+inline int bhsparse::csr_kcore_device(int n, int nnzS, const index_type *d_rowPtrS, const index_type *d_colIndS, int flags,
+                                      index_type *d_core, index_type *d_round, int *kmax_out, int *rounds_out)
+{
+    if (!_h) return BHS_ERR_NOT_READY;
+    return bhs_csr_kcore_device(_h, n, nnzS, d_rowPtrS, d_colIndS, flags, d_core, d_round, kmax_out, rounds_out, 0);
 }
 
 inline int bhsparse::csr_match_device(int n, int nnzA, const index_type *d_rowPtrA, const index_type *d_colIndA,

@@ -1160,6 +1160,55 @@ BHS_API int bhs_csr_rcm_device(bhs_handle *h, int n, int nnzS,
         int *passes_out /* may be NULL; a multiple of the batch, depends on timing */,
         double *ms_out /* may be NULL */);
 
+/* ---- k-core decomposition ---------------------------------------------------
+ * The core number of every vertex of a symmetric pattern by parallel peeling: the greatest k for which the vertex lies in a
+ * subgraph of minimum degree k (Batagelj-Zaversnik's core numbers, networkx's core_number) -- cohesive subgraphs, the
+ * degeneracy and a degeneracy ordering (no reference counterpart; bhs_kcore.hip.h).
+ * S is an n x n pattern on the device, 0-based int32 CSR, rows STRICTLY ASCENDING, STRUCTURALLY SYMMETRIC.  Values are NOT
+ * TAKEN, so the double and the float library run the same code and give the same bits.  A diagonal entry is allowed and
+ * ignored.
+ * Definition.  deg(v) = the entries of row v off the diagonal, and k_0 = 0.  In round r = 1, 2, ... let k_r = max(k_{r-1},
+ *   the smallest degree among the vertices still present).  Every present vertex with deg <= k_r leaves SIMULTANEOUSLY with
+ *   core = k_r and round = r; the degrees of the remaining vertices drop by the number of their neighbours that left.  The
+ *   rounds end when no vertex is present.  *kmax_out is the greatest core number (the degeneracy), *rounds_out the last r.
+ *   core is the usual core number; round is the synchronous peeling depth.  Sorting the vertices by (round, index) gives a
+ *   degeneracy ordering: every vertex has at most core(v) <= kmax neighbours behind it.
+ * Refusals by the device, each BHS_ERR_INVALID_ARG, found by the first kernel (bhs_csr_rcm_device's check, under this call's
+ *   own record kcore_check): a falling row pointer, or nnzS != rowPtr[n]; a column outside [0, n); a row that is not
+ *   strictly ascending (a repeated entry included); an entry (i, j) without (j, i), found by a binary search in row j.  Once
+ *   the check has raised the error word every later launch leaves at once: a refused pattern is refused BEFORE d_core or
+ *   d_round is written, nothing stays queued, and nothing beyond the outputs' stated sizes is ever written.
+ * Refusals by the host, each BHS_ERR_INVALID_ARG: a NULL handle, a call between bhs_spgemm_symbolic and bhs_spgemm_finish,
+ *   negative n or nnzS, flags other than 0, a NULL d_rowPtrS or d_core with n > 0, NULL d_colIndS with nnzS > 0, an output's
+ *   footprint overlapping S or the other output.
+ * n == 0 succeeds with *kmax_out = *rounds_out = 0 and launches nothing.
+ * Outputs.  d_core and d_round (may be NULL), n ints each, *kmax_out and *rounds_out are a function of the pattern alone: the
+ *   same bits from run to run, from handle to handle, and in the double and the float library.
+ * How.  A work-efficient frontier peel, O(nnz) in all: every vertex enters one queue of n ints exactly once, and a round's
+ *   vertices are a slice of it.  The order INSIDE the queue DEPENDS ON TIMING and is therefore NOT AN OUTPUT; which vertices a
+ *   round holds does not.  A pass is four launches with no host decision between them.  kcore_peel: for every vertex v of
+ *   the slice and every neighbour u, old = atomicSub(deg + u, 1), unconditionally; the one thread that sees old == k + 1
+ *   appends u and stores core[u] = k, round[u] = r + 1 with plain stores -- the only writer these words ever have.  A
+ *   present vertex has deg > k when the pass starts, so it crosses k + 1 exactly once if it ends at or below k, however
+ *   many neighbours it loses; a vertex that has left only sinks.  kcore_advance: where the peel appended
+ *   nothing and vertices remain, the smallest present degree by an integer atomicMin and the vertices of that degree
+ *   appended and stamped -- the level jump, so empty levels cost nothing, and the call's first frontier -- then ONE thread
+ *   makes the appended range the next slice.  8 passes a control round trip; the call ends after a batch whose last pass
+ *   left no vertex present; the passes behind the last round leave at once.  BHS_ERR_INTERNAL when more than n + 1 passes
+ *   would be needed.  Nothing spins, nothing waits for another workgroup; the atomics are integer atomics on the workspace
+ *   alone, no output is written by an atomic.  A row is spread over 1, 4, 16 or 64 lanes by the pattern's mean row length,
+ *   and in the peel a row of more than 32 entries a lane over a whole wave; the check gives a hub row ONE such group,
+ *   and a deep graph pays four launches a round (profiles/kcore_case.md).
+ * Synchronous on the handle's stream, needs no bound data, leaves the handle as it was (a workspace of its own).  ms_out
+ *   (may be NULL): device time of the call, the round trips included.                                                  */
+BHS_API int bhs_csr_kcore_device(bhs_handle *h, int n, int nnzS,
+        const int *d_rowPtrS, const int *d_colIndS /* n x n pattern, rows ascending, symmetric; values are not taken */,
+        int flags /* must be 0 */,
+        int *d_core  /* out: n ints: the core number of every vertex */,
+        int *d_round /* out, may be NULL: n ints: the round in which every vertex left, from 1 */,
+        int *kmax_out /* may be NULL: the degeneracy */, int *rounds_out /* may be NULL */,
+        double *ms_out /* may be NULL */);
+
 /* ---- spanning forest --------------------------------------------------------
  * The minimum (or maximum) spanning forest of the graph that an n x n matrix A stores, by Boruvka rounds on the device: for
  * network design, as the spanning tree under a support-graph or tree preconditioner (the MAXIMUM forest of |a_ij| is the
