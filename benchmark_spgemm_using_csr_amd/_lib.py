@@ -157,6 +157,8 @@ SYMBOLS = {
     "bhs_csr_rcm_device": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i),
                                 C.POINTER(C.c_double)]),
     "bhs_csr_kcore_device": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(C.c_double)]),
+    "bhs_csr_sssp_device": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _vp, C.c_double, _i, _vp, _vp, C.POINTER(_i), C.POINTER(_i),
+                                 C.POINTER(C.c_double)]),
     "bhs_csr_match_device": (_i, [_vp, _i, _i, _vp, _vp, _vp, C.c_uint, _i, _vp, _vp, C.POINTER(_i), C.POINTER(_i),
                                   C.POINTER(C.c_double)]),
     "bhs_csr_spanning_forest_device": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, C.POINTER(_i), C.POINTER(_i),

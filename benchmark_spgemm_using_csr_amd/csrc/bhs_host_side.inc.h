@@ -11,7 +11,7 @@
 // the row pointer from a family's counts, the aliasing check of an entry point (side_aliased) and the guarded entry of the
 // C-ABI.  For the graph and solver families, whose control blocks all begin with bhs_aggregate.hip.h's words: the lanes a row
 // gets and their dispatch (side_lanes, with_lanes), the loop of rounds that decide until no vertex is left (side_rounds)
-// and the loop of batched passes to a fixed point (side_passes).
+// and the loop of batched passes to a fixed point (side_passes, side_passes_within).
 
 int wait_stream(bhs_handle* h);          // (bhs_host_pipeline.inc.h)
 
@@ -235,15 +235,15 @@ int side_rounds(bhs_handle* h, SideWs& ws, long long n, int ctlInts, int* rounds
 
 // The passes to a fixed point (the level sets, the components): `batch` passes of launch() a round trip of ctlInts control
 // words, the clearInts words from AG_UNDEC on cleared ahead of the batch's last pass, so that they are that pass's alone.  It
-// ends after a batch whose last pass counted nothing, and with BHS_ERR_INTERNAL when more than n + 1 passes would be needed
-// (n passes change something, one more finds nothing).  *passes_out: the passes launched.
+// ends after a batch whose last pass counted nothing, and with BHS_ERR_INTERNAL when more than `bound` + 1 passes would be
+// needed.  *passes_out: the passes launched.
 template <typename F>
-int side_passes(bhs_handle* h, SideWs& ws, long long n, int batch, int clearInts, int ctlInts, int* passes_out, F&& launch)
+int side_passes_within(bhs_handle* h, SideWs& ws, long long bound, int batch, int clearInts, int ctlInts, int* passes_out, F&& launch)
 {
     int* ctl = (int*)ws.ctl.p;
     long long passes = 0;
     for (;;) {
-        if (passes > n) return BHS_ERR_INTERNAL;
+        if (passes > bound) return BHS_ERR_INTERNAL;
         for (int p = 0; p < batch; ++p) {
             if (p == batch - 1) BHS_HIP(hipMemsetAsync(ctl + AG_UNDEC, 0, sizeof(int) * (size_t)clearInts, h->stream));
             BHS_TRY(launch());
@@ -256,6 +256,14 @@ int side_passes(bhs_handle* h, SideWs& ws, long long n, int batch, int clearInts
         *passes_out = (int)std::min<long long>(passes, 0x7fffffff);
         if (count == 0) return BHS_SUCCESS;
     }
+}
+
+// ... where a pass changes one of n things at least: more than n + 1 passes are never needed (n passes change something, one
+// more finds nothing)
+template <typename F>
+int side_passes(bhs_handle* h, SideWs& ws, long long n, int batch, int clearInts, int ctlInts, int* passes_out, F&& launch)
+{
+    return side_passes_within(h, ws, n, batch, clearInts, ctlInts, passes_out, launch);
 }
 
 // after a failed call: nothing of it stays queued (the pipeline's own state is not touched)

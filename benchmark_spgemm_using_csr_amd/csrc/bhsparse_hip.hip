@@ -442,6 +442,10 @@ struct bhs_handle {
     SideWs rcmWs;
     // the k-core decomposition (bhs_host_kcore.inc.h): the degrees and the queue in its queue buffer, no counts
     SideWs coreWs;
+    // the shortest paths (bhs_host_sssp.inc.h): the distance words, the stamps, the two slices and the parents' words in its
+    // queue buffer, no counts
+    SideWs ssspWs;
+    long long ssspBuckets = 0, ssspLoose = 0, ssspWork = 0;   // bhs_get_info "sssp_buckets", "sssp_loose", "sssp_work_passes": of the last call
     // the matching (bhs_host_match.inc.h): the leader bitmap, the scanned offsets and the rounds' candidates in its queue
     // buffer, the leaders per bitmap word in its count buffer
     SideWs mtWs;
@@ -639,6 +643,7 @@ inline int one_launch(int rc) { return rc != BHS_SUCCESS ? rc : 1; }
 #include "bhs_host_scc.inc.h"
 #include "bhs_host_rcm.inc.h"
 #include "bhs_host_kcore.inc.h"
+#include "bhs_host_sssp.inc.h"
 #include "bhs_host_transpose.inc.h"
 #include "bhs_host_reduce.inc.h"
 #include "bhs_host_semiring.inc.h"

@@ -23,6 +23,11 @@ kcore_* give the core number of every vertex of an undirected graph and the roun
 leaves (bhs_csr_kcore_device; "k-core decomposition"): the degeneracy, a degeneracy ordering, the k-core as a submatrix;
 ktruss_device is the k-truss on top of the masked PLUS_PAIR product and the entry selection.
 
+sssp_delta_* are the shortest paths in ONE device-resident call (bhs_csr_sssp_device; "shortest paths"): delta-stepping on a
+queue over the OUT-EDGE matrix -- G(i, j) an edge i -> j, the push call's orientation, no transpose and no dense frontier --
+with distances that are the same bits as sssp_device's and, optionally, parents: path_from_parents walks them back to a
+source, bfs_levels_queue_device is the unit-weight case.
+
 spanning_forest_* give the minimum or maximum spanning forest of the weighted graph (bhs_csr_spanning_forest_device;
 "spanning forest"), unique for any input, in at most log2 n Boruvka rounds; single_linkage_device cuts its heaviest edges
 and calls the components on the rest."""
@@ -377,6 +382,76 @@ def largest_scc_csr(n, Ap, Aj, Ax, value_dtype=np.float64, device=0):
     vertices) through facade.extract_csr."""
     _, comp, sizes = scc_csr(n, Ap, Aj, device=device)
     return _largest_csr(n, Ap, Aj, Ax, comp, sizes, value_dtype, device)
+
+
+# ---------------------------------------------------------------- shortest paths in one call
+def sssp_delta_raw_device(bh, n, nnz, dGp, dGj, dGx, nsrc, dsources, delta, flags, dist, parent):
+    """bhs_csr_sssp_device on caller-given arrays, the C arguments in order (dGx and parent may be None): the status code,
+    BHS_ERR_NOT_READY without a platform; sets bh.sssp_reached, bh.sssp_passes (functions of the input and delta) and
+    bh.sssp_ms on success only.  bh.get_info("sssp_buckets"), ("sssp_loose") and ("sssp_work_passes") read the rest."""
+    return bh._counted("bhs_csr_sssp_device", "sssp", "reached", "passes", int(n), int(nnz), _ptr(dGp), _ptr(dGj), _ptr(dGx),
+                       int(nsrc), _ptr(dsources), C.c_double(float(delta)), int(flags), _ptr(dist), _ptr(parent))
+
+
+def sssp_delta_device(bh, n, G, sources, delta=None, parents=False):
+    """Shortest paths of the n-vertex graph G = (rowPtr, colInd, val or None) -- torch tensors on the handle's GPU, G(i, j) an
+    edge i -> j of weight val, not negative (1 without val) -- from the nearest of `sources`, in one call of the library.
+    Returns (dist[, parent], reached, passes): dist of the value type, +Inf where not reached; parent int32 (-1 a source or
+    not reached, -2 reached only over edges that gain nothing; every other parent has a strictly smaller distance);
+    reached the vertices with a finite distance; passes the passes launched.  delta is the bucket width and changes the
+    work, never the result; None: +Inf, one bucket -- the rule profiles/sssp_case.md's table gives (its "inf" rows: a pass
+    costs four launches whatever it holds, and on every measured input the fewest passes won by up to 50 ms or lost by less
+    than 1 ms; narrower buckets are for weights spread over many decades on a graph too large for the re-relaxations,
+    which that table does not hold).  bh.sssp_ms holds the device time.  Raises BhsparseError on failure -- BHS_ERR_INVALID_ARG for a negative or NaN weight; ValueError for a
+    source that is no vertex."""
+    import torch
+    Gp, Gj, Gx = G
+    src = torch.as_tensor(_sources(sources, n).astype(np.int32), device=Gp.device)
+    if delta is None:
+        delta = float("inf")
+    dist = _alloc(n, _value_type(bh, G), Gp.device)
+    parent = _alloc(n, torch.int32, Gp.device) if parents else None
+    torch.cuda.synchronize()                           # the library works on its own stream (see facade.initData_device)
+    _check(sssp_delta_raw_device(bh, n, Gj.numel(), Gp, Gj if Gj.numel() else None, Gx if Gj.numel() else None, src.numel(), src,
+                                 delta, 0, dist, parent), "bhs_csr_sssp_device")
+    out = (dist[:n], parent[:n]) if parents else (dist[:n],)
+    return out + (bh.sssp_reached, bh.sssp_passes)
+
+
+def sssp_delta_csr(n, Gp, Gj, Gx, sources, delta=None, parents=False, value_dtype=np.float64, device=0):
+    """Convenience: sssp_delta_device once on host CSR arrays (out-edges).  Returns (dist[, parent], info), the arrays as
+    numpy, with info["reached"], info["passes"], info["buckets"], info["loose"], info["ms"], info["kernels"]."""
+    G = _device_csr(Gp, Gj, Gx, value_dtype, device)
+    with _handle(value_dtype, device, None) as bh:
+        *arrays, reached, passes = sssp_delta_device(bh, n, G, sources, delta, parents)
+        info = {"reached": reached, "passes": passes, "buckets": bh.get_info("sssp_buckets"), "loose": bh.get_info("sssp_loose"),
+                "ms": bh.sssp_ms, "kernels": bh.kernel_stats()}
+        return _host(*arrays) + (info,)
+
+
+def path_from_parents(parent, target):
+    """The vertices from a source to `target` along sssp_delta_*'s parents (a host array): [source, ..., target]; every step
+    goes to a strictly smaller distance, so the walk ends.  A target with parent -1 gives [target]: a source, or a vertex that
+    is not reached -- its distance tells which.  Raises ValueError where the walk meets a vertex without a parent edge (-2)."""
+    parent = np.asarray(parent)
+    out = [int(target)]
+    for _ in range(len(parent)):
+        p = int(parent[out[-1]])
+        if p == -1:
+            return out[::-1]
+        if p < 0 or p >= len(parent):
+            raise ValueError("path_from_parents: vertex %d is reached over edges that gain nothing only (parent %d)" % (out[-1], p))
+        out.append(p)
+    raise ValueError("path_from_parents: the parents do not lead to a source")
+
+
+def bfs_levels_queue_device(bh, n, G, sources):
+    """Breadth-first levels by the queue: sssp_delta_device on the pattern of G = (rowPtr, colInd[, anything]) with unit
+    weights and delta = 1, so that a pass is a level.  int32[n]: depth + 1, 0 where not reached (bfs_levels_device's
+    numbering, for out-edges)."""
+    import torch
+    dist, _, _ = sssp_delta_device(bh, n, (G[0], G[1], None), sources, delta=1.0)
+    return torch.where(torch.isinf(dist), torch.zeros_like(dist), dist + 1.0).to(torch.int32)
 
 
 # ---------------------------------------------------------------- k-core and k-truss

@@ -227,6 +227,17 @@ public:
     int csr_kcore_device(int n, int nnzS, const index_type *d_rowPtrS, const index_type *d_colIndS, int flags,
                          index_type *d_core, index_type *d_round, int *kmax_out, int *rounds_out);
 
+    // EXTENSION, not part of the reference's API: shortest paths from nsrc sources over the OUT-EDGES of an n x n matrix G on
+    // DEVICE arrays by delta-stepping in one call (bhs_csr_sssp_device; include/bhsparse_hip.h, "shortest paths").  G(i, j) is
+    // an edge i -> j; d_valG may be null: every weight 1; a negative or NaN weight is refused on the device.  d_dist (n values)
+    // receives the distance to the nearest source, +Inf where there is none; d_parent (n ints, may be null) the smallest
+    // neighbour of strictly smaller distance with a tight edge, -1 for a source or a vertex not reached, -2 where no such edge
+    // exists.  delta > 0 or +Inf is the bucket width: it changes the work, never the result.  *reached_out and *passes_out (a
+    // multiple of 8) are functions of the input and delta.  flags must be 0.  Needs initPlatform only.
+    int csr_sssp_device(int n, int nnzG, const index_type *d_rowPtrG, const index_type *d_colIndG, const value_type *d_valG,
+                        int nsrc, const index_type *d_sources, double delta, int flags, value_type *d_dist, index_type *d_parent,
+                        int *reached_out, int *passes_out);
+
     // EXTENSION, not part of the reference's API: heavy-edge matching of the vertices of an n x n matrix A on DEVICE arrays
     // (bhs_csr_match_device; include/bhsparse_hip.h, "matching").  d_valA may be null: every weight 1.  d_mate (n ints)
     // receives every vertex's partner, the vertex itself where it is unmatched; d_agg (n ints, may be null) the number of its
@@ -585,6 +596,15 @@ inline int bhsparse::csr_kcore_device(int n, int nnzS, const index_type *d_rowPt
 {
     if (!_h) return BHS_ERR_NOT_READY;
     return bhs_csr_kcore_device(_h, n, nnzS, d_rowPtrS, d_colIndS, flags, d_core, d_round, kmax_out, rounds_out, 0);
+}
+
+inline int bhsparse::csr_sssp_device(int n, int nnzG, const index_type *d_rowPtrG, const index_type *d_colIndG,
+                                     const value_type *d_valG, int nsrc, const index_type *d_sources, double delta, int flags,
+                                     value_type *d_dist, index_type *d_parent, int *reached_out, int *passes_out)
+{
+    if (!_h) return BHS_ERR_NOT_READY;
+    return bhs_csr_sssp_device(_h, n, nnzG, d_rowPtrG, d_colIndG, d_valG, nsrc, d_sources, delta, flags, d_dist, d_parent, reached_out,
+                               passes_out, 0);
 }
 
 inline int bhsparse::csr_match_device(int n, int nnzA, const index_type *d_rowPtrA, const index_type *d_colIndA,

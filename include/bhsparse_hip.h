@@ -1209,6 +1209,72 @@ BHS_API int bhs_csr_kcore_device(bhs_handle *h, int n, int nnzS,
         int *kmax_out /* may be NULL: the degeneracy */, int *rounds_out /* may be NULL */,
         double *ms_out /* may be NULL */);
 
+/* ---- shortest paths ---------------------------------------------------------
+ * Distances, and optionally predecessors, from a set of sources over weights that are not negative, by delta-stepping on a
+ * queue in one device-resident call -- road networks, meshes, any graph of high diameter, where a loop of semiring calls pays
+ * a host round trip a sweep; with unit weights the queue breadth-first search (no reference counterpart; bhs_sssp.hip.h).
+ * Edges.  G is the n x n OUT-EDGE matrix on the device, 0-based int32 CSR: an entry G(i, j) is an edge i -> j of weight valG,
+ *   the orientation of bhs_csr_push_semiring_device.  Rows need not be sorted.  Repeated entries are parallel edges.  A
+ *   diagonal entry is a loop that never improves anything.  An entry of weight +Inf never relaxes.  -0 counts as 0.
+ *   d_valG == NULL: every edge weighs 1.
+ * Distances.  d_dist[v] is the least fixed point of d[s] = 0 for every listed source and d[v] = min over the edges (u, v) of
+ *   fl(d[u] + w(u, v)), fl being ONE rounding to value_type an edge, contraction off; +Inf where v is not reached.  With
+ *   several sources that is the distance to the nearest one; repeated sources are allowed.  Floating add is MONOTONE
+ *   (a <= b gives fl(a + w) <= fl(b + w)) and min is EXACT, so every distance only ever takes values that are the
+ *   left-to-right sum of the weights along some path, and the least fixed point does not depend on the order of the
+ *   relaxations: the result is a function of the input alone -- the same bits from run to run, from handle to handle and for
+ *   every delta, and in the double library the bits a textbook Dijkstra in double produces.
+ * delta is the bucket width: > 0 or +Inf.  It changes the work, never the result.  +Inf is one bucket: frontier Bellman-Ford.
+ *   With d_valG == NULL and delta = 1 the passes are the breadth-first levels.
+ * d_parent (may be NULL).  For a reached vertex v that is no source: the SMALLEST u that has an edge (u, v) with
+ *   fl(d[u] + w) == d[v] AND d[u] < d[v].  -1 for a source and for a vertex that is not reached.  -2 for a reached vertex with
+ *   no such edge: one reached only over edges that gain nothing -- zero weights, or weights absorbed by rounding -- which
+ *   could otherwise close a cycle.  Every parent has a STRICTLY SMALLER distance, so the parents that are not negative form a
+ *   forest rooted at the sources.  One pass behind the fixed point: a push over all edges with an integer atomicMin on a
+ *   workspace word, then a copy.
+ * Counts.  *reached_out: the vertices with a finite distance.  *passes_out: the passes launched, the passes that had a slice
+ *   (bhs_get_info "sssp_work_passes") rounded up to a multiple of 8.  bhs_get_info "sssp_buckets": the buckets that were not
+ *   empty; "sssp_loose": the vertices given -2 (0 without d_parent); all three need no bound data.  reached, sssp_buckets and
+ *   sssp_loose are functions of the input and delta; so are the passes, because a pass is SYNCHRONOUS: it relaxes from the
+ *   distances the pass before left, which it keeps beside its slice, so which words it lowers and which vertices it appends
+ *   do not depend on timing.
+ * Refusals by the device, each BHS_ERR_INVALID_ARG, found by the first kernel (record sssp_check): a weight that is NaN or
+ *   negative (sign bit set and not -0); a column outside [0, n); a row pointer that falls, does not start at 0 or does not end
+ *   at nnzG; a source outside [0, n).  Once the check has raised the error word every later launch leaves at once: a refused
+ *   input is refused BEFORE d_dist or d_parent is written, nothing stays queued, and nothing beyond the outputs' stated sizes
+ *   is ever written.
+ * Refusals by the host, each BHS_ERR_INVALID_ARG: a NULL handle, a call between bhs_spgemm_symbolic and bhs_spgemm_finish,
+ *   negative n, nnzG or nsrc, nsrc < 1 or a NULL d_sources, d_rowPtrG or d_dist with n > 0, NULL d_colIndG with nnzG > 0,
+ *   flags other than 0, a delta that is not > 0 (NaN included), an output's footprint overlapping an input or the other
+ *   output.
+ * n == 0 succeeds with *reached_out = *passes_out = 0 and launches nothing.
+ * How.  dist is kept as the unsigned integer words of value_type's width: values that are not negative order as their words
+ *   do, +Inf's word is the start value and an integer atomicMin is the relaxation.  done[v] is the distance at which v last
+ *   relaxed its out-edges; v is pending while dist[v] < done[v].  A pass is four launches with no host decision between them.
+ *   sssp_relax: every vertex of the slice relaxes its out-edges from its snapshot; the thread that lowers a word and leaves it
+ *   below the bucket's bound claims the vertex by an atomicExch on its stamp and appends it to the next slice -- at most one
+ *   append a vertex a pass; a vertex lowered to the bound or beyond stays pending.  sssp_advance: the appended vertices'
+ *   snapshots; or, where nothing was appended, the smallest pending distance by an integer atomicMin, the bound
+ *   (floor(min / delta) + 1) delta in double, and every pending vertex below it or EQUAL to the minimum appended -- the
+ *   bucket jump, so empty buckets cost nothing and the minimum's holder is taken whatever the bound's rounding; then ONE
+ *   thread swaps the slices.  8 passes a control round trip; the call ends after a batch whose last pass left no slice; the
+ *   passes behind the last one leave at once.  BHS_ERR_INTERNAL when more than 2 n + 2 passes would be needed.  Nothing
+ *   spins, nothing waits for another workgroup; the atomics are integer atomics on the workspace alone, and the one kernel
+ *   that writes an output (sssp_finish) uses plain stores.  A row is spread over 1, 4, 16 or 64 lanes by the mean row length,
+ *   and in the relax and the parents' pass a row of more than 32 entries a lane over a whole wave; the check walks the
+ *   entries, not the rows (profiles/sssp_case.md).
+ * Synchronous on the handle's stream, needs no bound data, leaves the handle as it was (a workspace of its own: 4 n
+ *   value_type words and 3 or 4 n ints).  ms_out (may be NULL): device time of the call, the round trips included.      */
+BHS_API int bhs_csr_sssp_device(bhs_handle *h, int n, int nnzG,
+        const int *d_rowPtrG, const int *d_colIndG /* n x n out-edges: G(i, j) is an edge i -> j */,
+        const bhs_value_t *d_valG /* the weights, not negative; NULL: every edge weighs 1 */,
+        int nsrc, const int *d_sources /* nsrc vertices, repeats allowed */,
+        double delta /* the bucket width: > 0 or +Inf */, int flags /* must be 0 */,
+        bhs_value_t *d_dist /* out: n values; +Inf where not reached */,
+        int *d_parent /* out, may be NULL: n ints; -1 a source or not reached, -2 no tight edge from a smaller distance */,
+        int *reached_out /* may be NULL */, int *passes_out /* may be NULL: a multiple of 8 */,
+        double *ms_out /* may be NULL */);
+
 /* ---- spanning forest --------------------------------------------------------
  * The minimum (or maximum) spanning forest of the graph that an n x n matrix A stores, by Boruvka rounds on the device: for
  * network design, as the spanning tree under a support-graph or tree preconditioner (the MAXIMUM forest of |a_ij| is the
