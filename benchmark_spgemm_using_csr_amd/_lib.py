@@ -76,6 +76,9 @@ BHS_FOREST_MAXIMUM, BHS_FOREST_ABS = 1, 2
 # bhs_csr_cfsplit_device (include/bhsparse_hip.h, "C/F splitting and interpolation")
 BHS_CF_DEGREE = 1
 
+# bhs_csr_betweenness_device (include/bhsparse_hip.h, "betweenness centrality")
+BHS_BC_ACCUMULATE = 1
+
 # bhs_coo_assemble_device / bhs_coo_assemble_values_device (include/bhsparse_hip.h, "assembly")
 BHS_COO_SUM, BHS_COO_FIRST, BHS_COO_LAST, BHS_COO_KEEP, BHS_COO_IGNORE_NEGATIVE = 0, 1, 2, 3, 4
 COO_COMBINE = {"sum": BHS_COO_SUM, "first": BHS_COO_FIRST, "last": BHS_COO_LAST, "keep": BHS_COO_KEEP}
@@ -159,6 +162,8 @@ SYMBOLS = {
     "bhs_csr_kcore_device": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(C.c_double)]),
     "bhs_csr_sssp_device": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _vp, C.c_double, _i, _vp, _vp, C.POINTER(_i), C.POINTER(_i),
                                  C.POINTER(C.c_double)]),
+    "bhs_csr_betweenness_device": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, C.POINTER(_i), C.POINTER(_i),
+                                        C.POINTER(C.c_double)]),
     "bhs_csr_match_device": (_i, [_vp, _i, _i, _vp, _vp, _vp, C.c_uint, _i, _vp, _vp, C.POINTER(_i), C.POINTER(_i),
                                   C.POINTER(C.c_double)]),
     "bhs_csr_spanning_forest_device": (_i, [_vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, C.POINTER(_i), C.POINTER(_i),

@@ -115,7 +115,7 @@ int bhs_destroy(bhs_handle* h)
     release(h->bWin); release(h->bWinTab); release(h->bWinSpill);
     release(h->hubBits); release(h->hubRank); release(h->hubItems); release(h->hubSeg); release(h->hubCtl);
     release(h->spaBits);
-    release(h->maskWs); release(h->addWs); release(h->selWs); release(h->trWs); release(h->exWs); release(h->rdWs); release(h->mvWs); release(h->sdWs); release(h->fsWs); release(h->srmvWs); release(h->pushWs); release(h->aggWs); release(h->colWs); release(h->trsvWs); release(h->ccWs); release(h->sccWs); release(h->rcmWs); release(h->coreWs); release(h->ssspWs); release(h->mtWs); release(h->sfWs); release(h->cfWs); release(h->asWs); release(h->rxWs); release(h->dotWs);
+    release(h->maskWs); release(h->addWs); release(h->selWs); release(h->trWs); release(h->exWs); release(h->rdWs); release(h->mvWs); release(h->sdWs); release(h->fsWs); release(h->srmvWs); release(h->pushWs); release(h->aggWs); release(h->colWs); release(h->trsvWs); release(h->ccWs); release(h->sccWs); release(h->rcmWs); release(h->coreWs); release(h->ssspWs); release(h->bcWs); release(h->mtWs); release(h->sfWs); release(h->cfWs); release(h->asWs); release(h->rxWs); release(h->dotWs);
     for (DevBuf& b : h->asBuf) release(b);
     for (int i = 0; i < 3; ++i) { release(h->maskM[i]); release(h->addD[i]); }
     release(h->addPos); release(h->sumCp);
@@ -493,6 +493,9 @@ int bhs_get_info(bhs_handle* h, const char* key, int64_t* value_out)
     if (!strcmp(key, "sssp_buckets")) { *value_out = h->ssspBuckets; return BHS_SUCCESS; }     // buckets that were not empty in the last bhs_csr_sssp_device (needs no bound data either)
     if (!strcmp(key, "sssp_loose")) { *value_out = h->ssspLoose; return BHS_SUCCESS; }         // ... vertices it gave the parent -2
     if (!strcmp(key, "sssp_work_passes")) { *value_out = h->ssspWork; return BHS_SUCCESS; }    // ... passes that had a slice: passes_out is this rounded up to the batch
+    if (!strcmp(key, "bc_levels")) { *value_out = h->bcLevels; return BHS_SUCCESS; }           // the sum over the sources of (deepest level + 1) in the last bhs_csr_betweenness_device (needs no bound data either)
+    if (!strcmp(key, "bc_overflow")) { *value_out = h->bcOverflow; return BHS_SUCCESS; }       // ... sources for which some sigma is not finite
+    if (!strcmp(key, "bc_work_passes")) { *value_out = h->bcWork; return BHS_SUCCESS; }        // ... passes that had a slice
     if (!h->hasData) return BHS_ERR_NOT_READY;
     if (!strcmp(key, "b_sorted")) { *value_out = h->bSorted; return BHS_SUCCESS; }
     if (!strcmp(key, "span_words")) { *value_out = h->ps.spanWPL; return BHS_SUCCESS; }   // bitmap words per lane of the last multiply's span kernels (0: hash kernels)

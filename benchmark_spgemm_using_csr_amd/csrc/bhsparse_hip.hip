@@ -446,6 +446,10 @@ struct bhs_handle {
     // queue buffer, no counts
     SideWs ssspWs;
     long long ssspBuckets = 0, ssspLoose = 0, ssspWork = 0;   // bhs_get_info "sssp_buckets", "sssp_loose", "sssp_work_passes": of the last call
+    // betweenness centrality (bhs_host_bc.inc.h): sigma, delta, the levels, the queue and its level pointer in its queue
+    // buffer, no counts
+    SideWs bcWs;
+    long long bcLevels = 0, bcOverflow = 0, bcWork = 0;       // bhs_get_info "bc_levels", "bc_overflow", "bc_work_passes": of the last call
     // the matching (bhs_host_match.inc.h): the leader bitmap, the scanned offsets and the rounds' candidates in its queue
     // buffer, the leaders per bitmap word in its count buffer
     SideWs mtWs;
@@ -644,6 +648,7 @@ inline int one_launch(int rc) { return rc != BHS_SUCCESS ? rc : 1; }
 #include "bhs_host_rcm.inc.h"
 #include "bhs_host_kcore.inc.h"
 #include "bhs_host_sssp.inc.h"
+#include "bhs_host_bc.inc.h"
 #include "bhs_host_transpose.inc.h"
 #include "bhs_host_reduce.inc.h"
 #include "bhs_host_semiring.inc.h"

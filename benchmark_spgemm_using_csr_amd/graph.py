@@ -28,6 +28,11 @@ queue over the OUT-EDGE matrix -- G(i, j) an edge i -> j, the push call's orient
 with distances that are the same bits as sssp_device's and, optionally, parents: path_from_parents walks them back to a
 source, bfs_levels_queue_device is the unit-weight case.
 
+betweenness_* say which vertices the shortest paths run through (bhs_csr_betweenness_device; "betweenness centrality"):
+Brandes' algorithm a source after the other over the out-edges and the in-edges, every sum with one writer and a fixed
+order, so that the doubles are a function of the input; betweenness_sample_csr estimates it from k pivots, and
+closeness_device reads the classic and the harmonic closeness off the levels of single-source calls.
+
 spanning_forest_* give the minimum or maximum spanning forest of the weighted graph (bhs_csr_spanning_forest_device;
 "spanning forest"), unique for any input, in at most log2 n Boruvka rounds; single_linkage_device cuts its heaviest edges
 and calls the components on the rest."""
@@ -452,6 +457,110 @@ def bfs_levels_queue_device(bh, n, G, sources):
     import torch
     dist, _, _ = sssp_delta_device(bh, n, (G[0], G[1], None), sources, delta=1.0)
     return torch.where(torch.isinf(dist), torch.zeros_like(dist), dist + 1.0).to(torch.int32)
+
+
+# ---------------------------------------------------------------- betweenness centrality
+def betweenness_raw_device(bh, n, nnzG, dGp, dGj, nnzT, dTp, dTj, nsrc, dsources, flags, bc, level, sigma):
+    """bhs_csr_betweenness_device on caller-given arrays, the C arguments in order (level and sigma may be None): the status
+    code, BHS_ERR_NOT_READY without a platform; sets bh.bc_reached, bh.bc_passes (functions of the input) and bh.bc_ms on
+    success only.  bh.get_info("bc_levels"), ("bc_overflow") and ("bc_work_passes") read the rest."""
+    return bh._counted("bhs_csr_betweenness_device", "bc", "reached", "passes", int(n), int(nnzG), _ptr(dGp), _ptr(dGj), int(nnzT),
+                       _ptr(dTp), _ptr(dTj), int(nsrc), _ptr(dsources), int(flags), _ptr(bc), _ptr(level), _ptr(sigma))
+
+
+def betweenness_device(bh, n, G, sources=None, Gt=None, accumulate=None, last=False):
+    """The betweenness of the n-vertex graph G = (rowPtr, colInd[, anything]) -- torch tensors on the handle's GPU, G(i, j) an
+    edge i -> j; values are not taken -- summed over `sources` in list order (None: all vertices, the exact centrality), in
+    one call of the library.  Gt holds the in-edges: None computes the transpose once with bh.csr_transpose_device; Gt = G
+    says the graph is undirected (every edge stored both ways).  accumulate: a float64 tensor of n sums that is added to in
+    place and returned, so that chained calls give the bits of one call; None: a new one, from zero.
+    Returns (bc[, level, sigma], reached, passes): bc float64, UNSCALED -- every ordered pair (s, t) counts, so an
+    undirected graph's values are twice networkx's; with last=True level (int32, -1 where not reached) and sigma (float64
+    path counts) of the last source; reached summed over the sources; passes the forward passes launched.  bh.bc_ms holds the
+    device time; profiles/bc_case.md says what it costs and where it loses.  Raises BhsparseError on failure; ValueError for
+    a source that is no vertex."""
+    import torch
+    Gp, Gj = G[0], G[1]
+    dev = Gp.device
+    src = np.arange(n, dtype=np.int32) if sources is None else _sources(sources, n).astype(np.int32)
+    src = torch.as_tensor(src, device=dev)
+    if Gt is None:
+        Tp, Tj, _, _ = bh.csr_transpose_device(n, n, (Gp, Gj, None), values=False)
+    else:
+        Tp, Tj = Gt[0], Gt[1]
+    if accumulate is not None and (accumulate.dtype != torch.float64 or accumulate.numel() < n or not accumulate.is_contiguous()):
+        raise ValueError("accumulate: a contiguous float64 tensor of n sums")
+    bc = _alloc(n, torch.float64, dev) if accumulate is None else accumulate
+    level = _alloc(n, torch.int32, dev) if last else None
+    sigma = _alloc(n, torch.float64, dev) if last else None
+    torch.cuda.synchronize()                           # the library works on its own stream (see facade.initData_device)
+    _check(betweenness_raw_device(bh, n, Gj.numel(), Gp, Gj if Gj.numel() else None, Tj.numel(), Tp, Tj if Tj.numel() else None,
+                                  src.numel(), src if n else None, 0 if accumulate is None else _lib.BHS_BC_ACCUMULATE,
+                                  bc if n else None, level, sigma), "bhs_csr_betweenness_device")
+    out = (bc[:n], level[:n], sigma[:n]) if last else (bc[:n],)
+    return out + (bh.bc_reached, bh.bc_passes)
+
+
+def _bc_scaled(bc, n, directed, normalized, factor=1.0):
+    """networkx's conventions: an undirected graph's pairs count once, normalised by the (n - 1)(n - 2) ordered pairs"""
+    if normalized:
+        return bc * (factor / ((n - 1) * (n - 2))) if n > 2 else bc * 0.0
+    return bc * (factor if directed else 0.5 * factor)
+
+
+def _betweenness_raw_csr(n, Gp, Gj, sources, directed, device):
+    """(raw, info): the UNSCALED sums of betweenness_device on host CSR arrays -- every ordered pair counts -- and the counts"""
+    G = _device_csr(Gp, Gj, None, np.float64, device)
+    with _handle(np.float64, device, None) as bh:
+        bc, reached, passes = betweenness_device(bh, n, G, sources, None if directed else G)
+        info = {"reached": reached, "passes": passes, "levels": bh.get_info("bc_levels"), "overflow": bh.get_info("bc_overflow"),
+                "ms": bh.bc_ms, "kernels": bh.kernel_stats()}
+        return _host(bc)[0], info
+
+
+def betweenness_csr(n, Gp, Gj, sources=None, directed=True, normalized=False, device=0):
+    """Convenience: betweenness_device once on host CSR arrays (out-edges; an undirected graph stores every edge both ways and
+    says directed=False, which halves).  Returns (bc float64[n], info) with networkx's betweenness_centrality conventions --
+    betweenness_centrality_subset's where sources is a list -- and info["reached"], info["passes"], info["levels"],
+    info["overflow"], info["ms"], info["kernels"]."""
+    raw, info = _betweenness_raw_csr(n, Gp, Gj, sources, directed, device)
+    return _bc_scaled(raw, n, directed, normalized), info
+
+
+def betweenness_sample_csr(n, Gp, Gj, k, seed=0, directed=True, normalized=False, device=0):
+    """The Brandes-Pich estimate: the dependencies of k pivots drawn without replacement by numpy's default_rng(seed), scaled
+    by n / k and then as betweenness_csr scales -- the raw sums are scaled ONCE, so with k = n the estimate is
+    betweenness_csr's value up to the order of the sources and the rounding of n / k = 1.  Returns (bc, info) as betweenness_csr
+    does, with info["pivots"]."""
+    if not 1 <= k <= n:
+        raise ValueError("k: between 1 and n pivots")
+    pivots = np.sort(np.random.default_rng(seed).choice(n, int(k), replace=False))
+    raw, info = _betweenness_raw_csr(n, Gp, Gj, pivots, directed, device)
+    info["pivots"] = pivots
+    return _bc_scaled(raw, n, directed, normalized, n / float(k)), info
+
+
+def closeness_device(bh, n, G, sources):
+    """The closeness of every vertex of `sources` over the out-edges of G, from the levels of single-source calls (the call's
+    d_level; its sums are not used).  Returns (classic, harmonic), float64 numpy arrays in the order of the sources: classic
+    is Wasserman and Faust's (r - 1) / (n - 1) * (r - 1) / sum of the distances to the r - 1 vertices reached, 0 where none
+    is; harmonic the sum of 1 / distance over them, added level by level in ascending order.  Every call still pulls the
+    path counts and runs the backward sweep, which closeness does not need: where the levels alone are wanted,
+    bfs_levels_queue_device gives them at 0.75 to 0.9 of the cost (profiles/bc_case.md, "BFS calls")."""
+    import torch
+    src = _sources(sources, n)
+    Gt = (G[0], G[1])                                  # the path counts are not read: any in-edges do
+    bc = torch.zeros(max(n, 1), dtype=torch.float64, device=G[0].device)
+    classic, harmonic = np.zeros(len(src)), np.zeros(len(src))
+    for k, s in enumerate(src):
+        _, level, _, reached, _ = betweenness_device(bh, n, G, [int(s)], Gt, bc, last=True)
+        per = torch.bincount(level[level > 0].to(torch.int64)).cpu().numpy()       # vertices at every distance
+        total = sum(int(d) * int(c) for d, c in enumerate(per))
+        if total:
+            classic[k] = (reached - 1) / (n - 1) * (reached - 1) / total
+            for d in range(1, len(per)):
+                harmonic[k] += per[d] / d
+    return classic, harmonic
 
 
 # ---------------------------------------------------------------- k-core and k-truss

@@ -238,6 +238,18 @@ public:
                         int nsrc, const index_type *d_sources, double delta, int flags, value_type *d_dist, index_type *d_parent,
                         int *reached_out, int *passes_out);
 
+    // EXTENSION, not part of the reference's API: betweenness centrality over the OUT-EDGES G and the IN-EDGES T = G^T of an
+    // n-vertex graph on DEVICE arrays, by Brandes' algorithm a source after the other in one call
+    // (bhs_csr_betweenness_device; include/bhsparse_hip.h, "betweenness centrality").  For an undirected graph T is G: the same
+    // arrays.  d_bc (n doubles) receives the dependencies summed over the nsrc sources in list order -- added to what it holds
+    // under BHS_BC_ACCUMULATE -- every number a double whatever value_type is; d_level and d_sigma (n each, may be null) the
+    // levels and the path counts of the LAST source.  Every sum has one writer and a fixed order: the bits are a function of
+    // the input.  *reached_out (summed over the sources) and *passes_out (a multiple of 8 a source) are too.  Needs
+    // initPlatform only.
+    int csr_betweenness_device(int n, int nnzG, const index_type *d_rowPtrG, const index_type *d_colIndG, int nnzT,
+                               const index_type *d_rowPtrT, const index_type *d_colIndT, int nsrc, const index_type *d_sources,
+                               int flags, double *d_bc, index_type *d_level, double *d_sigma, int *reached_out, int *passes_out);
+
     // EXTENSION, not part of the reference's API: heavy-edge matching of the vertices of an n x n matrix A on DEVICE arrays
     // (bhs_csr_match_device; include/bhsparse_hip.h, "matching").  d_valA may be null: every weight 1.  d_mate (n ints)
     // receives every vertex's partner, the vertex itself where it is unmatched; d_agg (n ints, may be null) the number of its
@@ -605,6 +617,16 @@ inline int bhsparse::csr_sssp_device(int n, int nnzG, const index_type *d_rowPtr
     if (!_h) return BHS_ERR_NOT_READY;
     return bhs_csr_sssp_device(_h, n, nnzG, d_rowPtrG, d_colIndG, d_valG, nsrc, d_sources, delta, flags, d_dist, d_parent, reached_out,
                                passes_out, 0);
+}
+
+inline int bhsparse::csr_betweenness_device(int n, int nnzG, const index_type *d_rowPtrG, const index_type *d_colIndG, int nnzT,
+                                            const index_type *d_rowPtrT, const index_type *d_colIndT, int nsrc,
+                                            const index_type *d_sources, int flags, double *d_bc, index_type *d_level,
+                                            double *d_sigma, int *reached_out, int *passes_out)
+{
+    if (!_h) return BHS_ERR_NOT_READY;
+    return bhs_csr_betweenness_device(_h, n, nnzG, d_rowPtrG, d_colIndG, nnzT, d_rowPtrT, d_colIndT, nsrc, d_sources, flags, d_bc,
+                                      d_level, d_sigma, reached_out, passes_out, 0);
 }
 
 inline int bhsparse::csr_match_device(int n, int nnzA, const index_type *d_rowPtrA, const index_type *d_colIndA,

@@ -1275,6 +1275,82 @@ BHS_API int bhs_csr_sssp_device(bhs_handle *h, int n, int nnzG,
         int *reached_out /* may be NULL */, int *passes_out /* may be NULL: a multiple of 8 */,
         double *ms_out /* may be NULL */);
 
+/* ---- betweenness centrality -------------------------------------------------
+ * Which vertices the shortest paths run through: bc[u] = the sum over the listed sources s of Brandes' dependency of s on u,
+ * in one device-resident call a list of sources -- all vertices for the exact centrality, a sample of pivots for an estimate
+ * (no reference counterpart; bhs_bc.hip.h).  Values are not taken and every number is a double in both libraries: the double
+ * and the float build run the same code and give the same bits.
+ * Edges.  G is the n x n OUT-EDGE matrix on the device, 0-based int32 CSR: an entry G(i, j) is an edge i -> j.  T holds the
+ *   IN-EDGES: T = G^T, row v of T lists the u with an edge u -> v; for an undirected graph T is G, the SAME arrays.  Rows need
+ *   not be sorted.  Repeated entries are parallel edges: they count in sigma, each a path of its own (networkx agrees on the
+ *   graph with a vertex put on every edge; on a MultiDiGraph it counts neighbours, not edges).  Loops never qualify.  T is taken as given: the call does not verify T = G^T, which would cost a sort; the result is a function of
+ *   (G, T, sources) either way, and nothing is read or written out of bounds whatever T holds.
+ * For each source s, in list order (a repeated source counts again):
+ *   Levels.  level[s] = 0, level[v] is the breadth-first depth over G, -1 where v is not reached.
+ *   Path counts.  sigma[s] = 1.  For a reached v != s, sigma[v] is the sum of sigma[u] over the entries u of ROW v OF T with
+ *     level[u] == level[v] - 1.  A vertex that is not reached has sigma = 0.
+ *   Dependencies.  On the deepest level delta[u] = 0.  Otherwise delta[u] = sigma[u] * S, S being the sum of
+ *     (1 + delta[v]) / sigma[v] over the entries v of ROW u OF G with level[v] == level[u] + 1: a true division, contraction
+ *     off.
+ *   Accumulation.  bc[u] = fl(bc[u] + delta[u]) for every reached u != s with 0 < level[u] < the deepest level, one source
+ *     after the other in list order.
+ * Summation rule -- what makes the bits a function of the input when sigma passes 2^53 and the sums stop being exact.  Let L
+ *   in {1, 4, 16, 64} be the lanes of the matrix whose row is walked: 1 up to a mean row length (nnz / n) of 4, 4 up to 16, 16
+ *   up to 64, else 64.  A row of more than 32 L entries takes L_row = 64 (the wave rule of the k-core decomposition and the
+ *   shortest paths), any other L_row = L.  The entry at position p in the row belongs to lane p mod L_row; each lane adds its
+ *   qualifying terms in ascending p, starting from +0; the lane sums are combined by the xor butterfly
+ *   t[l] = t[l] + t[l ^ off] for off = L_row / 2, ..., 1.  A non-qualifying entry contributes nothing.  IEEE semantics hold
+ *   throughout: a sigma that overflows to +Inf stays +Inf, and a NaN in bc that follows from Inf * 0 or Inf / Inf is the
+ *   defined result.  Every NaN is STORED as the one word 0x7FF8000000000000, in delta and in d_bc (one that the caller passes
+ *   in under BHS_BC_ACCUMULATE and a dependency is added to included), so that its bits do not depend on what a processor
+ *   gives an invalid operation.
+ * flags.  BHS_BC_ACCUMULATE: d_bc is added to instead of zero-filled, so one call over s_1 ... s_k gives the same bits as k
+ *   chained single-source calls.
+ * d_level, d_sigma (may be NULL): level and sigma of the LAST source of the list.
+ * Counts.  *reached_out: the sum over the sources of their reached vertices (at most 2^31 - 1 is reported).  *passes_out:
+ *   the forward passes launched, a multiple of 8 per source.  bhs_get_info "bc_levels": the sum over the sources of (deepest
+ *   level + 1); "bc_overflow": the sources for which some sigma is not finite; "bc_work_passes": the passes that had a slice;
+ *   all three need no bound data.  All of these are functions of the input.
+ * Refusals by the device, each BHS_ERR_INVALID_ARG, found by the first kernel (record bc_check), which walks entries, not
+ *   rows: a row pointer of G or T that falls, does not start at 0 or does not end at its nnz; a column of either matrix
+ *   outside [0, n); a source outside [0, n).  Once the check has raised the error word every later launch leaves at once: a
+ *   refused call writes none of d_bc, d_level, d_sigma, and nothing stays queued.
+ * Refusals by the host, each BHS_ERR_INVALID_ARG: a NULL handle, a call between bhs_spgemm_symbolic and bhs_spgemm_finish,
+ *   negative n, nnzG, nnzT or nsrc, nsrc < 1 or a NULL d_sources, d_rowPtrG, d_rowPtrT or d_bc with n > 0, a NULL column
+ *   array with its nnz > 0, flags other than BHS_BC_ACCUMULATE or 0, an output's footprint overlapping an input or another
+ *   output.  Inputs may alias each other: the undirected case.
+ * n == 0 succeeds with *reached_out = *passes_out = 0 and launches nothing.
+ * How.  Per source every reached vertex enters ONE queue once; a level is a slice of it, kept in levelPtr.  bc_seed (1 launch)
+ *   resets level, sigma and delta, queues the source and, on the first source of a call without BHS_BC_ACCUMULATE, zero-fills
+ *   d_bc.  A forward pass is three launches with no host decision between them.  bc_expand: every vertex of the slice walks
+ *   its row of G; the thread whose integer atomicCAS turns level[v] from -1 into l + 1 appends v -- the order inside the queue
+ *   depends on timing and is no output.  bc_count: every vertex of the new slice pulls its sigma over its row of T by the
+ *   summation rule, no atomic and ONE writer; then ONE thread stores levelPtr and makes the appended range the next slice.
+ *   8 passes a control round trip; the forward half ends after a batch whose last pass left no slice; the passes behind the
+ *   last level leave at once.  BHS_ERR_INTERNAL when more than n + 1 passes would be needed.  The host then knows the deepest
+ *   level, and bc_back is a fixed list of max(deepest - 1, 0) launches, l = deepest - 1 down to 1, queued back to back with
+ *   no round trip: each takes slice l from levelPtr on the device, computes delta by the rule and adds it to d_bc[u] with
+ *   plain stores -- only u's own group of lanes ever writes bc[u].  bc_finish, once, copies d_level and d_sigma.  Nothing
+ *   spins, nothing waits for another workgroup; the only atomics are integer atomics on the workspace.  Grids are capped at
+ *   16 workgroups a CU with block loops.  Measured on one MI355X from one source (profiles/bc_case.md): uniform 2^20 x 8
+ *   1.80 ms in 10 levels, poisson27pt 128^3 7.59 ms in 128, the R-MAT triangle 3.58 ms in 7, road-like 2^20 58.8 ms in 2063
+ *   -- 1.1 to 1.36 times as many queue breadth-first calls of bhs_csr_sssp_device, and three to four orders of magnitude
+ *   below networkx on a host.  It LOSES on depth: a level is four launches over grids sized for n, 28 us a level on the
+ *   road-like graph; and 64 sources cost 64 times one (113 ms to 2.77 s), because several sources are not batched into one
+ *   pass.
+ * Synchronous on the handle's stream, needs no bound data, leaves the handle as it was (a workspace of its own: 2 n doubles
+ *   and 3 n + 2 ints).  ms_out (may be NULL): device time of the call, the round trips included.                       */
+#define BHS_BC_ACCUMULATE 1
+BHS_API int bhs_csr_betweenness_device(bhs_handle *h, int n,
+        int nnzG, const int *d_rowPtrG, const int *d_colIndG /* out-edges: G(i, j) is an edge i -> j */,
+        int nnzT, const int *d_rowPtrT, const int *d_colIndT /* in-edges: T = G^T; the SAME arrays as G for an undirected graph */,
+        int nsrc, const int *d_sources /* processed in this order; repeats count again */,
+        int flags /* BHS_BC_ACCUMULATE or 0 */,
+        double *d_bc /* out (in/out under ACCUMULATE): n doubles */,
+        int *d_level, double *d_sigma /* out, may be NULL: n each, of the LAST source */,
+        int *reached_out /* may be NULL */, int *passes_out /* may be NULL: a multiple of 8 per source */,
+        double *ms_out /* may be NULL */);
+
 /* ---- spanning forest --------------------------------------------------------
  * The minimum (or maximum) spanning forest of the graph that an n x n matrix A stores, by Boruvka rounds on the device: for
  * network design, as the spanning tree under a support-graph or tree preconditioner (the MAXIMUM forest of |a_ij| is the
